@@ -8,6 +8,12 @@ before the timed region.  N>1: one process per GPU (torch.distributed.run), ever
 own B pairs (weak scaling, no data-path collective) and the step ends with the RCCL all-gather
 that collects the terminal scores Vt from all ranks (--gather e also gathers E).
 
+A plain run sets up, warms up, times exactly --steps steps and prints the headline fields (`metric`, `value`, `unit`,
+`ms_per_step` = wall time of the timed steps / --steps, `dtype`, `config`, ...).  Everything else -- `kernel_ms` and
+`roofline`, `cpu_baseline`, `direct_cotangent`, `no_skip`, `pipelined_walk`, `clocks`, the E / path gathers of N > 1,
+`scores_roofline` / `scores_torch_baseline` -- is measured after the timed region with --full only.
+--dump-outputs DIR writes what the last timed step returned (dump_outputs).
+
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel of the mode (the one with the longest
 mean launch; sdp_fwd_kernel in the headline mode): algorithmic bytes (12 B per cell-update for the forward
 and backward sweeps, 32 B for each adjoint sweep; flops on the matrix pipe when the scores
@@ -56,9 +62,19 @@ def parse():
     ap.add_argument("--D", type=int, default=512, help="embedding width of --mode scores+dp (reference default n_embed)")
     ap.add_argument("--gather", choices=["vt", "e", "paths", "none"], default="vt")
     ap.add_argument("--e-chunks", type=int, default=1, help="pieces of the backward sweep / E gather when E is gathered (1 = one collective after the sweep)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-pairs", type=int, default=256, help="pairs in the CPU-baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline")
+    ap.add_argument("--cpu-pairs", type=int, default=256, help="(--full) pairs in the CPU-baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else: per-kernel launch times and the roofline, the CPU "
+                         "baseline, the secondary figures (direct cotangent, no_skip, pipelined walk, E / path gathers), clocks. "
+                         "Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64; batch-shaped "
+                         "arrays larger than the budget are cut to the same seeded sample of pairs (dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 class KernelTimer:
@@ -222,6 +238,37 @@ def cpu_baseline(args):
     return out
 
 
+DUMP_BYTES = 48 << 20   # budget of --dump-outputs (all files together)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(outputs, directory, B):
+    """--dump-outputs: every array of `outputs` (name -> tensor) as DIR/<name>.npy.  Floating arrays keep their precision
+    (float32 / float64), integer ones are written as float64 (exact).  When the whole set exceeds DUMP_BYTES, the arrays
+    whose first axis is the batch are cut to the same pairs: a sorted sample drawn with numpy's default_rng(DUMP_SEED),
+    as many pairs as fit the budget -- identical from run to run for the same arguments."""
+    arrs = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        arrs[name] = (t, np.float64 if t.dtype == torch.float64 or not t.is_floating_point() else np.float32)
+    size = lambda t, dt: t.numel() * np.dtype(dt).itemsize
+    batched = {k for k, (t, _) in arrs.items() if t.dim() >= 1 and t.shape[0] == B}
+    total = sum(size(t, dt) for t, dt in arrs.values())
+    pairs = None
+    if total > DUMP_BYTES and batched:
+        fixed = sum(size(t, dt) for k, (t, dt) in arrs.items() if k not in batched)
+        per_pair = sum(size(t, dt) for k, (t, dt) in arrs.items() if k in batched) / B
+        k = max(1, min(B, int((DUMP_BYTES - fixed) // per_pair)))
+        pairs = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=k, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    for name, (t, dt) in arrs.items():
+        if pairs is not None and name in batched:
+            t = t.index_select(0, torch.from_numpy(pairs).to(t.device))
+        np.save(os.path.join(directory, f"{name}.npy"), t.cpu().numpy().astype(dt, copy=False))
+    how = f"pairs {len(pairs)} of {B} (default_rng({DUMP_SEED}))" if pairs is not None else "whole"
+    print(f"[bench] outputs of the last timed step -> {directory}: {', '.join(sorted(arrs))} ({how})", file=sys.stderr, flush=True)
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: re-run this script under torch.distributed.run with one
     rank per GPU of this node (RCCL over xGMI), rendezvous on 127.0.0.1.  Fails loudly if the node has fewer
@@ -314,7 +361,12 @@ def main():
 
     walk = {"stream": None}
 
+    def aligned(out):
+        """what align() hands its caller on this rank: the scores (all ranks' when gathered) and this rank's E"""
+        return {"Vt": out["Vt"] if out["Vt"] is not None else out["Vt_local"], "E": out["E_local"]}
+
     def step():
+        """one step; -> the arrays its caller receives (name -> tensor; --dump-outputs writes those of the last timed step)"""
         if mce is not None:
             t = theta.detach().requires_grad_(True)
             a = A.detach().requires_grad_(True)
@@ -323,34 +375,38 @@ def main():
             else:
                 loss = mce(Yt, dec.decode(t, a), xl, yl, Gm)
             loss.backward()
-            return t.grad
+            return {"loss": loss, "theta_grad": t.grad, "A_grad": a.grad}
         if args.mode == "scores+dp":
             th, ga = alignment_scores(*emb)     # one MFMA launch: both GEMMs + softplus / logsigmoid
-            return aligner.align(th, ga)["E_local"]
+            return aligned(aligner.align(th, ga))
         if args.mode == "fwdbwd":
             out = aligner.align(theta, A)      # Vt = dec(theta, A); Vt.sum().backward(); all-gather Vt under the backward sweep
-            return out["E_local"]
+            return aligned(out)
         if args.mode == "align+traceback":     # inference: the alignment matrix and its arg-max walk (alignment.py:165-170, batched)
             out = aligner.align(theta, A)
+            res = aligned(out)
             if out.get("paths") is not None:
-                return out["paths"]
+                res["path_states"], res["path_counts"] = out["paths"]
+                return res
             E = out["E_local"]
             ws = walk["stream"]
             if ws is None:
-                return eng.traceback(E)
+                res["path_states"], res["path_counts"] = eng.traceback(E)
+                return res
             # (secondary figure `pipelined_walk`: the walk of this batch on a second stream, beside the sweeps of the next batch)
             ws.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(ws):
                 paths = eng.traceback(E)
             E.record_stream(ws)   # the allocator must not hand E's memory to the next step before the walk has read it
-            return paths
+            res["path_states"], res["path_counts"] = paths
+            return res
         t = theta.detach().requires_grad_(True)
         a = A.detach().requires_grad_(True)    # decode() differentiates w.r.t. (theta, A) like the reference
         aln = dec.decode(t, a)                 # forward + backward kernels (create_graph)
         # synthetic loss <aln, Z> as one dot product (forward: one reduction; backward: one scaling of Z) instead of
         # mul + sum (three elementwise kernels): the framework's share of the step, not the sweeps'
         torch.dot(aln.reshape(-1), Zl.reshape(-1)).backward()   # adjoint forward + adjoint backward kernels
-        return t.grad
+        return {"aln": aln, "theta_grad": t.grad, "A_grad": a.grad}
 
     def fence():
         torch.cuda.synchronize()
@@ -361,18 +417,22 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    def timed(nsteps):
+    last = {}
+
+    def timed(nsteps, keep=False):
         """EXACTLY nsteps steps between two fences; -> (wall seconds, max over ranks; ms per step between two events).
 
         ONE pair of events around the whole loop, not one per step: an event record between two dependent kernels costs the
         stream ~6 us (rocprofv3 kernel trace of this loop with a record after every step: a 6.0-6.3 us hole in front of every
-        forward sweep, none without; tools/gap_probe.py) -- 2 % of a 0.32 ms step spent on the measurement itself."""
+        forward sweep, none without; tools/gap_probe.py) -- 2 % of a 0.32 ms step spent on the measurement itself.
+        keep: what the last step returned is kept in `last["outputs"]` (--dump-outputs)."""
         m0, m1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         fence()
         t0 = time.perf_counter()
         m0.record()
-        for i in range(nsteps):
+        for i in range(nsteps - 1):
             step()
+        out = step()
         m1.record()
         fence()
         dt = time.perf_counter() - t0
@@ -380,9 +440,11 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if keep:
+            last["outputs"] = out
         return dt, m0.elapsed_time(m1) / nsteps
 
-    elapsed, ms_per_step_events = timed(args.steps)   # the headline: nothing but the steps between the two fences
+    elapsed, ms_per_step_events = timed(args.steps, keep=True)   # the headline: nothing but the steps between the two fences
 
     def kernel_loop(tm):
         """per-kernel mean launch times: KSTEPS more steps of the same loop, right behind the timed region (the GPU never idles in
@@ -400,7 +462,47 @@ def main():
     cells = B * N * M if args.variant == "nw" else B * (N - 1) * (M - 1)
     per_step_updates = (4 if args.mode.startswith("train") else 2) * cells
     value = world * per_step_updates * args.steps / elapsed
-    ms = kernel_loop(timer)
+
+    def headline():
+        """the fields of the result line that every run carries: the timed steps' own figures and what was timed"""
+        line = {
+            "metric": {"fwdbwd": "DP cell-updates/sec (fwd+bwd)", "align+traceback": "DP cell-updates/sec (fwd+bwd + batched traceback)", "train": "DP cell-updates/sec (train: fwd+bwd+adjoint pair)",
+                       "scores+dp": "DP cell-updates/sec (scores from embeddings + fwd+bwd)",
+                       "train-mce": "DP cell-updates/sec (train: decode + MatrixCrossEntropy + backward)",
+                       "train-mce-fused": "DP cell-updates/sec (train: fused decode + MatrixCrossEntropy + backward)"}[args.mode],
+            "value": value, "unit": "cell-updates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "ms_per_step_events": ms_per_step_events,
+            "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{args.variant.upper()} soft-DP " + {"fwdbwd": "fwd+bwd", "align+traceback": "fwd+bwd+traceback", "train": "decode+loss.backward",
+                                                                        "scores+dp": f"scores(D={args.D})+fwd+bwd", "train-mce": "decode+MatrixCrossEntropy.backward",
+                                                                        "train-mce-fused": "fused decode+MatrixCrossEntropy.backward"}[args.mode] +
+                                   f", B={B} per GPU, N={N}, M={M}, random theta/A "
+                                   + ("(BASELINE.json configs[1])" if world == 1 else
+                                      f"(BASELINE.json configs[4] sharding: {B * world} pairs over {world} GPUs)"),
+                       "global_batch": B * world, "N": N, "M": M, "variant": args.variant,
+                       "parallelism": f"batch-sharded x{world}", "gather": args.gather if multi else "none",
+                       "backend": ("rccl" if backend == "nccl" else backend + (" (ranks share one GPU: test mode)" if shared else "")) if multi else "none",
+                       "arith": "fwd: scaled exp-domain f32 (exact power-of-two rescaling); bwd: f32; adjoint pair: f64 carries; f32 storage",
+                       "data_dependent": "the backward sweep does not run 32-step chunks whose outputs are exactly +0 nor read their state "
+                                         "(bit-identical E; 47 % of E's cells, 29 % of the chunks on this data: DESIGN.md 3.8); the forward sweep "
+                                         "-- the kernel the roofline is quoted on -- does all of its work"},
+        }
+        if args.mode == "fwdbwd":
+            line["config"]["step"] = "Vt = dec(theta, A); Vt.sum().backward()  (public API, autograd, .grad accumulation included)"
+        return line
+
+    ms = kernel_loop(timer) if args.full else None   # (--full: right behind the timed region, before anything else)
+    if args.dump_outputs and rank == 0:
+        dump_outputs({k: v for k, v in last["outputs"].items() if v is not None}, args.dump_outputs, B)
+    last.clear()
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     no_skip = clocks = pipelined = None
 
@@ -446,28 +548,8 @@ def main():
                 per_kernel[k] = {"launch_ms": v_ms, "algorithmic_bytes_per_launch": ab, "frac": ab / (v_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                  "traffic": tr, "real_frac": (tr / (v_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if tr else None}
             step_algo_bytes = cells * sum(algo_bytes_per_cell(k) for k in per_kernel) if per_kernel else per_step_updates * ALGO_BYTES_PER_CELL_UPDATE
-            line = {
-                "metric": {"fwdbwd": "DP cell-updates/sec (fwd+bwd)", "align+traceback": "DP cell-updates/sec (fwd+bwd + batched traceback)", "train": "DP cell-updates/sec (train: fwd+bwd+adjoint pair)",
-                           "scores+dp": "DP cell-updates/sec (scores from embeddings + fwd+bwd)",
-                           "train-mce": "DP cell-updates/sec (train: decode + MatrixCrossEntropy + backward)",
-                           "train-mce-fused": "DP cell-updates/sec (train: fused decode + MatrixCrossEntropy + backward)"}[args.mode],
-                "value": value, "unit": "cell-updates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": elapsed / args.steps * 1e3, "ms_per_step_events": ms_per_step_events,
-                "higher_is_better": True, "scaling": "weak",
-                "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-                "config": {"workload": f"{args.variant.upper()} soft-DP " + {"fwdbwd": "fwd+bwd", "align+traceback": "fwd+bwd+traceback", "train": "decode+loss.backward",
-                                                                            "scores+dp": f"scores(D={args.D})+fwd+bwd", "train-mce": "decode+MatrixCrossEntropy.backward",
-                                                                            "train-mce-fused": "fused decode+MatrixCrossEntropy.backward"}[args.mode] +
-                                       f", B={B} per GPU, N={N}, M={M}, random theta/A "
-                                       + ("(BASELINE.json configs[1])" if world == 1 else
-                                          f"(BASELINE.json configs[4] sharding: {B * world} pairs over {world} GPUs)"),
-                           "global_batch": B * world, "N": N, "M": M, "variant": args.variant,
-                           "parallelism": f"batch-sharded x{world}", "gather": args.gather if multi else "none",
-                           "backend": ("rccl" if backend == "nccl" else backend + (" (ranks share one GPU: test mode)" if shared else "")) if multi else "none",
-                           "arith": "fwd: scaled exp-domain f32 (exact power-of-two rescaling); bwd: f32; adjoint pair: f64 carries; f32 storage",
-                           "data_dependent": "the backward sweep does not run 32-step chunks whose outputs are exactly +0 nor read their state "
-                                             "(bit-identical E; 47 % of E's cells, 29 % of the chunks on this data: DESIGN.md 3.8); the forward sweep "
-                                             "-- the kernel the roofline is quoted on -- does all of its work"},
+            line = headline()
+            line.update({
                 "kernel_ms": ms,
                 "kernel_ms_how": f"HIP event pairs on the launch stream around every 4th launch of each kernel, in {KSTEPS} steps of the same loop run right behind the timed region; the timed region itself holds no event record besides the pair around all of it",
                 "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -488,7 +570,7 @@ def main():
                              # the chip's own ceilings for bare streams of 1 KB per wave-instruction, one wave per SIMD (tools/ubench/
                              # vmemissue.hip, profiles/r06_ubench_vmemissue.txt): what "memory-bound" means on this part
                              "measured_stream_ceilings_GBs": {"loads": 7000.0, "stores": 5400.0, "fwd_mix": 5050.0}},
-            }
+            })
             if pipelined is not None:
                 line["pipelined_walk"] = pipelined
             if no_skip is not None:
@@ -536,8 +618,6 @@ def main():
                                                  "F.logsigmoid(torch.einsum(...gx, gy)) (deepblast/alignment.py:122-123), fp32, this box"}
             if line["roofline"] is None:
                 line["roofline"] = line.get("scores_roofline")
-            if args.mode == "fwdbwd":
-                line["config"]["step"] = "Vt = dec(theta, A); Vt.sum().backward()  (public API, autograd, .grad accumulation included)"
             if direct is not None:
                 # the same two sweeps asked for with torch.autograd.grad(Vt, theta, ones): no sum / fill kernels, no .grad
                 line["direct_cotangent"] = {"ms_per_step": direct * 1e3, "value": world * per_step_updates / direct,

@@ -162,9 +162,9 @@ def _run_bench(nproc, extra_args, extra_env, timeout):
 def test_bench_eight_ranks_flow_on_one_gpu():
     """`bench.py --gpus 8` exactly as the driver launches it (torch.distributed.run, 8 ranks, default shape = 256 pairs of
     512 x 512 per rank = BASELINE configs[4]) -- except that the ranks share GPU 0 and gather over gloo: exactly one JSON
-    line, n_gpus 8, global batch 2048, the secondary gather figures present."""
+    line, n_gpus 8, global batch 2048, and with --full the secondary gather figures present."""
     # (--e-chunks 4: the E gather in pieces under the backward sweep is exercised here; the default is one collective since round 5)
-    r = _run_bench(8, ["--steps", "2", "--warmup", "1", "--e-chunks", "4"], {}, timeout=1500)
+    r = _run_bench(8, ["--steps", "2", "--warmup", "1", "--e-chunks", "4", "--full"], {}, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -180,7 +180,7 @@ def test_bench_eight_ranks_flow_on_one_gpu():
 def test_bench_primary_line_survives_a_hung_secondary():
     """A rank that never reaches the collective of a SECONDARY measurement (here: on purpose) must not cost the primary
     figure: the watchdog lets rank 0 print the one JSON line without the secondary fields, and every rank exits."""
-    r = _run_bench(2, ["--steps", "2", "--warmup", "1", "--B", "24", "--N", "200", "--M", "180"],
+    r = _run_bench(2, ["--steps", "2", "--warmup", "1", "--B", "24", "--N", "200", "--M", "180", "--full"],
                    {"BENCH_TEST_HANG_RANK": "1", "BENCH_WATCHDOG_S": "20"}, timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, (r.stdout, r.stderr[-2000:])
