@@ -3,6 +3,8 @@
 Tolerances (BASELINE.json north_star "<= 1e-4 fp32"):
   E, Ed : max-abs <= 1e-4 (E in [0,1]); Ed scaled by max(1, max|Ed_ref|)
   Vt,Vtd: |d| <= 1e-4 * max(1, |ref|)   (fp32 cannot hold Vt ~ 1000 to 1e-4 absolute)
+Second order (check_second_order): plain max-abs Ed and Vtd within TOL of the fp32 reference, or else -- the exemption, where
+the fp32 reference's own roundings are the noise -- within F64_TOL of the reference run in float64.
 """
 import os
 import sys
@@ -16,6 +18,13 @@ if ROOT not in sys.path:
 from oracle import oracle  # noqa: E402  (test infrastructure)
 
 TOL = 1e-4
+# engine against the reference run in float64 (first screen: <= 1.4e-5 on the corners measured there; README: <= 2e-5)
+F64_TOL = 2e-5
+# Two quantities held to float64 by bounds of their own ("Against float64"), in the named long / steep cases:
+# Vtd = <Z, E> sums the exact state's per-cell error of E (<= 7e-6) over the whole pair, where |Vtd| may be < 1 (measured 3.1e-5
+# and 3.5e-5); plain Ed on pairs of ~4000 steps with max|Ed| ~ 40 (measured 7.3e-5; scaled, 1.7e-6, it is within F64_TOL)
+F64_TOL_VTD_SUM = 5e-5
+F64_TOL_ED_LONG = TOL
 
 
 def rel_err(got, ref):
@@ -45,12 +54,14 @@ def oracle_all(theta, A, Et, Z, variant, ZA=None, omp=True):
 
 def oracle_lens(theta, A, Et, Z, variant, lens, threads=1):
     """Lengths-aware semantics = per-item sliced calls (deepblast/alignment.py:165-170).  `threads` > 1 runs the
-    items on a thread pool (the oracle is a C call that releases the GIL): whole config-sized batches in seconds."""
+    items on a thread pool (the oracle is a C call that releases the GIL): whole config-sized batches in seconds.
+    The oracle runs in theta's dtype (float32 or float64) and the outputs keep it."""
     B, N, M = theta.shape
-    out = {"Vt": np.zeros(B, np.float32), "E": np.zeros((B, N, M), np.float32)}
+    dt = np.dtype(theta.dtype)
+    out = {"Vt": np.zeros(B, dt), "E": np.zeros((B, N, M), dt)}
     if Z is not None:
-        out["Ed"] = np.zeros((B, N, M), np.float32)
-        out["Vtd"] = np.zeros(B, np.float32)
+        out["Ed"] = np.zeros((B, N, M), dt)
+        out["Vtd"] = np.zeros(B, dt)
 
     def one(b):
         n, m = int(lens[b, 0]), int(lens[b, 1])
@@ -155,3 +166,43 @@ def compare(got, ref, plain=True):
         errs["Ex"] = abs_err(got["Ex"], ref["E"])
         errs["Vtx"] = rel_err(got["Vtx"], ref["Vt"])
     return errs
+
+
+def f64(x):
+    """x promoted to float64 (exact), None stays None: the inputs of a float64 oracle run."""
+    return None if x is None else np.asarray(x).astype(np.float64)
+
+
+def oracle_f64(theta, A, Et, Z, variant, lens=None, ZA=None, threads=1):
+    """The reference in float64 on the same (fp32) inputs: oracle_lens with per-pair lengths, oracle_all without."""
+    if lens is not None:
+        assert ZA is None, "oracle_lens has no ZA"
+        return oracle_lens(f64(theta), f64(A), f64(Et), f64(Z), variant, lens, threads=threads)
+    return oracle_all(f64(theta), f64(A), f64(Et), f64(Z), variant, ZA=f64(ZA), omp=threads > 1)
+
+
+def check_second_order(got, ref32, ref64_fn, what="", ed_f64_tol=F64_TOL, vtd_f64_tol=F64_TOL):
+    """The one rule for second-order results (Ed as a PLAIN max-abs).
+
+    Pass: plain max|Ed - Ed_ref| <= TOL and Vtd (rel_err) <= TOL against the fp32 reference `ref32`.
+    Otherwise the exemption, checked and not assumed: `ref64_fn()` (called only then) gives the reference run in float64 on the
+    same inputs, and the engine must be within F64_TOL of it on plain Ed and on Vtd -- which by the triangle inequality means
+    the fp32 reference itself is more than TOL - F64_TOL from float64 there.  Anything else fails (AssertionError naming all
+    three distances: engine vs fp32, engine vs float64, fp32 vs float64).  `ed_f64_tol` / `vtd_f64_tol`: the named cases' own
+    bounds against float64 (F64_TOL_ED_LONG, F64_TOL_VTD_SUM; never above TOL).
+    -> record: {"status": "pass" | "exempt", "Ed": plain vs fp32, "Vtd": vs fp32, and for an exemption "Ed64", "Vtd64" (engine
+    vs float64), "noise_Ed", "noise_Vtd" (fp32 reference vs float64)}."""
+    has_vtd = "Vtd" in got   # (a caller with no Vtd to compare -- a loss gradient -- leaves it out of all three dicts)
+    assert ed_f64_tol <= TOL and vtd_f64_tol <= TOL
+    ed, vtd = abs_err(got["Ed"], ref32["Ed"]), rel_err(got["Vtd"], ref32["Vtd"]) if has_vtd else 0.0
+    rec = {"status": "pass", "Ed": ed, "Vtd": vtd}
+    if np.isfinite(ed) and np.isfinite(vtd) and ed <= TOL and vtd <= TOL:
+        return rec
+    ref64 = ref64_fn()
+    rec.update(status="exempt", Ed64=abs_err(got["Ed"], ref64["Ed"]), Vtd64=rel_err(got["Vtd"], ref64["Vtd"]) if has_vtd else 0.0,
+               noise_Ed=abs_err(ref32["Ed"], ref64["Ed"]), noise_Vtd=rel_err(ref32["Vtd"], ref64["Vtd"]) if has_vtd else 0.0)
+    ok = all(np.isfinite(rec[k]) for k in ("Ed64", "Vtd64")) and rec["Ed64"] <= ed_f64_tol and rec["Vtd64"] <= vtd_f64_tol
+    assert ok, (f"{what} second order: engine vs fp32 reference Ed {ed:.3e} Vtd {vtd:.3e} (bound {TOL:g}); engine vs float64 "
+                f"Ed {rec['Ed64']:.3e} Vtd {rec['Vtd64']:.3e} (bounds {ed_f64_tol:g} / {vtd_f64_tol:g}); fp32 reference vs float64 Ed {rec['noise_Ed']:.3e} "
+                f"Vtd {rec['noise_Vtd']:.3e}; max|Ed_ref| = {float(np.max(np.abs(ref32['Ed']))) if np.size(ref32['Ed']) else 0.0:.2f}")
+    return rec

@@ -168,3 +168,41 @@ def test_launch_plan_policy(lib):
     # the long-M fallback: throughput builds do not fit with 2048 columns
     assert _plan(lib, 0, 256, 512, 2048)[0] == 6 and _plan(lib, 1, 256, 512, 2048)[0] in (1, 4, 36)
     assert _plan(lib, 1, 256, 512, 2048, exact=1)[0] in (7, 8)
+
+
+# sdp_api.hip general_id (and the parts twins, 21-24 -> 25-28): the general-pitch instantiation a launch takes in place of the
+# build sdp_plan reports when M is not a multiple of 32
+GENERAL_PITCH_ID = {0: 11, 37: 11, 1: 12, 3: 14, 4: 15, 7: 18, 8: 19, 9: 20, 38: 20, 21: 25, 22: 26, 23: 27, 24: 28}
+
+
+def _exact_state_builds(lib, B, N, M, lens):
+    """{(pass, kernel id, waves)} of the four passes of the training path (exact state) on a 256-CU device"""
+    out = set()
+    for pass_ in range(4):
+        kid, _, waves, _ = _plan(lib, pass_, B, N, M, lens, exact=1)
+        out.add((pass_, kid if M % 32 == 0 else GENERAL_PITCH_ID.get(kid, kid), waves))
+    return out
+
+
+def test_second_order_cases_reach_every_exact_state_build(lib):
+    """tests/test_parity_gpu.py::test_second_order_tracks_float64 holds the exact-state results to the float64 reference; its
+    cases must reach every (pass, build, waves) the launch policy gives the exact-state passes over a grid of shapes -- batch
+    sizes across the latency / throughput / two-wave / parts thresholds, 1 to 64+ strips, M on and off the 32 grid up to the
+    column limit, with and without per-pair lengths.  A build or wave count added later with no case for it fails here."""
+    from test_parity_gpu import F64_CASES
+    Bs = [1, 2, 3, 8, 40, 64, 72, 73, 74, 100, 127, 128, 200, 256, 257, 300, 512, 513, 600, 1024]
+    Ns = [1, 2, 31, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 320, 321, 384, 385, 448, 449, 512, 513, 576, 577, 640,
+          768, 769, 1024, 1025, 2048, 4097]
+    Ms = [1, 7, 31, 32, 33, 64, 65, 96, 100, 512, 513, 960, 1024, 1025, 1500, 1536, 2000, 2048]
+    reachable = set()
+    for B in Bs:
+        for N in Ns:
+            for M in Ms:
+                for lens in (0, 1):
+                    reachable |= _exact_state_builds(lib, B, N, M, lens)
+    covered = set()
+    for c in F64_CASES:
+        covered |= _exact_state_builds(lib, c[0], c[1], c[2], int(c[4]))
+    assert not reachable - covered, f"exact-state builds no case of F64_CASES reaches: {sorted(reachable - covered)}"
+    # (the grid does see all of them: forward 5 / 40 / adjoint forward at 1-8 waves, the throughput builds at 1-4, the parts twins)
+    assert {(0, 5, 8), (0, 40, 5), (1, 19, 8), (2, 2, 8), (3, 14, 4), (0, 22, 4), (0, 26, 4), (1, 24, 4), (1, 28, 4), (0, 20, 2)} <= reachable

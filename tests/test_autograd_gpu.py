@@ -47,10 +47,21 @@ def test_quirks_and_double_backward(golden_dir, kind):
     (aln * Z).sum().backward()
     assert parity.abs_err(theta.grad.cpu().numpy(), d["Ed"], scale=True) <= parity.TOL
     assert A.grad is None                                      # nw.py:386
+    ed = theta.grad.cpu().numpy()
     et = torch.from_numpy(d["Et"]).cuda().requires_grad_()
     g, _ = torch.autograd.grad(dec(theta, A), (theta, A), et, create_graph=True)
     (vtd,) = torch.autograd.grad((g * Z).sum(), et)
     assert parity.rel_err(vtd.cpu().numpy(), d["Vtd_et"]) <= parity.TOL
+    # the plain rule as well (parity.check_second_order); the fixtures are fp32, the float64 reference is the C oracle's f64 path
+    # on the same inputs (Ed from decode(): Et = 1; Vtd with the fixture's Et)
+    variant = {"nw": 0, "sw": 1}[kind]
+
+    def ref64():
+        r1 = parity.oracle_f64(d["theta"], d["A"], None, d["Z"], variant)
+        r2 = parity.oracle_f64(d["theta"], d["A"], d["Et"], d["Z"], variant)
+        return {"Ed": r1["Ed"], "Vtd": r2["Vtd"]}
+    parity.check_second_order({"Ed": ed, "Vtd": vtd.detach().cpu().numpy()}, {"Ed": d["Ed"], "Vtd": d["Vtd_et"]}, ref64,
+                              f"double backward {kind}")
 
 
 @pytest.mark.parametrize("kind", ["nw", "sw"])

@@ -41,6 +41,7 @@ def test_collate_decode_loss_backward(golden_dir, variant):
 
     # reference procedure, pair by pair
     ref_loss, ref_grad, ref_aln = 0.0, np.zeros((B, N, M)), np.zeros((B, N, M), np.float32)
+    seeds = []   # per pair: the loss gradient the adjoint pair is seeded with (for the float64 reference below)
     eps = 3e-8
     for b in range(B):
         n, m = xl[b], yl[b]
@@ -56,9 +57,19 @@ def test_collate_decode_loss_backward(golden_dir, variant):
         Z = np.where(g & inside, -(y / pr - (1 - y) / (1 - pr)) / (cnt * B), 0.0).astype(np.float32)
         Ed, _, _ = oracle.double_backward(Q, Ef, Z[None])
         ref_grad[b, :n, :m] = Ed[0]
+        seeds.append(Z)
     assert parity.abs_err(aln.detach().cpu().numpy(), ref_aln) <= parity.TOL
     assert abs(float(loss) - ref_loss) <= 1e-4 * max(1.0, abs(ref_loss))
     assert parity.abs_err(t.grad.cpu().numpy(), ref_grad, scale=True) <= parity.TOL
+
+    def ref64():   # the same procedure in float64 (the C oracle's f64 path), seeded with the same loss gradient
+        g64 = np.zeros((B, N, M))
+        for b in range(B):
+            n, m = xl[b], yl[b]
+            _, _, Q, Ef = oracle.fwd_bwd(parity.f64(theta[b:b + 1, :n, :m]), parity.f64(A[b:b + 1, :n, :m]), None, variant)
+            g64[b, :n, :m] = oracle.double_backward(Q, Ef, parity.f64(seeds[b][None]))[0][0]
+        return {"Ed": g64}
+    parity.check_second_order({"Ed": t.grad.cpu().numpy()}, {"Ed": ref_grad}, ref64, f"collate -> decode -> loss, variant {variant}")
     # nothing leaks outside a pair's own block
     for b in range(B):
         assert not t.grad[b, xl[b]:, :].any() and not t.grad[b, :, yl[b]:].any()
