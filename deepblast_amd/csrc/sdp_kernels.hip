@@ -323,6 +323,7 @@ constexpr int WB = 16;  // steps per frame (every chunk length is a multiple)
 constexpr int FRAME_NONE = (int)0x80000000;  // published chunk is not in one frame (per-value exponents apply)
 constexpr float EXP_ONE_A = 0.5f;
 constexpr int EXP_ONE_E = 1;
+constexpr int ZERO_E = -(1 << 29);   // the exponent a zero operand takes in the normalised forward form: below every real one
 
 template <int KIND>
 __device__ __forceinline__ u64 edge_zero()
@@ -1603,7 +1604,15 @@ __device__ __forceinline__ void sweep(const Params &p)
                             const int kai = ma ? __builtin_amdgcn_frexp_expf(ea2) : (int)ka;
                             const float ua = __uint_as_float(dpp_i32<DPP_IN>((int)lo32(bcv[j]), __float_as_int(cy.xa)));
                             const int ue = dpp_i32<DPP_IN>((int)hi32(bcv[j]), cy.xe);
-                            const int ex = ue + kai, ey = cy.xe + kai, ed = cy.de;
+                            // A value of exactly 0 (a cell nothing reaches) keeps the exponent it was formed with, er + kti, and
+                            // along a run of such cells that exponent climbs by kti + kai per step -- faster than any real value,
+                            // whose mantissa products take bits off.  Once it is more than 149 bits above the real operands of a
+                            // reachable cell it won er, the real operands underflowed, ssum was 0 and the cell -- and every cell
+                            // after it -- turned unreachable: Vt = -inf on a 200 x 2048 NW pair with positive and forbidden gap
+                            // scores (tests/test_parity_gpu.py::test_first_order_positive_and_forbidden_gaps_on_long_rows).  A
+                            // zero operand never sets the scale.
+                            const int ex = ua != 0.f ? ue + kai : ZERO_E, ey = cy.xa != 0.f ? cy.xe + kai : ZERO_E;
+                            const int ed = cy.da != 0.f ? cy.de : ZERO_E;
                             const int er = max(max(ex, ey), ed);
                             const float u = __builtin_amdgcn_ldexpf(ua, ex - er);
                             const float l = __builtin_amdgcn_ldexpf(cy.xa, ey - er);
@@ -1621,7 +1630,8 @@ __device__ __forceinline__ void sweep(const Params &p)
                                 // steep scores are where paths saturate -- a packed weight left at 1 - 2^-23 instead of 1
                                 // loses 1.7e-8 of E per step on average (7e-5 over the 4096 steps of a 2048 x 2048
                                 // problem).  Which blocks run this form does not depend on the build (wf_skip counts
-                                // blocks, not chunks), so results stay bit-identical across wave counts.
+                                // blocks, not chunks), so results are meant to stay bit-identical across wave counts (one measured
+                                // exception between the cleaning twins 37 and 39: DESIGN.md 7, "First order on the packed state").
                                 q_sharpen(qq.x, qq.y, d * rinv);
                                 if constexpr (ABL_NOSTORE) { keep(qq.x); keep(qq.y); }
                                 else if constexpr (QX) store_state(tb, j, qq);

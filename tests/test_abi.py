@@ -206,3 +206,105 @@ def test_second_order_cases_reach_every_exact_state_build(lib):
     assert not reachable - covered, f"exact-state builds no case of F64_CASES reaches: {sorted(reachable - covered)}"
     # (the grid does see all of them: forward 5 / 40 / adjoint forward at 1-8 waves, the throughput builds at 1-4, the parts twins)
     assert {(0, 5, 8), (0, 40, 5), (1, 19, 8), (2, 2, 8), (3, 14, 4), (0, 22, 4), (0, 26, 4), (1, 24, 4), (1, 28, 4), (0, 20, 2)} <= reachable
+
+
+# The general-pitch build a packed-state launch takes in place of the one sdp_plan reports (sdp_api.hip: plan): general_id, the parts
+# twins 21 / 23 -> 25 / 27 -- and the pipelined backward build 36, which plan only picks in place of build 1, so a general-pitch
+# launch that sdp_plan reports as 36 runs build 12
+PACKED_GENERAL_PITCH_ID = {0: 11, 37: 11, 1: 12, 36: 12, 4: 15, 21: 25, 23: 27}
+
+
+def _packed_state_builds(lib, B, N, M, lens, offset=0):
+    """{(pass, kernel id, waves)} of the forward and backward sweeps on the packed state (256 CUs), or the empty set where the
+    padded shape takes the exact state as a whole (sdp_api.hip: exact_for -- sdp_state_bytes then sizes the float2 state).  A
+    launch takes the general-pitch twin when M is not a multiple of 32 or a plane does not start on a 128-byte line (`offset`
+    floats: the cases of FIRST_ORDER_CASES offset theta, A and E alike)."""
+    if lib.sdp_state_bytes(B, N, M) == lib.sdp_state_d_bytes(B, N, M):
+        return set()
+    out = set()
+    for pass_ in (0, 1):
+        kid, _, waves, _ = _plan(lib, pass_, B, N, M, lens)
+        out.add((pass_, PACKED_GENERAL_PITCH_ID.get(kid, kid) if (M % 32 or offset % 32) else kid, waves))
+    return out
+
+
+def test_first_order_cases_reach_every_packed_state_build(lib):
+    """tests/test_parity_gpu.py::test_first_order_tracks_float64 holds the packed state's E and Vt to the float64 reference; its
+    cases must reach every (pass, build, waves) the launch policy gives the forward and backward sweeps on the packed state over a
+    grid of shapes -- batch sizes across the latency / throughput / pipelined / two-wave / parts thresholds, 1 to 32 strips, N on
+    and off the 64 grid, M on and off the 32 grid up to the column limit, with and without per-pair lengths, aligned and offset
+    planes.  A build or wave count added later with no case for it fails here, and names it."""
+    from test_parity_gpu import FIRST_ORDER_CASES
+    Bs = [1, 2, 3, 8, 40, 64, 72, 73, 74, 100, 127, 128, 200, 224, 225, 256, 257, 300, 384, 512, 513, 600, 768, 1024]
+    Ns = [1, 2, 31, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 320, 321, 384, 385, 448, 449, 512, 513, 576, 577, 640,
+          768, 769, 1020, 1022, 1023, 1024, 1025, 2048, 4097]
+    Ms = [1, 7, 31, 32, 33, 64, 65, 96, 100, 512, 513, 960, 1020, 1022, 1023, 1024, 1025, 1500, 1536, 2000, 2048]
+    reachable = set()
+    for B in Bs:
+        for N in Ns:
+            for M in Ms:
+                for lens in (0, 1):
+                    for offset in (0, 1):
+                        reachable |= _packed_state_builds(lib, B, N, M, lens, offset)
+    covered = set()
+    for c in FIRST_ORDER_CASES:
+        covered |= _packed_state_builds(lib, c[0], c[1], c[2], int(c[4]), c[9])
+    assert not reachable - covered, f"packed-state builds no case of FIRST_ORDER_CASES reaches: {sorted(reachable - covered)}"
+    assert not covered - reachable, f"cases reach builds the grid does not see (widen the grid): {sorted(covered - reachable)}"
+    # the grid does see the thin-margin builds: the pipelined backward sweep (36), the parts builds and their general-pitch twins,
+    # two waves per pair, every wave count of the latency builds
+    assert {(1, 36, 4), (0, 21, 4), (0, 25, 4), (1, 23, 4), (1, 27, 4), (0, 0, 2), (1, 1, 2), (0, 11, 2), (0, 6, 8), (0, 39, 8),
+            (1, 12, 8)} <= reachable
+    # ... and the cases reach the branches a key alone does not tell apart: two waves because of the batch size (more pairs than
+    # CUs, four strips and more), the column-limit fallback of a full batch to the latency forward builds (6, 39), 36 on an
+    # aligned batch
+    two_waves = [c for c in FIRST_ORDER_CASES if c[0] > 256 and c[1] > 192 and _plan(lib, 0, c[0], c[1], c[2], int(c[4]))[2] == 2]
+    assert len(two_waves) >= 2, two_waves
+    fallback = [c for c in FIRST_ORDER_CASES if c[2] == 2048 and _plan(lib, 0, c[0], c[1], c[2], int(c[4]))[0] in (6, 39)
+                and _plan(lib, 0, c[0], c[1], 1024, int(c[4]))[0] in (0, 37)]
+    fallback_ids = {_plan(lib, 0, c[0], c[1], c[2], int(c[4]))[0] for c in fallback}
+    for kid in (6, 39):
+        assert kid in fallback_ids, f"no full-batch case of FIRST_ORDER_CASES reaches the 2048-column fallback to build {kid}"
+    assert any(_plan(lib, 1, c[0], c[1], c[2], int(c[4]))[0] == 36 and not (c[2] % 32 or c[9]) for c in FIRST_ORDER_CASES)
+    # (the packed backward sweep's latency build 4 / 15 is NOT reachable by the policy on its own since round 5: the K = 32 build
+    #  runs eight waves and fits the column limit -- only a forced wave count above eight would take it)
+    assert not any(k[0] == 1 and k[1] in (4, 15) for k in reachable)
+    # shapes exact_for sends to the float2 state as a whole report exact-state builds, and are no packed build
+    assert _packed_state_builds(lib, 3, 2049, 2048, 0) == set() and _packed_state_builds(lib, 3, 40, 1024, 1) == set()
+
+
+def _variant_table():
+    """{kernel id: symbol} of the `case N: return {(const void *)SYMBOL, K, maxw, N};` lines of variant() in csrc/sdp_api.hip (and of
+    its `default:` line, which is build 4: the id is the last field of the Variant)"""
+    src = open(os.path.join(ROOT, "deepblast_amd", "csrc", "sdp_api.hip")).read()
+    body = re.search(r"\nVariant variant\(int id\)\n\{(.*?)\n\}\n", src, flags=re.S)
+    assert body, "variant() not found in sdp_api.hip"
+    table = {}
+    for label, sym, kid in re.findall(r"(case\s+\d+|default):\s*return\s*\{\s*\(const void \*\)\s*(\w+)\s*,[^{}]*?(\d+)\s*\};", body.group(1)):
+        assert label == "default" or int(label.split()[1]) == int(kid), (label, sym, kid)
+        assert int(kid) not in table, kid
+        table[int(kid)] = sym
+    assert len(table) == body.group(1).count("return {") and {0, 4, 36, 40} <= set(table), table
+    return table
+
+
+def test_kernel_names_are_the_builds_the_library_launches(monkeypatch):
+    """bench.py's per-kernel timers label a launch with Engine.KERNEL_NAMES[sdp_plan's id]: the table must name exactly the builds
+    of variant() -- no id of a build that is gone, none missing -- or a launch carries another kernel's name (or the default one)."""
+    from deepblast_amd._engine import HipEngine
+    assert HipEngine.KERNEL_NAMES == _variant_table()
+    # _label asks the library's own launch policy (sdp_plan) on the device's CU count
+    import torch
+
+    class _Props:
+        multi_processor_count = 256
+
+    monkeypatch.setattr(torch.cuda, "get_device_properties", lambda dev: _Props())
+    eng = HipEngine()
+    assert eng._label(0, 256, 500, 512, False, False, 0, "default") == "default"   # (no hook: no lookup)
+    eng.launch_hook = lambda name: None
+    assert eng._label(0, 256, 500, 512, False, False, 0, "default") == "sdp_fwd_c_kernel"
+    assert eng._label(0, 16, 512, 512, True, False, 0, "default") == "sdp_fwd_lat_c_kernel"
+    assert eng._label(0, 256, 512, 512, False, False, 0, "default") == "sdp_fwd_kernel"
+    assert eng._label(1, 256, 1024, 1024, False, False, 0, "default") == "sdp_bwd_pipe_kernel"
+    assert eng._label(0, 256, 512, 512, True, True, 0, "default") == "sdp_fwd_x_c_kernel"
