@@ -370,6 +370,23 @@ class HipEngine:
         _lib.check(rc, "sdp_traceback_rule_i32")
         return states, counts
 
+    def alignment_targets(self, codes, code_lens, lens, shape, dm, P, G, flags, status):
+        """Enqueue sdp_alignment_targets on the current stream (include/sdp.h): codes (B, L) uint8, code_lens (B,) int32,
+        lens (B, 2) int32 or None; dm / P fp32, G bool or fp32 (flags), each (B, N, M) or None; status (B,) int32."""
+        dev = self._dev(codes)
+        B, N, M = shape
+        for name, t in (("dm", dm), ("P", P), ("G", G)):
+            if t is not None and (t.shape != (B, N, M) or not t.is_contiguous() or t.device != codes.device):
+                raise ValueError(f"{name} must be a contiguous ({B}, {N}, {M}) tensor on {codes.device}")
+        with torch.cuda.device(dev), self._bracket("sdp_targets_kernel"):
+            rc = self.lib.sdp_alignment_targets(_ptr(codes), _ptr(code_lens), codes.shape[1], _ptr(lens), B, N, M, _ptr(dm),
+                                                _ptr(P), _ptr(G), flags, _ptr(status), dev, self._stream(dev))
+        _lib.check(rc, "sdp_alignment_targets")
+        return status
+
+    def targets_selftest(self, device=0):
+        _lib.check(self.lib.sdp_targets_selftest(device), "sdp_targets_selftest")
+
     def init(self, device=None):
         """Create the library's per-device state now (include/sdp.h: sdp_init) -- needed only before stream capture."""
         dev = torch.cuda.current_device() if device is None else device

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("SDP_LIB_PATH") or os.path.join(_HERE, "libsdp_hip.so"
 
 SDP_NW, SDP_SW = 0, 1
 SDP_NO_ZERO_SKIP, SDP_NO_FILL = 0x800, 0x10000   # include/sdp.h: flags of the backward sweeps
+SDP_TARGETS_GAP_MASK, SDP_TARGETS_G_F32 = 0x1, 0x2  # include/sdp.h: flags of sdp_alignment_targets
 
 _c_f32p = ctypes.c_void_p
 _c_i32p = ctypes.c_void_p
@@ -70,6 +71,10 @@ SIGNATURES = {
     "sdp_comm_all_gather_f32": (ctypes.c_int, [ctypes.c_void_p, _c_f32p, _c_f32p, ctypes.c_size_t, ctypes.c_void_p]),
     "sdp_comm_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "sdp_comm_last_error_string": (ctypes.c_char_p, []),
+    "sdp_alignment_targets": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, _c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_int, _c_i32p,
+                                             ctypes.c_int, ctypes.c_void_p]),
+    "sdp_targets_selftest": (ctypes.c_int, [ctypes.c_int]),
     "sdp_selftest": (ctypes.c_int, [ctypes.c_int]),
     "sdp_device_status": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
 }

@@ -1071,6 +1071,44 @@ int sdp_loss_backward_f32(const float *ref, const float *pred, const float *G, c
     return 0;
 }
 
+int sdp_alignment_targets(const uint8_t *codes, const int32_t *code_lens, int L, const int32_t *lens, int B, int N, int M,
+                          float *dm, float *P, void *G, int flags, int32_t *status, int device, void *stream)
+{
+    if (!codes || !code_lens || !status) return fail(SDP_E_NULLPTR, "sdp_alignment_targets: null pointer");
+    if (B <= 0 || N <= 0 || M <= 0 || L <= 0) return fail(SDP_E_SHAPE, "B, N, M and L must be positive");
+    if (N > SDP_TARGETS_MAX_DIM || M > SDP_TARGETS_MAX_DIM || L > 2 * SDP_TARGETS_MAX_DIM - 1)
+        return fail(SDP_E_TOOBIG, "sdp_alignment_targets: N and M must be <= 8192 and L <= 16383");
+    if (flags & ~(SDP_TARGETS_GAP_MASK | SDP_TARGETS_G_F32)) return fail(SDP_E_VARIANT, "sdp_alignment_targets: unknown flag");
+    const int strips = (M + sdp::TARGETS_TPB - 1) / sdp::TARGETS_TPB;
+    if ((long long)strips * B > 0x7fffffffLL) return fail(SDP_E_TOOBIG, "sdp_alignment_targets: too many pairs");
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    hipLaunchKernelGGL(sdp_targets_kernel, dim3(strips * B), dim3(sdp::TARGETS_TPB), sdp::targets_lds_bytes(N, L),
+                       (hipStream_t)stream, codes, code_lens, L, lens, N, M, strips, dm, P, G, flags, status);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "sdp_targets_kernel");
+    return 0;
+}
+
+int sdp_targets_selftest(int device)
+{
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    int *d = nullptr;
+    e = hipMalloc(&d, sizeof(int));
+    if (e != hipSuccess) return fail_hip(e, "hipMalloc");
+    int h = 0;
+    e = hipMemcpy(d, &h, sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(sdp_targets_selftest_kernel, dim3(1024), dim3(256), 0, 0, d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof(int), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail_hip(e, "sdp_targets_selftest_kernel");
+    if (h) return fail(SDP_E_SELFTEST, "sdp_targets_selftest: a square root of P is not correctly rounded");
+    return 0;
+}
 
 int sdp_selftest(int device)
 {

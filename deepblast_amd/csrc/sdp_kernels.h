@@ -162,6 +162,11 @@ constexpr int SCORES_LDS_BYTES = 2 * 2 * 128 * (SDP_SC_BK + 4) * 4;  // sdp_scor
 constexpr int SCORES_X6_LDS_BYTES = 2 * 2 * 3 * 128 * 32;            // sdp_scores_x6_kernel: [buffer][operand][piece][128 rows][32 bytes]
 constexpr int SCORES_X6W_LDS_BYTES = 2 * 2 * 3 * 256 * 32;           // sdp_scores_x6w_kernel: the same with 256 rows per operand
 
+// sdp_targets_kernel (csrc/sdp_targets.hip): one wavefront per (pair, 64-column strip); LDS = three uint16 per row of the
+// output (lo, hi, first code of the row) + the pair's codes
+constexpr int TARGETS_TPB = 64;
+__host__ __device__ inline size_t targets_lds_bytes(int N, int L) { return (size_t)6 * N + ((size_t)L + 3) / 4 * 4; }
+
 }  // namespace sdp
 
 extern "C" {
@@ -226,6 +231,9 @@ __global__ void sdp_bridge_reset_kernel(unsigned long long *xb, size_t n8);
 __global__ void sdp_parts_map_kernel(const int *lens, int *map, int B, int N, int M, int nparts_max, int strips);
 __global__ void sdp_traceback_kernel(const float *grad, int *states, int *counts, const int *lens, int B, int N, int M, int cap);
 __global__ void sdp_traceback_cuda_kernel(const float *grad, int *states, int *counts, const int *lens, int B, int N, int M, int cap);
+__global__ void sdp_targets_kernel(const uint8_t *codes, const int *code_lens, int L, const int *lens, int N, int M, int strips, float *dm,
+                                   float *P, void *G, int flags, int *status);
+__global__ void sdp_targets_selftest_kernel(int *bad);
 }
 
 #endif  // SDP_KERNELS_H_

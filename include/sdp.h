@@ -253,6 +253,46 @@ int sdp_loss_backward_f32(const float *ref, const float *pred, const float *G, c
                           const float *scale, float *grad, int B, int N, int M, int kind, int device,
                           void *stream);
 
+/* Alignment training targets from the true alignments (csrc/sdp_targets.hip).  The reference builds them per pair on
+ * the host in AlignmentDataset.__getitem__ (deepblast/dataset/dataset.py:157-179) and pads them in collate_f
+ * (dataset/utils.py:254-279); here one launch builds the padded (B, N, M) tensors of a whole batch.  Added after
+ * SDP_VERSION 106 without a version change: look the symbol up to detect it.
+ *   codes      (B, L) uint8, DEVICE: pair b's TM-align state characters in codes[b, 0 .. code_lens[b]); '1' is state x
+ *              (step (1, 0)), '2' state y (step (0, 1)), any other byte state m (step (1, 1)) -- tmstate_f, utils.py:22-29.
+ *              Step k >= 1 moves by the step of state k alone; state 0 only marks cell (0, 0) (state_diff_f / states2edges,
+ *              utils.py:60-114).  The path's extent is n = 1 + #{k >= 1: s_k != y}, m = 1 + #{k >= 1: s_k != x}.
+ *   code_lens  (B,) int32, DEVICE: 1 <= code_lens[b] <= L.
+ *   lens       NULL, or (B, 2) int32 DEVICE (len(gene), len(other)): an extent equal to lens is written as is, one equal to
+ *              its transpose (and not to lens) is written TRANSPOSED -- reshape's quirk, utils.py:465-473 --, any other
+ *              pair is refused.  NULL: the extent is the block.
+ *   dm         (B, N, M) fp32 or NULL: 1 on path cells (states2matrix, utils.py:117-134).
+ *   P          (B, N, M) fp32 or NULL: sqrtf(d2), d2 the integer squared Euclidean distance to the nearest path cell,
+ *              correctly rounded -- the bits of the reference's float64 cKDTree distance stored to float32
+ *              (path_distance_matrix, utils.py:315-339).  Every pair needs min(n, m) <= SDP_TARGETS_MAX_SHORT_SIDE, which
+ *              keeps d2 < 2^24 (exact in float32); larger pairs are refused whichever outputs are asked for.
+ *   G          (B, N, M) uint8 (0 / 1, a torch.bool tensor), or fp32 with SDP_TARGETS_G_F32 (what sdp_loss_*_f32 read),
+ *              or NULL.  With SDP_TARGETS_GAP_MASK: gap_mask (utils.py:393-409) -- path cells whose character is ':'
+ *              ('.' mismatches are path cells of dm and P but not of G), and always cell (0, 0) (idx[0] = 1, :401).
+ *              Without: 1 on the whole n x m block (the dataset's mask_gaps=False, its torch.ones, dataset.py:166).
+ *   status     (B,) int32 DEVICE, required: 0 written as is, 1 written transposed, < 0 refused (SDP_TARGETS_BAD_*):
+ *              a refused pair's (N, M) slot is zero in every output, and nothing outside it is written.
+ * Cells outside a pair's block are 0 in every output (collate_f pads with zeros).  N, M <= SDP_TARGETS_MAX_DIM,
+ * L <= 2 * SDP_TARGETS_MAX_DIM - 1; the outputs must not overlap.  One launch of ceil(M / 64) * B wavefronts: each
+ * rescans its pair's codes, P is an exact separable distance transform, O(n * m) per pair whatever the path's shape. */
+#define SDP_TARGETS_GAP_MASK 0x1
+#define SDP_TARGETS_G_F32 0x2
+#define SDP_TARGETS_MAX_DIM 8192
+#define SDP_TARGETS_MAX_SHORT_SIDE 4096
+#define SDP_TARGETS_BAD_LENS (-1)  /* extent is neither lens[b] nor its transpose */
+#define SDP_TARGETS_BAD_SHAPE (-2) /* the block does not fit (N, M) */
+#define SDP_TARGETS_TOO_LONG (-3)  /* min(n, m) > SDP_TARGETS_MAX_SHORT_SIDE */
+#define SDP_TARGETS_BAD_CODES (-4) /* code_lens[b] outside 1 .. L */
+int sdp_alignment_targets(const uint8_t *codes, const int32_t *code_lens, int L, const int32_t *lens, int B, int N, int M,
+                          float *dm, float *P, void *G, int flags, int32_t *status, int device, void *stream);
+/* Every integer d2 in [0, 4096^2] through the rounding helper of P, checked against the correctly rounded square root
+ * with integer arithmetic, in one launch.  Synchronises the device.  0 = ok, SDP_E_SELFTEST on a mismatch. */
+int sdp_targets_selftest(int device);
+
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept
  * for callers who are short of memory, not of time; deepblast_amd.losses uses the unfused kernels by default.
