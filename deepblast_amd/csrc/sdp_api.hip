@@ -592,11 +592,14 @@ size_t sdp_state_d_bytes_v(int B, int N, int M, int variant)
 int sdp_plan(int pass, int B, int N, int M, int has_lens, int exact_state, int cus, int *kernel_id, int *chunk,
              int *waves, size_t *lds)
 {
+    const bool fused_seed = (pass & SDP_PLAN_FUSED_SEED) != 0;
+    pass &= ~SDP_PLAN_FUSED_SEED;
     if (pass < 0 || pass > 3) return fail(SDP_E_VARIANT, "sdp_plan: pass must be 0..3");
+    if (fused_seed && pass != sdp::PASS_AFWD) return fail(SDP_E_VARIANT, "sdp_plan: SDP_PLAN_FUSED_SEED needs pass 2 (adjoint forward)");
     if (int rc = check_shape(B, N, M, SDP_NW)) return rc;
     if (cus <= 0) return fail(SDP_E_SHAPE, "sdp_plan: cus must be positive");
     const bool exact = (pass == sdp::PASS_FWD || pass == sdp::PASS_BWD) ? exact_for(exact_state != 0, N, M) : exact_state != 0;
-    const Plan pl = plan(pass, B, N, M, has_lens != 0, exact, cus, 0);
+    const Plan pl = plan(pass, B, N, M, has_lens != 0, exact, cus, 0, fused_seed);
     if (kernel_id) *kernel_id = pl.v.id;
     if (chunk) *chunk = pl.v.K;
     if (waves) *waves = pl.W;
@@ -1038,6 +1041,15 @@ int sdp_traceback_i32(const float *grad, int32_t *states, int32_t *counts, int B
     return sdp_traceback_rule_i32(grad, states, counts, B, N, M, lens, SDP_TRACEBACK_CPU, device, stream);
 }
 
+// The loss kernels move four columns per 16-byte access only when every row of every tensor they touch starts on a 16-byte
+// boundary: M a multiple of 4 AND 16-byte aligned base pointers (include/sdp.h).  A contiguous view at a 4-byte offset has
+// M % 4 == 0 but misaligned rows; it takes the scalar path.
+static int loss_vec4(int M, const float *ref, const float *pred, const float *G, const float *grad)
+{
+    auto aligned16 = [](const void *q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    return (M & 3) == 0 && aligned16(ref) && aligned16(pred) && aligned16(G) && aligned16(grad);
+}
+
 int sdp_loss_forward_f32(const float *ref, const float *pred, const float *G, const int32_t *lens, double *acc, int32_t *cnt,
                          int B, int N, int M, int kind, int device, void *stream)
 {
@@ -1046,7 +1058,9 @@ int sdp_loss_forward_f32(const float *ref, const float *pred, const float *G, co
     if (kind < 0 || kind > 2) return fail(SDP_E_VARIANT, "loss kind must be 0 (cross entropy), 1 (path) or 2 (alignment)");
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-    hipLaunchKernelGGL(sdp_loss_fwd_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, ref, pred, G, lens, acc, cnt, N, M, kind);
+    const int vec4 = loss_vec4(M, ref, pred, G, nullptr);
+    hipLaunchKernelGGL(sdp_loss_fwd_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, ref, pred, G, lens, acc, cnt, N, M, kind,
+                       vec4);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "sdp_loss_fwd_kernel");
     return 0;
@@ -1064,8 +1078,9 @@ int sdp_loss_backward_f32(const float *ref, const float *pred, const float *G, c
     int gx = (int)((groups + 256 * 4 - 1) / (256 * 4));
     if (gx < 1) gx = 1;
     if (gx > 64) gx = 64;
+    const int vec4 = loss_vec4(M, ref, pred, G, grad);
     hipLaunchKernelGGL(sdp_loss_bwd_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, ref, pred, G, lens, scale, grad, N, M,
-                       kind);
+                       kind, vec4);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "sdp_loss_bwd_kernel");
     return 0;

@@ -355,14 +355,21 @@ __device__ __forceinline__ float loss_clamp(float p)
     return fminf(fmaxf(p, eps), 1.0f - eps);
 }
 
-// value of one counted cell (kind as above)
-__device__ __forceinline__ float loss_term(float r, float y, int kind)
+// value of one counted cell (kind as above).  1 - p rounded to fp32 is off by up to 3e-8, which is all of log(1 - p) at
+// p = 3e-8 and 3e-6 of it at p = 0.01 -- a pair whose counted cells are all such would miss the float64 value by that
+// much.  So 1 - p = q + e exactly (Fast2Sum, p <= 1), and log(1 - p) = log(q) + e / q, with e / q taken as e: e != 0 only
+// where p < 1/2, and there the difference, e * p / q, is below 6e-8 of log(1 - p).  (log1pf does the same job, but
+// measured on MI355X at 256 x 512^2 the forward kernel then took 294-314 us instead of 142-146 us.)  The square of kinds 1 and 2 is formed in float64: d itself is an fp32
+// value, so d * d is exact there, where in fp32 it would lose bits below 1e-19 (denormal squares) and vanish below 1e-23
+// -- a pair whose vector is all that small would then get norm 0 instead of the reference's norm
+__device__ __forceinline__ double loss_term(float r, float y, int kind)
 {
     if (kind == 0) {
         const float p = loss_clamp(y);
-        return r * logf(p) + (1.0f - r) * logf(1.0f - p);
+        const float q = 1.0f - p, e = (1.0f - q) - p;
+        return (double)(r * logf(p) + (1.0f - r) * (logf(q) + e));
     }
-    const float d = kind == 1 ? r * y : r - y;
+    const double d = (double)(kind == 1 ? r * y : r - y);
     return d * d;
 }
 // derivative factor of one counted cell w.r.t. the predicted value
@@ -3007,11 +3014,12 @@ extern "C" __global__ void __launch_bounds__(64) sdp_traceback_cuda_kernel(const
 // HBM-bound elementwise work: 12 B read per cell in the forward, 12 B read + 4 B written in the backward.
 // ----------------------------------------------------------------------------------
 // One workgroup per pair; a thread takes four consecutive columns of a row per iteration (one 16-byte load per
-// tensor when the rows are 16-byte aligned, i.e. M a multiple of 4), so the three tensors stream at full width and
-// there is one index division per four cells.  Per-thread float64 partial sums, fixed reduction order: deterministic.
+// tensor when every row of every tensor is 16-byte aligned: M a multiple of 4 and 16-byte aligned base pointers, which
+// the host decides and passes as `vec4`), so the three tensors stream at full width and there is one index division per
+// four cells.  Per-thread float64 partial sums, fixed reduction order: deterministic.
 extern "C" __global__ void __launch_bounds__(1024) sdp_loss_fwd_kernel(const float *ref, const float *pred, const float *G,
                                                                        const int *lens, double *acc, int *cnt, int N, int M,
-                                                                       int kind)
+                                                                       int kind, int vec4)
 {
     __shared__ double s_acc[16];
     __shared__ int s_cnt[16];
@@ -3026,7 +3034,7 @@ extern "C" __global__ void __launch_bounds__(1024) sdp_loss_fwd_kernel(const flo
     int c = 0;
     const int q4 = (m + 3) >> 2;            // groups of four columns per row
     const int total = n * q4;
-    const bool vec = (M & 3) == 0;
+    const bool vec = vec4 != 0;   // (the host checked M % 4 == 0 and the pointers' alignment)
     for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
         const int i = idx / q4, j = (idx - i * q4) << 2;
         const size_t o = base + (size_t)i * M + j;
@@ -3049,7 +3057,7 @@ extern "C" __global__ void __launch_bounds__(1024) sdp_loss_fwd_kernel(const flo
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if (g[e] != 0.f) {
-                a += (double)sdp::loss_term(r[e], y[e], kind);
+                a += sdp::loss_term(r[e], y[e], kind);
                 ++c;
             }
         }
@@ -3071,10 +3079,10 @@ extern "C" __global__ void __launch_bounds__(1024) sdp_loss_fwd_kernel(const flo
 }
 
 // grid (x, B): the workgroups of a pair stride over groups of four columns of the FULL padded matrix (grad is written
-// in full: zero outside the pair's block and where G is 0)
+// in full: zero outside the pair's block and where G is 0); `vec4` as in the forward, with grad's alignment too
 extern "C" __global__ void __launch_bounds__(256) sdp_loss_bwd_kernel(const float *ref, const float *pred, const float *G,
                                                                       const int *lens, const float *scale, float *grad, int N,
-                                                                      int M, int kind)
+                                                                      int M, int kind, int vec4)
 {
     const int b = blockIdx.y;
     int n = N, m = M;
@@ -3086,7 +3094,7 @@ extern "C" __global__ void __launch_bounds__(256) sdp_loss_bwd_kernel(const floa
     const size_t base = (size_t)b * N * M;
     const int q4 = (M + 3) >> 2;
     const int total = N * q4;
-    const bool vec = (M & 3) == 0;
+    const bool vec = vec4 != 0;   // (the host checked M % 4 == 0 and the pointers' alignment)
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int i = idx / q4, j = (idx - i * q4) << 2;
         const size_t o = base + (size_t)i * M + j;

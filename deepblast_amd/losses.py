@@ -19,6 +19,9 @@ def _lens(x_len, y_len, B, device):
     y = torch.as_tensor(y_len, dtype=torch.int32).reshape(-1)
     if x.numel() != B or y.numel() != B:
         raise ValueError(f"x_len / y_len must have one entry per pair ({B})")
+    if (x < 0).any() or (y < 0).any():
+        # the reference's slice [:-k] would keep all rows but the last k; the kernels would count nothing: neither is meant
+        raise ValueError("x_len / y_len must not be negative")
     return torch.stack([x, y], dim=1).to(device).contiguous()
 
 
@@ -173,13 +176,26 @@ def decode_loss(decoder, loss, theta, A, first, x_len, y_len, G, lengths=None, f
               deepblast/losses.py:30-40 does, the sweeps mask by `lengths`), and `decoder.traceback_batch(E, lengths)` does not
               either; True zero-fills it like decoder.decode() does.  When `lengths` differs from (x_len, y_len) E is always
               zero-filled: the loss then reads cells outside the DP's blocks.  The gradient w.r.t. theta is always zero
-              outside the blocks."""
+              outside the blocks.
+    Pairs wider than the sweeps take (M > sdp_max_cols(), N within it) are swept transposed, as decoder.decode() sweeps them:
+    theta, A, first, G and both sets of lengths are transposed, the loss value is the same, and E comes back as a transposed
+    (non-contiguous) view of the (B, M, N) matrix the sweeps wrote.  Both sides over the limit raise what decode() raises."""
     from ._engine import NW, SW
     from .sw import SmithWatermanDecoder
     variant = SW if isinstance(decoder, SmithWatermanDecoder) else NW
     if getattr(decoder, "arithmetic", "fast") != "fast":
         raise NotImplementedError("decode_loss runs the tuned sweeps only; with arithmetic='reference' use "
                                   "loss(first, decoder.decode(theta, A), x_len, y_len, G)")
+    if decoder._transposed(theta, A, None) is not None:
+        # more columns than the sweeps take, but not more rows: decode() sweeps the transposed problem (_dp.py: _transposed),
+        # and so does this op -- with the loss's operands and both sets of lengths transposed too.  A masked sum over the
+        # block is the same sum over its transpose, so the loss value does not change; E is handed back transposed.
+        if lengths is not None:
+            lengths = (torch.stack([lengths[:, 1], lengths[:, 0]], dim=1) if isinstance(lengths, torch.Tensor)
+                       else [(b, a) for a, b in lengths])
+        loss_value, E = decode_loss(decoder, loss, theta.transpose(1, 2), A.transpose(1, 2), first.transpose(1, 2), y_len, x_len,
+                                    G.transpose(1, 2), lengths, fill)
+        return loss_value, E.transpose(1, 2)
     B = theta.shape[0]
     lens_loss = _lens(x_len, y_len, B, theta.device)
     lens_dp = None

@@ -243,7 +243,10 @@ int sdp_traceback_rule_i32(const float *grad, int32_t *states, int32_t *counts, 
  * G = mask (non-zero = counted); all (B,N,M) fp32.  Forward: acc[b] = per-pair masked sum (see kernel
  * header), cnt[b] = number of counted cells.  Backward: grad (B,N,M), written in full, = scale[b] times the
  * per-element derivative factor.  The Python layer (deepblast_amd/losses.py) turns acc/cnt into the
- * reference's scalar and supplies scale. */
+ * reference's scalar and supplies scale.
+ * Any pointer alignment of 4 bytes is accepted.  The kernels read (and the backward writes) four columns per
+ * 16-byte access only when M is a multiple of 4 AND ref, pred, G (and grad, in the backward) are all 16-byte
+ * aligned; anything else takes the scalar path, with the same results bit for bit. */
 #define SDP_LOSS_CROSS_ENTROPY 0
 #define SDP_LOSS_PATH 1
 #define SDP_LOSS_ALIGNMENT 2
@@ -338,7 +341,10 @@ int sdp_device_status(int device, int32_t info[4]);
  * (throughput)), chunk length, waves per pair,
  * dynamic LDS bytes.  Pure function, needs no device.  (Reported for tensors whose rows and planes start on 128-byte
  * lines -- M a multiple of 32; other launches use the "general pitch" instantiations of the same builds, ids 11-20.
- * Ids 21-28: the throughput builds with the bridge between workgroups, see sdp_plan_parts.) */
+ * Ids 21-28: the throughput builds with the bridge between workgroups, see sdp_plan_parts.)
+ * pass 2 | SDP_PLAN_FUSED_SEED: the adjoint forward sweep with the fused loss seed (sdp_adjoint_forward_loss_f32, build
+ * 10), which stages three planes instead of two. */
+#define SDP_PLAN_FUSED_SEED 0x100
 int sdp_plan(int pass, int B, int N, int M, int has_lens, int exact_state, int cus, int *kernel_id, int *chunk,
              int *waves, size_t *lds);
 

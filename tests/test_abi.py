@@ -308,3 +308,21 @@ def test_kernel_names_are_the_builds_the_library_launches(monkeypatch):
     assert eng._label(0, 256, 512, 512, False, False, 0, "default") == "sdp_fwd_kernel"
     assert eng._label(1, 256, 1024, 1024, False, False, 0, "default") == "sdp_bwd_pipe_kernel"
     assert eng._label(0, 256, 512, 512, True, True, 0, "default") == "sdp_fwd_x_c_kernel"
+
+
+def test_fused_seed_plan_keeps_four_waves_at_the_column_limit(lib):
+    """The adjoint forward sweep with the fused loss seed (build 10) stages three planes (ref, pred, G) instead of two; by the
+    LDS arithmetic of plan() with K = 16 it still keeps four waves at M = 2048, where it takes the most LDS.  The (N, M) grid is
+    that of tests/test_end_to_end_gpu.py::test_fused_seed_tracks_float64, which runs every pair of it for NW and for SW: 1, 3 and
+    4 waves, the last with strips taken in rounds."""
+    FUSED = 0x100   # include/sdp.h: SDP_PLAN_FUSED_SEED
+    hdr = open(os.path.join(ROOT, "include", "sdp.h")).read()
+    assert re.search(r"#define\s+SDP_PLAN_FUSED_SEED\s+0x100\b", hdr)
+    for N, waves in ((40, 1), (130, 3), (300, 4)):
+        for M in (37, 170, 516, 1100, 2048):
+            for B, lens in ((3, 0), (3, 1), (300, 1)):
+                kid, chunk, w, lds = _plan(lib, 2 | FUSED, B, N, M, lens, 1)
+                assert (kid, chunk, w) == (10, 16, waves), (N, M, B, lens, kid, chunk, w)
+                assert lds <= 160 * 1024
+                assert _plan(lib, 2, B, N, M, lens, 1)[0] != 10   # without the flag: the plain adjoint forward build
+    assert lib.sdp_plan(0 | FUSED, 3, 40, 37, 0, 1, 256, None, None, None, None) != 0   # the flag belongs to pass 2 only
