@@ -253,6 +253,17 @@ class _Decoder(nn.Module):
             raise IndexError(f"traceback walked off the matrix for pairs {np.nonzero(counts < 0)[0].tolist()}")
         return [[tuple(int(v) for v in row) for row in states[b, :counts[b]]] for b in range(len(counts))]
 
+    def validation_stats(self, grad, true_states, lengths=None, no_gaps=True, strict=True):
+        """Extension (row f6): the accuracy statistics the reference's validation and test steps log
+        (DeepBLAST.validation_stats, trainer.py:190-233: per pair traceback(aln[b, :xlen, :ylen]) -> states2edges ->
+        filter_gaps -> roc_edges), for a whole batch on the device: the walk of traceback_batch by this decoder's
+        traceback_rule, then one scoring launch; the walks never reach the host.  -> (B, 7) float64, the columns of
+        deepblast_amd.score.COLUMNS.  true_states: the dataset's int states (or strings, or (codes, code_lens));
+        strict: see deepblast_amd.score.alignment_stats (IndexError for a walk that leaves its matrix)."""
+        from . import score
+        states, counts = _engine.get_engine().traceback(grad, lengths, self.traceback_rule)
+        return score.alignment_stats(true_states, (states, counts), no_gaps=no_gaps, device=grad.device, strict=strict)
+
     def decode(self, theta, A, lengths=None, fill=True):
         """Expected alignment matrix dVt/dtheta, differentiable (nw_cuda.py:319-325).  `lengths`, `fill`: see forward()
         (the gradient that flows back through the result, Ed, is always zero outside the blocks)."""

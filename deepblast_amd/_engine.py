@@ -384,6 +384,35 @@ class HipEngine:
         _lib.check(rc, "sdp_alignment_targets")
         return status
 
+    def alignment_stats(self, true_codes, true_lens, pred, pred_lens, offsets, widths, flags, counts, stats, hits, identity,
+                        status):
+        """Enqueue sdp_alignment_stats on the current stream (include/sdp.h): true_codes (B, Lt) uint8, true_lens (B,) int32;
+        pred (B, Lp) uint8 codes, or with SDP_SCORE_PRED_WALK the walk (B, cap, 3) int32, pred_lens (B,) int32 (its counts);
+        offsets (B, 2) int32 or None; widths (W,) int32 or None; counts (B, 5) int32; stats (B, 7) float64, hits (B, W)
+        int32, identity (B, W) float64, each or None; status (B,) int32.  Every tensor contiguous on one device."""
+        dev = self._dev(true_codes)
+        B, Lt = true_codes.shape
+        Lp = pred.shape[1]
+        W = 0 if widths is None else widths.numel()
+        want = {"true_codes": (true_codes, torch.uint8, (B, Lt)), "true_lens": (true_lens, torch.int32, (B,)),
+                "pred": (pred, torch.int32 if flags & _lib.SDP_SCORE_PRED_WALK else torch.uint8,
+                         (B, Lp, 3) if flags & _lib.SDP_SCORE_PRED_WALK else (B, Lp)),
+                "pred_lens": (pred_lens, torch.int32, (B,)), "offsets": (offsets, torch.int32, (B, 2)),
+                "widths": (widths, torch.int32, (W,)), "counts": (counts, torch.int32, (B, 5)),
+                "stats": (stats, torch.float64, (B, 7)), "hits": (hits, torch.int32, (B, W)),
+                "identity": (identity, torch.float64, (B, W)), "status": (status, torch.int32, (B,))}
+        for name, (t, dtype, shape) in want.items():
+            if t is None:
+                continue
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != true_codes.device:
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {true_codes.device}")
+        with torch.cuda.device(dev), self._bracket("sdp_score_kernel"):
+            rc = self.lib.sdp_alignment_stats(_ptr(true_codes), _ptr(true_lens), Lt, _ptr(pred), _ptr(pred_lens), Lp,
+                                              _ptr(offsets), _ptr(widths), W, B, flags, _ptr(counts), _ptr(stats), _ptr(hits),
+                                              _ptr(identity), _ptr(status), dev, self._stream(dev))
+        _lib.check(rc, "sdp_alignment_stats")
+        return status
+
     def targets_selftest(self, device=0):
         _lib.check(self.lib.sdp_targets_selftest(device), "sdp_targets_selftest")
 

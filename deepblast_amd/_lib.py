@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("SDP_LIB_PATH") or os.path.join(_HERE, "libsdp_hip.so"
 SDP_NW, SDP_SW = 0, 1
 SDP_NO_ZERO_SKIP, SDP_NO_FILL = 0x800, 0x10000   # include/sdp.h: flags of the backward sweeps
 SDP_TARGETS_GAP_MASK, SDP_TARGETS_G_F32 = 0x1, 0x2  # include/sdp.h: flags of sdp_alignment_targets
+SDP_SCORE_NO_GAPS, SDP_SCORE_PRED_WALK = 0x1, 0x2    # include/sdp.h: flags of sdp_alignment_stats
 
 _c_f32p = ctypes.c_void_p
 _c_i32p = ctypes.c_void_p
@@ -75,6 +76,9 @@ SIGNATURES = {
                                              ctypes.c_int, _c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_int, _c_i32p,
                                              ctypes.c_int, ctypes.c_void_p]),
     "sdp_targets_selftest": (ctypes.c_int, [ctypes.c_int]),
+    "sdp_alignment_stats": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, ctypes.c_int, ctypes.c_void_p, _c_i32p, ctypes.c_int,
+                                           _c_i32p, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32p,
+                                           ctypes.c_void_p, _c_i32p, ctypes.c_void_p, _c_i32p, ctypes.c_int, ctypes.c_void_p]),
     "sdp_selftest": (ctypes.c_int, [ctypes.c_int]),
     "sdp_device_status": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
 }

@@ -15,7 +15,7 @@ KERNELS = os.path.join(HERE, "csrc", "sdp_kernels.hip")
 KERNEL_GROUPS = 9   # SDP_GROUP = 0 .. 8 (sdp_kernels.hip, "SDP_IN_GROUP")
 SRC = [KERNELS, os.path.join(HERE, "csrc", "sdp_scores.hip"), os.path.join(HERE, "csrc", "sdp_ref.hip"),
        os.path.join(HERE, "csrc", "sdp_comm.hip"), os.path.join(HERE, "csrc", "sdp_targets.hip"),
-       os.path.join(HERE, "csrc", "sdp_api.hip")]
+       os.path.join(HERE, "csrc", "sdp_score.hip"), os.path.join(HERE, "csrc", "sdp_api.hip")]
 HDR = [os.path.join(HERE, "csrc", "sdp_kernels.h"), os.path.join(ROOT, "include", "sdp.h")]
 OUT = os.path.join(HERE, "libsdp_hip.so")
 

@@ -1125,6 +1125,26 @@ int sdp_targets_selftest(int device)
     return 0;
 }
 
+int sdp_alignment_stats(const uint8_t *true_codes, const int32_t *true_lens, int Lt, const void *pred, const int32_t *pred_lens,
+                        int Lp, const int32_t *offsets, const int32_t *widths, int W, int B, int flags, int32_t *counts,
+                        double *stats, int32_t *hits, double *identity, int32_t *status, int device, void *stream)
+{
+    if (!true_codes || !true_lens || !pred || !pred_lens || !counts || !status || (W > 0 && !widths))
+        return fail(SDP_E_NULLPTR, "sdp_alignment_stats: null pointer");
+    if (B <= 0 || Lt <= 0 || Lp <= 0) return fail(SDP_E_SHAPE, "B, Lt and Lp must be positive");
+    if (W < 0 || W > SDP_SCORE_MAX_WIDTHS) return fail(SDP_E_SHAPE, "sdp_alignment_stats: W must be in 0 .. 1024");
+    if (flags & ~(SDP_SCORE_NO_GAPS | SDP_SCORE_PRED_WALK)) return fail(SDP_E_VARIANT, "sdp_alignment_stats: unknown flag");
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    const int rows = Lp < SDP_SCORE_MAX_STATES ? Lp : SDP_SCORE_MAX_STATES;  // a pair's rows <= its states
+    hipLaunchKernelGGL(sdp_score_kernel, dim3(B), dim3(sdp::SCORE_TPB), sdp::score_lds_bytes(rows, W), (hipStream_t)stream,
+                       true_codes, true_lens, Lt, pred, pred_lens, Lp, rows, offsets, widths, W, flags, counts, stats, hits,
+                       identity, status);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "sdp_score_kernel");
+    return 0;
+}
+
 int sdp_selftest(int device)
 {
     hipError_t e = hipSetDevice(device);

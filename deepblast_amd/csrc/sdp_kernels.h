@@ -167,6 +167,11 @@ constexpr int SCORES_X6W_LDS_BYTES = 2 * 2 * 3 * 256 * 32;           // sdp_scor
 constexpr int TARGETS_TPB = 64;
 __host__ __device__ inline size_t targets_lds_bytes(int N, int L) { return (size_t)6 * N + ((size_t)L + 3) / 4 * 4; }
 
+// sdp_score_kernel (csrc/sdp_score.hip): one wavefront per pair; LDS = two int32 per width (S_i, hits) + one uint16 per row
+// of the prediction (rows <= SDP_SCORE_MAX_STATES: at most 32 KB + 8 KB)
+constexpr int SCORE_TPB = 64;
+__host__ __device__ inline size_t score_lds_bytes(int rows, int W) { return (size_t)8 * W + ((size_t)rows * 2 + 3) / 4 * 4; }
+
 }  // namespace sdp
 
 extern "C" {
@@ -234,6 +239,9 @@ __global__ void sdp_traceback_cuda_kernel(const float *grad, int *states, int *c
 __global__ void sdp_targets_kernel(const uint8_t *codes, const int *code_lens, int L, const int *lens, int N, int M, int strips, float *dm,
                                    float *P, void *G, int flags, int *status);
 __global__ void sdp_targets_selftest_kernel(int *bad);
+__global__ void sdp_score_kernel(const uint8_t *t_codes, const int *t_lens, int Lt, const void *pred, const int *p_lens, int Lp,
+                                 int rows, const int *offsets, const int *widths, int W, int flags, int *counts, double *stats,
+                                 int *hits, double *ident, int *status);
 }
 
 #endif  // SDP_KERNELS_H_

@@ -296,6 +296,48 @@ int sdp_alignment_targets(const uint8_t *codes, const int32_t *code_lens, int L,
  * with integer arithmetic, in one launch.  Synchronises the device.  0 = ok, SDP_E_SELFTEST on a mismatch. */
 int sdp_targets_selftest(int device);
 
+/* Accuracy statistics of predicted alignments against the true ones (csrc/sdp_score.hip).  The reference computes them
+ * per pair on the host: DeepBLAST.validation_stats (deepblast/trainer.py:190-233: walk, states2edges, filter_gaps,
+ * roc_edges), alignment_score and alignment_score_kernel (deepblast/score.py:8-97); here one launch scores a whole batch.
+ * Added after SDP_VERSION 106 without a version change: look the symbol up to detect it.
+ *   true_codes (B, Lt) uint8, DEVICE, and true_lens (B,) int32 DEVICE: the true alignments, as sdp_alignment_targets
+ *              takes them ('1' state x, '2' state y, any other byte state m -- tmstate_f, utils.py:22-29).
+ *   pred       without SDP_SCORE_PRED_WALK: (B, Lp) uint8 codes, pred_lens (B,) int32 their lengths, as the truth.
+ *              With it: the walk exactly as sdp_traceback_rule_i32 leaves it, (B, Lp, 3) int32 with Lp its capacity and
+ *              pred_lens its counts; the state column is read (0 x, 2 y, anything else m), a count of -1 is the walk's
+ *              IndexError.
+ *   Edges come from the states alone (states2edges, utils.py:107-114): edge 0 is (0, 0), edge k adds the step of state k
+ *   (x (1, 0), m (1, 1), y (0, 1)).  With SDP_SCORE_NO_GAPS only the edges whose state is m are kept (filter_gaps,
+ *   score.py:37-41); the edges of a path are distinct, so roc_edges' sets are its lists.
+ *   offsets    NULL, or (B, 2) int32 DEVICE (query_offset, hit_offset): added to the predicted edges before the
+ *              comparison, as alignment_score_kernel does (score.py:66-68).  They shift the exact hits (tp) as well.
+ *   widths     (W,) int32 DEVICE, the kernel widths of alignment_score_kernel, in order; NULL when W = 0.  Width i
+ *              counts a kept true edge (a, b) as hit if a predicted edge (c, d) has a - c = b - d and |a - c| <= S_i,
+ *              S_i = sum over t <= i of max(w_t - 1, 0): roc_edges_kernel_identity extends the caller's list in place, so
+ *              the widths of one call accumulate (score.py:21-35, 72-75).  0 <= W <= SDP_SCORE_MAX_WIDTHS.
+ *   counts     (B, 5) int32 DEVICE, required: tp, fp, fn, n_true, n_pred (kept true / predicted edges).
+ *   stats      (B, 7) float64 DEVICE or NULL: roc_edges' row (score.py:8-18) -- tp, fp, fn, then perc_id = tp / n_true,
+ *              ppv = tp / (tp + fp), fnr = fn / (fn + tp), fdr = fp / (fp + tp), each a correctly rounded division.
+ *   hits       (B, W) int32 DEVICE or NULL: true edges hit at each width.
+ *   identity   (B, W) float64 DEVICE or NULL: hits / n_true, alignment_score_kernel's list.
+ *   status     (B,) int32 DEVICE, required: 0, or the first of the SDP_SCORE_* codes below that applies.  A pair with a
+ *              status < 0 has tp = fp = fn = 0 and hits 0, NaN in stats and identity; n_true and n_pred are counted as
+ *              far as the status allows.
+ * Pairs are independent; no atomics, deterministic.  One launch of B wavefronts; cost O(Lt + Lp) per pair plus, per kept
+ * true edge, the row distance to its nearest predicted edge on its diagonal (capped by max S_i). */
+#define SDP_SCORE_NO_GAPS 0x1
+#define SDP_SCORE_PRED_WALK 0x2
+#define SDP_SCORE_MAX_STATES 16383
+#define SDP_SCORE_MAX_WIDTHS 1024
+#define SDP_SCORE_NO_TRUE_MATCH (-1) /* no_gaps and no m state in the truth: filter_gaps raises ValueError */
+#define SDP_SCORE_NO_PRED_MATCH (-2) /* no_gaps and no m state in the prediction (checked before the truth, as score.py) */
+#define SDP_SCORE_WALK_RAISED (-3)   /* the walk's count is -1: the reference's traceback raised IndexError */
+#define SDP_SCORE_BAD_LENGTH (-4)    /* true_lens[b] outside 1 .. Lt, or pred_lens[b] outside 1 .. Lp */
+#define SDP_SCORE_TOO_LONG (-5)      /* more than SDP_SCORE_MAX_STATES states on either side */
+int sdp_alignment_stats(const uint8_t *true_codes, const int32_t *true_lens, int Lt, const void *pred, const int32_t *pred_lens,
+                        int Lp, const int32_t *offsets, const int32_t *widths, int W, int B, int flags, int32_t *counts,
+                        double *stats, int32_t *hits, double *identity, int32_t *status, int device, void *stream);
+
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept
  * for callers who are short of memory, not of time; deepblast_amd.losses uses the unfused kernels by default.
