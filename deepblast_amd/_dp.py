@@ -173,6 +173,8 @@ class _Decoder(nn.Module):
     """Common body of NeedlemanWunschDecoder / SmithWatermanDecoder (nw_cuda.py:265-325)."""
 
     _function = None
+    _variant = None                # SDP_NW / SDP_SW, for the calls that go to the engine without an autograd Function (score)
+    _allow_none_operator = False
 
     def __init__(self, operator, traceback_rule="cpu", arithmetic="fast"):
         """traceback_rule (extension): "cpu" = the walk of the reference's CPU decoders (nw.py:401-444, the parity
@@ -210,6 +212,25 @@ class _Decoder(nn.Module):
         if not fill:
             return self._function.apply(theta, A, self.operator, lengths, False, True)
         return self._function.apply(theta, A, self.operator, lengths)
+
+    def score(self, theta, A, lengths=None):
+        """theta, A: (B, N, M) on a ROCm device -> Vt (B,), the alignment scores alone -- what the reference's
+        NeuralAligner.score keeps of `self.ddp(theta, A)` under torch.no_grad() (alignment.py:127-137).  The result carries
+        NO autograd graph, whatever the inputs require: use forward() to differentiate.  Same values as forward(); the sweep
+        behind it (include/sdp.h: sdp_forward_value_f32) neither forms nor stores the state, so nothing but Vt (and, with
+        `lengths`, a workspace of a few KB) is allocated -- forward() allocates and writes 5 bytes per cell.  `lengths` as in
+        forward(); problems wider than the column limit are swept transposed.  arithmetic="reference" decoders run the
+        reference-rounding forward and drop its state (that mode has no fast path)."""
+        _validate(theta, A, self.operator, type(self)._allow_none_operator)
+        tr = self._transposed(theta, A, lengths)
+        if tr is not None:
+            theta, A, lengths = tr
+        eng = _engine.get_engine()
+        with torch.no_grad():
+            theta, A = theta.detach(), A.detach()
+            if self.arithmetic == "reference":
+                return eng.forward(theta, A, self._variant, lengths, exact_state=_engine.REF)[0]
+            return eng.forward_value(theta, A, self._variant, lengths)
 
     @staticmethod
     def _transposed(theta, A, lengths):

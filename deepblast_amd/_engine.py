@@ -45,7 +45,7 @@ class HipEngine:
         # optional profiling hook (bench.py): callable(name) -> context manager that brackets one
         # kernel launch on the current stream, e.g. with a pair of events.  None = no overhead.
         self.launch_hook = None
-        # per-pass wave-count override for experiments and tests ({0 fwd, 1 bwd, 2 adj-fwd, 3 adj-bwd} -> waves);
+        # per-pass wave-count override for experiments and tests ({0 fwd, 1 bwd, 2 adj-fwd, 3 adj-bwd, 4 value-only fwd} -> waves);
         # travels with each call as SDP_WAVES(w), the library keeps no tuning state
         self.force_waves = {}
         # measurement control (bench.py's `no_skip` figures): False = the backward sweep runs every chunk (SDP_NO_ZERO_SKIP);
@@ -61,7 +61,8 @@ class HipEngine:
                     21: "sdp_fwd_p_kernel", 22: "sdp_fwd_x_tp_p_kernel", 23: "sdp_bwd_p_kernel", 24: "sdp_bwd_x_p_kernel",
                     25: "sdp_fwd_pg_kernel", 26: "sdp_fwd_x_tp_pg_kernel", 27: "sdp_bwd_pg_kernel", 28: "sdp_bwd_x_pg_kernel",
                     36: "sdp_bwd_pipe_kernel", 37: "sdp_fwd_c_kernel", 38: "sdp_fwd_x_tp_c_kernel", 39: "sdp_fwd_lat_c_kernel",
-                    40: "sdp_fwd_x_c_kernel"}
+                    40: "sdp_fwd_x_c_kernel", 41: "sdp_val_kernel", 42: "sdp_val_c_kernel", 43: "sdp_val_g_kernel",
+                    44: "sdp_val_lat_kernel", 45: "sdp_val_lat_c_kernel"}
 
     def _label(self, pass_, B, N, M, has_lens, exact, dev, default):
         """Name of the kernel a launch will use (for the launch hook: bench.py's per-kernel timers must carry the names the
@@ -172,6 +173,28 @@ class HipEngine:
                                           self._v(0, variant), dev, self._stream(dev))
         _lib.check(rc, "sdp_forward_f32")
         return Vt, state
+
+    def forward_value(self, theta, A, variant, lens=None):
+        """-> Vt (B,) and nothing else: the forward sweep for callers that never differentiate (scoring / search; the
+        reference's NeuralAligner.score, alignment.py:127-137).  No state is formed or allocated (include/sdp.h:
+        sdp_forward_value_f32) -- only Vt and, with lengths, a workspace of a few KB.  float64 tensors take the float64
+        forward (a test path) and drop its state."""
+        dev = self._dev(theta)
+        if theta.dtype == torch.float64:
+            return self._forward_f64(theta, A, variant, lens, dev)[0]
+        self._check(theta, theta=theta, A=A)
+        theta, A = theta.contiguous(), A.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        ws = None
+        if lens is not None:
+            ws = torch.empty(max(self.lib.sdp_forward_value_ws_bytes(B, N, M), 4) // 4, dtype=torch.int32, device=theta.device)
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        with torch.cuda.device(dev), self._bracket(self._label(4, B, N, M, lens is not None, False, dev, "sdp_val_kernel")):
+            rc = self.lib.sdp_forward_value_f32(_ptr(theta), _ptr(A), _ptr(Vt), _ptr(ws), B, N, M, _ptr(lens),
+                                                self._v(4, variant), dev, self._stream(dev))
+        _lib.check(rc, "sdp_forward_value_f32")
+        return Vt
 
     def state_pair_bytes(self, N, M, exact_state=False):
         """Bytes between the records of consecutive pairs in the state buffer (include/sdp.h: sdp_state_pair_stride)."""

@@ -31,6 +31,9 @@ SIGNATURES = {
     "sdp_plan_parts": (ctypes.c_int, [ctypes.c_int] * 7),
     "sdp_forward_f32": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_forward_value_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "sdp_forward_value_f32": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "sdp_backward_f32": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "sdp_state_pair_stride": (ctypes.c_size_t, [ctypes.c_int] * 3),

@@ -109,6 +109,12 @@ Variant variant(int id)
     case 38: return {(const void *)sdp_fwd_x_tp_c_kernel, SDP_K_FWD, SDP_MAXW_FWD, 38};
     case 39: return {(const void *)sdp_fwd_lat_c_kernel, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, 39};   // [6] ...
     case 40: return {(const void *)sdp_fwd_x_c_kernel, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, 40};     // [5] ...
+    // the value-only forward sweep (sdp_forward_value_f32: Vt, no state): [0] / [37] / [11] / [6] / [39] with the state path compiled out
+    case 41: return {(const void *)sdp_val_kernel, SDP_K_FWD, SDP_MAXW_FWD, 41};
+    case 42: return {(const void *)sdp_val_c_kernel, SDP_K_FWD, SDP_MAXW_FWD, 42};
+    case 43: return {(const void *)sdp_val_g_kernel, SDP_K_FWD, SDP_MAXW_FWD, 43};
+    case 44: return {(const void *)sdp_val_lat_kernel, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, 44};
+    case 45: return {(const void *)sdp_val_lat_c_kernel, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, 45};
     default: return {(const void *)sdp_bwd_lat_kernel, SDP_K_BWD_LAT, SDP_MAXW_BWD_LAT, 4};
     }
 }
@@ -269,6 +275,41 @@ Plan plan(int pass, int B, int N, int M, bool has_lens, bool exact_state, int cu
     return {v, W, lds, off, parts};
 }
 
+// The value-only forward sweep (sdp_forward_value_f32).  It runs the forward sweep's builds with the state path compiled out, and
+// its policy is the forward sweep's wherever that keeps one workgroup per pair: the throughput build (K = 32, <= 4 waves) for
+// batches that fill the GPU, the latency build (K = 16, <= 8 waves) for smaller ones, for batches with per-pair lengths that do not
+// queue up and where four waves' staging does not fit beside long boundary rows; two waves per pair where that saves rounds; the
+// twins with the edge cleaning for per-pair lengths and partial strips; the general-pitch twin of the throughput build.  No parts:
+// bridge rows and dispatch map would have to live in a state buffer, and this call has none.  The staged inputs take the LDS they
+// take in the forward sweep (the state never went through LDS), so the wave counts that fit are the same.
+Plan plan_value(int B, int N, int M, bool has_lens, int cus, int forced_waves, bool general_pitch = false)
+{
+    const int pass = sdp::PASS_FWD;
+    const int nstrips = sdp::state_nstrips(N);
+    const int mcap = (M + 63) / 64 * 64;
+    const bool full = B * 7 >= cus * 2 && !(has_lens && B <= 2 * cus);
+    Variant v = variant(41);
+    int W = forced_waves;
+    if (W <= 0) {
+        W = full ? 4 : 8;
+        const int r4 = (B + cus - 1) / cus, r2 = (B + 2 * cus - 1) / (2 * cus);
+        if (full && B > cus && 181 * r2 < 100 * r4) W = 2;
+    }
+    const int w4 = nstrips < 4 ? nstrips : 4;
+    if (W > v.maxw || lds_bytes(pass, v.K, w4, mcap, nullptr) > 160 * 1024) v = variant(44);
+    if (has_lens || (N & 63) != 0) v = variant(v.id == 41 ? 42 : 45);
+    if (general_pitch && v.K == SDP_K_FWD) v = variant(43);   // (the latency builds' staged blocks keep the column-aligned geometry at any pitch)
+    if (W > v.maxw) W = v.maxw;
+    if (W > nstrips) W = nstrips;
+    size_t off = 0, lds = 0;
+    for (;; --W) {
+        lds = lds_bytes(pass, v.K, W, mcap, &off);
+        if (lds <= 160 * 1024 || W == 1) break;
+    }
+    if (W == 2 && B > cus && lds < 80 * 1024) lds = 80 * 1024;   // two-wave workgroups share a CU in pairs (see plan)
+    return {v, W, lds, off, 0};
+}
+
 // Where the 32-step units of the skewed state live (sdp_kernels.hip, "Skewed state addressing"): every (pair, strip) is one
 // contiguous stream of units.  (A "marching" layout -- unit u of every (pair, strip) in one slab, so that a batch whose pairs
 // advance in lockstep sweeps memory front to back -- measured equal in round 3 and was removed in round 6: the sweeps are not
@@ -397,7 +438,7 @@ VariantBits split_variant(int variant)
 // 160 KiB the hardware has, so concurrent callers cannot disagree
 int raise_lds_limit(const Variant &v, int device)
 {
-    static thread_local unsigned long long lds_raised[41] = {0};  // per kernel id: bit d = done on device d
+    static thread_local unsigned long long lds_raised[46] = {0};  // per kernel id: bit d = done on device d
     if (device >= 64 || !(lds_raised[v.id] >> device & 1ull)) {
         hipError_t e = hipFuncSetAttribute(v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return fail_hip(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
@@ -512,6 +553,35 @@ int launch(int pass, sdp::Params &p, int device, void *stream, bool exact_state 
     return 0;
 }
 
+// The value-only forward sweep: the forward sweep's launch without a state -- no parts, no routing of thin pairs (the state
+// format is all that routing is about), the launch order of a long variable-length batch in the caller's workspace.
+int launch_value(sdp::Params &p, int device, void *stream, int forced_waves)
+{
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = pending_handoff_error(device)) return rc;
+    p.nstrips_max = sdp::state_nstrips(p.N);
+    p.tpad = sdp::state_tpad(p.M);
+    p.mcap = (p.M + 63) / 64 * 64;
+    state_layout(p);   // (never used: no state is addressed)
+    p.status = status_words(device);
+#ifdef SDP_EXPERIMENTS
+    p.dbg = g_dbg.load();
+    p.trace = g_trace.load();
+#else
+    p.dbg = 0;
+#endif
+    auto misaligned = [](const void *ptr) { return ptr != nullptr && ((uintptr_t)ptr & 127u) != 0; };
+    const bool general_pitch = (p.M & 31) != 0 || misaligned(p.sin0) || misaligned(p.sin1);
+    const Plan pl = plan_value(p.B, p.N, p.M, p.lens != nullptr, num_cus(device), forced_waves, general_pitch);
+    p.stage_off = (int)pl.stage_off;
+    if (int rc = raise_lds_limit(pl.v, device)) return rc;
+    void *args[] = {&p};
+    e = hipLaunchKernel(pl.v.kernel, dim3((unsigned)p.B), dim3(64 * pl.W), args, pl.lds, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "hipLaunchKernel");
+    return 0;
+}
+
 // dynamic-LDS limits of the scores kernels, once per (thread, device): sticky attributes, set before any launch that
 // may be captured (sdp_init) or lazily by the first call
 int raise_scores_limits(int device)
@@ -594,7 +664,17 @@ int sdp_plan(int pass, int B, int N, int M, int has_lens, int exact_state, int c
 {
     const bool fused_seed = (pass & SDP_PLAN_FUSED_SEED) != 0;
     pass &= ~SDP_PLAN_FUSED_SEED;
-    if (pass < 0 || pass > 3) return fail(SDP_E_VARIANT, "sdp_plan: pass must be 0..3");
+    if (pass == sdp::PLAN_VALUE && !fused_seed) {   // the value-only forward sweep (sdp_forward_value_f32); exact_state does not apply
+        if (int rc = check_shape(B, N, M, SDP_NW)) return rc;
+        if (cus <= 0) return fail(SDP_E_SHAPE, "sdp_plan: cus must be positive");
+        const Plan pl = plan_value(B, N, M, has_lens != 0, cus, 0);
+        if (kernel_id) *kernel_id = pl.v.id;
+        if (chunk) *chunk = pl.v.K;
+        if (waves) *waves = pl.W;
+        if (lds) *lds = pl.lds;
+        return 0;
+    }
+    if (pass < 0 || pass > 3) return fail(SDP_E_VARIANT, "sdp_plan: pass must be 0..3, or 4 for the value-only forward sweep");
     if (fused_seed && pass != sdp::PASS_AFWD) return fail(SDP_E_VARIANT, "sdp_plan: SDP_PLAN_FUSED_SEED needs pass 2 (adjoint forward)");
     if (int rc = check_shape(B, N, M, SDP_NW)) return rc;
     if (cus <= 0) return fail(SDP_E_SHAPE, "sdp_plan: cus must be positive");
@@ -619,7 +699,7 @@ int sdp_init(int device)
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
     if (device >= 0 && device < MAX_DEV && !status_words(device)) return fail(SDP_E_SELFTEST, "sdp_init: could not create the host-pinned status words");
-    for (int id = 0; id <= 40; ++id) {   // (21-28: the parts instantiations, 36: the pipelined backward twin, 37-40: the cleaning forward twins)
+    for (int id = 0; id <= 45; ++id) {   // (21-28: the parts instantiations, 36: the pipelined backward twin, 37-40: the cleaning forward twins, 41-45: the value-only forward builds)
         const Variant v = variant(id);
         if (v.id != id) continue;   // ids without a build of their own map to the default
         if (int rc = raise_lds_limit(v, device)) return rc;
@@ -684,6 +764,42 @@ int sdp_forward_f32(const float *theta, const float *A, float *state, float *Vt,
     if (!routes_thin(exact, N, M, lens)) return launch(sdp::PASS_FWD, p, device, stream, exact, vb.waves, false, state);
     if (int rc = launch(sdp::PASS_FWD, p, device, stream, false, vb.waves, false, state, 1)) return rc;
     return launch(sdp::PASS_FWD, p, device, stream, true, 0, false, nullptr, 2);
+}
+
+size_t sdp_forward_value_ws_bytes(int B, int N, int M)
+{
+    if (B <= 0 || N <= 0 || M <= 0 || M > sdp::MAX_COLS) return 0;
+    return sdp::state_order_bytes(B);   // the launch order of a variable-length batch with more pairs than CUs: B ints
+}
+
+int sdp_forward_value_f32(const float *theta, const float *A, float *Vt, void *ws, int B, int N, int M, const int32_t *lens,
+                          int variant, int device, void *stream)
+{
+    if (!theta || !A || !Vt) return fail(SDP_E_NULLPTR, "sdp_forward_value_f32: null pointer");
+    if (variant & (SDP_EXACT_STATE | SDP_REF_ROUNDING | SDP_ET_BROADCAST | SDP_NO_FILL))
+        return fail(SDP_E_VARIANT, "sdp_forward_value_f32: SDP_EXACT_STATE, SDP_REF_ROUNDING, SDP_ET_BROADCAST and SDP_NO_FILL do not apply to a sweep "
+                                   "that writes no state and no E (SDP_NW / SDP_SW | SDP_WAVES(w) only)");
+    const VariantBits vb = split_variant(variant);
+    variant = vb.variant;
+    if (int rc = check_shape(B, N, M, variant)) return rc;
+    if (lens != nullptr && ws == nullptr && sdp_forward_value_ws_bytes(B, N, M) != 0)
+        return fail(SDP_E_NULLPTR, "sdp_forward_value_f32: per-pair lengths need a workspace of sdp_forward_value_ws_bytes(B, N, M) bytes");
+    sdp::Params p = {};
+    p.sin0 = theta;
+    p.sin1 = A;
+    p.vout = Vt;
+    p.lens = lens;
+    p.B = B, p.N = N, p.M = M, p.variant = variant;
+    if (wants_order(B, N, lens, device)) {   // longest first, as in the forward sweep; the order lives in the workspace
+        hipError_t e = hipSetDevice(device);
+        if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+        int *order = static_cast<int *>(ws);
+        hipLaunchKernelGGL(sdp_order_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, lens, order, B, N, M);
+        e = hipGetLastError();
+        if (e != hipSuccess) return fail_hip(e, "sdp_order_kernel");
+        p.order = order;
+    }
+    return launch_value(p, device, stream, vb.waves);
 }
 
 int sdp_backward_f32(const float *Et, const float *state, float *E, int B, int N, int M, const int32_t *lens,

@@ -66,6 +66,7 @@
 namespace sdp {
 
 enum { PASS_FWD = 0, PASS_BWD = 1, PASS_AFWD = 2, PASS_ABWD = 3 };
+constexpr int PLAN_VALUE = 4;   // sdp_plan's number for the value-only forward sweep (a forward sweep to the kernels: PASS_FWD)
 
 constexpr int max_waves(int pass)
 {
@@ -183,6 +184,11 @@ __global__ void sdp_fwd_c_kernel(const sdp::Params p);
 __global__ void sdp_fwd_x_tp_c_kernel(const sdp::Params p);
 __global__ void sdp_fwd_lat_c_kernel(const sdp::Params p);
 __global__ void sdp_fwd_x_c_kernel(const sdp::Params p);
+__global__ void sdp_val_kernel(const sdp::Params p);
+__global__ void sdp_val_c_kernel(const sdp::Params p);
+__global__ void sdp_val_g_kernel(const sdp::Params p);
+__global__ void sdp_val_lat_kernel(const sdp::Params p);
+__global__ void sdp_val_lat_c_kernel(const sdp::Params p);
 __global__ void sdp_bwd_kernel(const sdp::Params p);
 __global__ void sdp_bwd_pipe_kernel(const sdp::Params p);
 __global__ void sdp_bwd_lat_kernel(const sdp::Params p);

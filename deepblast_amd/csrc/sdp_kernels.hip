@@ -390,10 +390,18 @@ __device__ __forceinline__ float loss_dterm(float r, float y, float sc, int kind
 // start on K-float boundaries (M a multiple of 32, 128-byte aligned tensors): the same formulas with the offsets
 // folded to constants -- the host picks per launch (sdp_api.hip), and the headline shape pays nothing for generality
 // (with one instantiation for both, the forward kernel measured +5 % and the backward +3 % at M = 512).
-template <int PASS, int K, bool QX = false, bool LINES = false, bool GEN = false, bool PARTS = false, bool NOPIPE = false, bool NOCLEAN = false>
+// VALUE: the forward sweep for callers that want Vt alone (sdp_forward_value_f32: search / scoring).  The recurrence, its two forms, the
+// hand-off between strips and the terminal value are the packed-state forward build's, instruction for instruction; what is compiled
+// out is everything that exists for the state only -- the reciprocal of a cell's sum, its weights, their sharpening, the 20-bit
+// packing and the state stores.  Vt has the bits the stateful sweep gives it.  One workgroup per pair (no PARTS: the bridge rows and
+// the dispatch map of a parts launch live in the state buffer, and this call has none).
+template <int PASS, int K, bool QX = false, bool LINES = false, bool GEN = false, bool PARTS = false, bool NOPIPE = false, bool NOCLEAN = false,
+          bool VALUE = false>
 __device__ __forceinline__ void sweep(const Params &p)
 {
     using T = Traits<PASS, QX>;
+    static_assert(!VALUE || (PASS == PASS_FWD && !QX && !PARTS), "the value-only build is the packed-arithmetic forward sweep, one workgroup per pair");
+    constexpr int QOUT = VALUE ? Q_NONE : T::QOUT;   // the state this pass writes
     constexpr bool REV = T::REV;
     constexpr int KIND = Kind<PASS>::value;
     constexpr bool CLEAN = PASS == PASS_FWD && !NOCLEAN;   // forward sweep: what lies beside the matrix takes no part in anything (see need_clean)
@@ -618,8 +626,8 @@ __device__ __forceinline__ void sweep(const Params &p)
         //  per-lane skipping in round 4 (partial 128-byte lines at the edge of a ramp: forward 210 -> 215 us), whole dead lines in
         //  round 5 (bit-identical; forward alone 193 -> 185 us, nothing in the forward;backward sequence).  DESIGN_HISTORY.md.)
         __amdgpu_buffer_rsrc_t rs_q = make_rsrc(T::QIN == Q_PACKED ? (const void *)(reinterpret_cast<const char *>(p.qin) + ps_idx * p.st_ps)
-                                                : (T::QOUT == Q_PACKED ? (const void *)(static_cast<char *>(p.dout) + ps_idx * p.st_ps) : (const void *)p.vout),
-                                                (T::QIN == Q_PACKED || T::QOUT == Q_PACKED) ? ST_RECORDS : 0u);
+                                                : (QOUT == Q_PACKED ? (const void *)(static_cast<char *>(p.dout) + ps_idx * p.st_ps) : (const void *)p.vout),
+                                                (T::QIN == Q_PACKED || QOUT == Q_PACKED) ? ST_RECORDS : 0u);
         // Packed state: a 16-step BLOCK of a lane is 20 dwords (four records of five), kept as five rows of 1024 B -- row j holds
         // dwords 4j .. 4j+3 of every lane -- so that every access is a whole dwordx4 of contiguous 1 KB per wave: five memory
         // instructions per 16 steps.  A 32-step unit is two blocks, ten rows.  Scalar offset of row jr (0..4) of the block that
@@ -670,8 +678,8 @@ __device__ __forceinline__ void sweep(const Params &p)
                                                        : (T::DOUT ? (const void *)(static_cast<char *>(p.dout) + ps_idx * p.st2_ps) : (const void *)p.vout),
                                                 (T::DIN || T::DOUT) ? ST_RECORDS : 0u);
         __amdgpu_buffer_rsrc_t rs_qx = make_rsrc(T::QIN == Q_EXACT ? (const void *)(reinterpret_cast<const char *>(p.qin) + ps_idx * p.st2_ps)
-                                                 : (T::QOUT == Q_EXACT ? (const void *)(static_cast<char *>(p.dout) + ps_idx * p.st2_ps) : (const void *)p.vout),
-                                                 (T::QIN == Q_EXACT || T::QOUT == Q_EXACT) ? ST_RECORDS : 0u);
+                                                 : (QOUT == Q_EXACT ? (const void *)(static_cast<char *>(p.dout) + ps_idx * p.st2_ps) : (const void *)p.vout),
+                                                 (T::QIN == Q_EXACT || QOUT == Q_EXACT) ? ST_RECORDS : 0u);
         // scalar offset of row t_base + k8 (k8 = 0, 8, 16, 24)
         auto f2_soff = [&](int t_base, int k8) { return (unsigned)(t_base >> 5) * p.st2_us + (unsigned)(((t_base & 31) + k8) * 512); };
         auto load_f2 = [&](__amdgpu_buffer_rsrc_t rs, int t_base, int k) {  // row t_base + k
@@ -711,9 +719,9 @@ __device__ __forceinline__ void sweep(const Params &p)
         };
         // the state this pass produces, step t_base + k
         auto store_state = [&](int t_base, int k, float2 qq) {
-            if constexpr (T::QOUT == Q_PACKED) {
+            if constexpr (QOUT == Q_PACKED) {
                 store_state_bits(t_base, k, __float_as_uint(__builtin_fmaf(qq.x, QF_SCALE, QF_BASE)), __float_as_uint(__builtin_fmaf(qq.y, QF_SCALE, QF_BASE)));
-            } else if constexpr (T::QOUT == Q_EXACT) {
+            } else if constexpr (QOUT == Q_EXACT) {
                 store_f2(rs_qx, t_base, k, qq);
             } else {
                 store_f2(rs_d, t_base, k, qq);
@@ -1523,7 +1531,9 @@ __device__ __forceinline__ void sweep(const Params &p)
                             const float ssum = __builtin_fmaf(ca, u + x, d);
                             const float rinv = __builtin_amdgcn_rcpf(ssum);
                             const float tq = ca * rinv;
-                            if constexpr (QX) {
+                            if constexpr (VALUE) {
+                                // no state: the weights are not formed (rinv and tq are dead, the compiler drops them)
+                            } else if constexpr (QX) {
                                 float2 qq = make_float2(tq * u, tq * x);
                                 q_sharpen(qq.x, qq.y, d * rinv);
                                 if constexpr (ABL_NOSTORE) { keep(qq.x); keep(qq.y); }
@@ -1631,7 +1641,7 @@ __device__ __forceinline__ void sweep(const Params &p)
                             //  spread over the whole pair: Vtd = NaN in 3 of 4000 cases of round 5's last soak, thin problems with 20 % forbidden gaps)
                             const float rinv = ssum >= 1.1754944e-38f ? __builtin_amdgcn_rcpf(ssum) : 0.f;
                             const float tq = ca * rinv;
-                            {
+                            if constexpr (!VALUE) {
                                 float2 qq = make_float2(tq * u, tq * l);
                                 // every build sharpens here: a block lands in this form when its scores are steep, and
                                 // steep scores are where paths saturate -- a packed weight left at 1 - 2^-23 instead of 1
@@ -2425,7 +2435,7 @@ __device__ __forceinline__ void sweep(const Params &p)
                     if constexpr (T::DIN) q1 = rdd2[P][k];
 
                     if constexpr (ABL_NOMATH) {
-                        if constexpr (T::QOUT != Q_NONE || T::DOUT) {
+                        if constexpr (QOUT != Q_NONE || T::DOUT) {
                             float2 qq = make_float2(in0[k], T::QIN != Q_NONE ? q0.x + q0.y : in1[k]);
                             if constexpr (ABL_NOSTORE) { keep(qq.x); keep(qq.y); } else store_state(t0, k, qq);
                         }
@@ -2602,6 +2612,16 @@ SDP_KERNEL(sdp_bwd_x_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, true)
 SDP_KERNEL(sdp_adj_bwd_kernel, sdp::PASS_ABWD, SDP_K_ABWD, SDP_MAXW_ABWD)
 #elif defined(SDP_ONLY) && SDP_ONLY == 2
 SDP_KERNEL(sdp_adj_fwd_kernel, sdp::PASS_AFWD, SDP_K_AFWD, SDP_MAXW_AFWD)
+#elif defined(SDP_ONLY) && SDP_ONLY == 41
+SDP_KERNEL(sdp_val_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, false, false, false, true, true)
+#elif defined(SDP_ONLY) && SDP_ONLY == 42
+SDP_KERNEL(sdp_val_c_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, false, false, false, false, true)
+#elif defined(SDP_ONLY) && SDP_ONLY == 43
+SDP_KERNEL(sdp_val_g_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, true, false, false, false, true)
+#elif defined(SDP_ONLY) && SDP_ONLY == 44
+SDP_KERNEL(sdp_val_lat_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, false, false, false, false, false, true, true)
+#elif defined(SDP_ONLY) && SDP_ONLY == 45
+SDP_KERNEL(sdp_val_lat_c_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, false, false, false, false, false, false, true)
 #else
 // (-DSDP_GROUP=<g>: compile one group of kernels -- deepblast_amd/build.py builds the groups of this file in parallel and links
 //  them; without it, everything.  Group 0 holds the small kernels at the end of the file.)
@@ -2611,6 +2631,7 @@ SDP_KERNEL(sdp_adj_fwd_kernel, sdp::PASS_AFWD, SDP_K_AFWD, SDP_MAXW_AFWD)
 #define SDP_IN_GROUP(g) (SDP_GROUP < 0 || SDP_GROUP == (g))
 // template arguments after MAXW: QX (exact state / fused loss seed), LINES (throughput forward builds: line-aligned input blocks),
 // GEN (general pitch), PARTS (a pair over several workgroups), NOPIPE (packed backward sweep without the pipelined chunk)
+// (... VALUE, last: the forward sweep without any state output)
 // (... NOCLEAN: the aligned throughput forward builds without the edge cleaning -- full strips, no per-pair lengths; their _c twins carry it)
 #if SDP_IN_GROUP(1)
 SDP_KERNEL(sdp_fwd_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, false, false, false, true)
@@ -2654,6 +2675,17 @@ SDP_KERNEL(sdp_bwd_p_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, false, fals
 SDP_KERNEL(sdp_bwd_x_p_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, true, false, false, true)
 SDP_KERNEL(sdp_bwd_pg_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, false, false, true, true)
 SDP_KERNEL(sdp_bwd_x_pg_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, true, false, true, true)
+#endif
+// value-only forward builds (VALUE = true: Vt and nothing else, sdp_forward_value_f32): the throughput build without and with the edge
+// cleaning and its general-pitch twin, the latency build without and with the cleaning -- the packed-state forward builds 0 / 37 / 11 / 6 / 39
+#if SDP_IN_GROUP(9)
+SDP_KERNEL(sdp_val_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, false, false, false, true, true)
+SDP_KERNEL(sdp_val_c_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, false, false, false, false, true)
+SDP_KERNEL(sdp_val_g_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, true, false, false, false, true)
+#endif
+#if SDP_IN_GROUP(10)
+SDP_KERNEL(sdp_val_lat_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, false, false, false, false, false, true, true)
+SDP_KERNEL(sdp_val_lat_c_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, false, false, false, false, false, false, true)
 #endif
 // general-pitch instantiations (GEN = true) of the kernels that stage outputs, and of the line-aligned forward builds
 #if SDP_IN_GROUP(6)

@@ -12,3 +12,4 @@ NeedlemanWunschFunction, NeedlemanWunschFunctionBackward = _dp.make_functions(NW
 
 class NeedlemanWunschDecoder(_dp._Decoder):
     _function = NeedlemanWunschFunction
+    _variant = NW

@@ -15,3 +15,5 @@ SmithWatermanFunction, SmithWatermanFunctionBackward = _dp.make_functions(SW, "S
 
 class SmithWatermanDecoder(_dp._Decoder):
     _function = SmithWatermanFunction
+    _variant = SW
+    _allow_none_operator = True

@@ -148,6 +148,25 @@ size_t sdp_state_d_bytes_v(int B, int N, int M, int variant);
 int sdp_forward_f32(const float *theta, const float *A, float *state, float *Vt, int B, int N,
                     int M, const int32_t *lens, int variant, int device, void *stream);
 
+/* The forward sweep for callers that want Vt alone (search / scoring: the reference's NeuralAligner.score keeps only Vt,
+ * deepblast/alignment.py:127-137, and scripts/deepblast-search loops it over a database).  Vt[b] = V[n_b, m_b] and NOTHING else
+ * is written: no state is formed, staged or stored, and there is no state buffer.  Same arithmetic as the packed-state forward
+ * sweep -- Vt has the bits sdp_forward_f32 gives it on the same chunk length and wave count.  Added after SDP_VERSION 106 without
+ * a version change: look the symbol up to detect it.
+ *   ws       workspace of sdp_forward_value_ws_bytes(B, N, M) bytes (the launch order of a variable-length batch with more
+ *            pairs than CUs: B ints, 256-byte granules), DEVICE, caller-owned, written only inside those bytes.  May be NULL
+ *            when lens is NULL; with lens it is required (SDP_E_NULLPTR).
+ *   variant  SDP_NW / SDP_SW | SDP_WAVES(w).  SDP_EXACT_STATE, SDP_REF_ROUNDING, SDP_ET_BROADCAST and SDP_NO_FILL are refused
+ *            (SDP_E_VARIANT): there is no state whose format could be chosen, no Et and no E; the reference-rounding mode
+ *            has no fast path -- run sdp_forward_f32 | SDP_REF_ROUNDING and drop its state.
+ * One workgroup per pair always: a pair is never spread over several workgroups (sdp_plan_parts), because the bridge rows
+ * and the dispatch map of such a launch live in the state buffer and this call has none.  M <= sdp_max_cols(); errors are
+ * reported as for the other sweeps (SDP_E_NULLPTR, SDP_E_SHAPE, SDP_E_MAXCOLS, SDP_E_TOOBIG, SDP_E_HANDOFF).
+ * sdp_forward_value_ws_bytes: 0 on a bad shape. */
+size_t sdp_forward_value_ws_bytes(int B, int N, int M);
+int sdp_forward_value_f32(const float *theta, const float *A, float *Vt, void *ws, int B, int N, int M,
+                          const int32_t *lens, int variant, int device, void *stream);
+
 /* E = dVt/dtheta * Et  (expected alignment matrix), from the saved state. */
 int sdp_backward_f32(const float *Et, const float *state, float *E, int B, int N, int M,
                      const int32_t *lens, int variant, int device, void *stream);
@@ -385,7 +404,10 @@ int sdp_device_status(int device, int32_t info[4]);
  * lines -- M a multiple of 32; other launches use the "general pitch" instantiations of the same builds, ids 11-20.
  * Ids 21-28: the throughput builds with the bridge between workgroups, see sdp_plan_parts.)
  * pass 2 | SDP_PLAN_FUSED_SEED: the adjoint forward sweep with the fused loss seed (sdp_adjoint_forward_loss_f32, build
- * 10), which stages three planes instead of two. */
+ * 10), which stages three planes instead of two.
+ * pass 4: the value-only forward sweep (sdp_forward_value_f32) -- builds 41 throughput, 42 throughput with the edge cleaning
+ * (per-pair lengths, N not a multiple of 64), 43 their general-pitch twin, 44 / 45 latency without / with the cleaning;
+ * exact_state is ignored. */
 #define SDP_PLAN_FUSED_SEED 0x100
 int sdp_plan(int pass, int B, int N, int M, int has_lens, int exact_state, int cus, int *kernel_id, int *chunk,
              int *waves, size_t *lds);

@@ -38,6 +38,9 @@ for name, pattern in (("kernel_stats.csv", "prof/**/*kernel_stats.csv"), ("train
                       ("pmc_write_size.csv", "pmc_WRITE_SIZE/**/*counter_collection.csv"),
                       ("pmc_train_fetch_size.csv", "pmc_train_FETCH_SIZE/**/*counter_collection.csv"),
                       ("pmc_train_write_size.csv", "pmc_train_WRITE_SIZE/**/*counter_collection.csv"),
+                      ("pmc_value_fetch_size.csv", "pmc_value_FETCH_SIZE/**/*counter_collection.csv"),
+                      ("pmc_value_write_size.csv", "pmc_value_WRITE_SIZE/**/*counter_collection.csv"),
+                      ("value_kernel_stats.csv", "prof_value/**/*kernel_stats.csv"),
                       ("bench.json", "bench.json"), ("bench_train.json", "bench_train.json"),
                       ("scores_kernel_stats.csv", "prof_scores/**/*kernel_stats.csv"), ("configs_kernel_stats.csv", "prof_cfg/**/*kernel_stats.csv"),
                       ("scores_bwd_kernel_stats.csv", "prof_scores_bwd/**/*kernel_stats.csv"), ("scores_bwd.txt", "scores_bwd.txt"),
@@ -84,7 +87,7 @@ traffic = {"_stamp": stamp,
                     "doubled (MI355X_MICROARCH.md, HBM section: on gfx950 it reports half the bytes of wide coalesced reads; "
                     "calibrated on sdp_bwd_kernel, which must read exactly the packed state).  WRITE_SIZE as is.  The counters "
                     "sit on the fabric side of L2 and include Infinity-Cache hits."}
-for mode in ("", "train_"):
+for mode in ("", "train_", "value_"):   # (value_: the value-only forward sweep alone, tools/value_bench.py only=B cfg=1)
     fe, meta = counter_means(first(f"pmc_{mode}FETCH_SIZE/**/*counter_collection.csv"))
     wr, _ = counter_means(first(f"pmc_{mode}WRITE_SIZE/**/*counter_collection.csv"))
     for k in sorted(set(fe) | set(wr)):
@@ -97,4 +100,19 @@ for mode in ("", "train_"):
                       "fetch_size_raw_kb": f, "write_size_raw_kb": w, "fetch_correction": 2.0,
                       "launches_averaged": len(fe.get(k, [])), **meta.get(k, {})}
 json.dump(traffic, open(os.path.join(dst, "traffic.json"), "w"), indent=1)
+# the value-only forward sweep alone (tools/value_bench.py only=B cfg=1 under rocprofv3): its kernel time and its traffic go next to
+# the A/B figures in profiles/value_bench.json, if that file belongs to the same sources
+vb, ks = os.path.join(dst, "value_bench.json"), first("prof_value/**/*kernel_stats.csv")
+if os.path.exists(vb) and "sdp_val_kernel" in traffic:
+    doc = json.load(open(vb))
+    if doc.get("_stamp", {}).get("source_sha256") == stamp["source_sha256"]:
+        doc["profile_B_configs1"] = {"traffic": traffic["sdp_val_kernel"], "note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, one pass each, nothing else traced; "
+                                     "rocprofv3 --kernel-trace --stats in a run of its own.  WRITE_SIZE counts in KB: Vt is 1 KB"}
+        if ks:
+            row = [r for r in csv.DictReader(open(ks)) if r["Name"] == "sdp_val_kernel"]
+            if row:
+                doc["profile_B_configs1"]["kernel_us"] = {"calls": int(row[0]["Calls"]), "mean": float(row[0]["AverageNs"]) / 1e3,
+                                                          "min": float(row[0]["MinNs"]) / 1e3, "max": float(row[0]["MaxNs"]) / 1e3}
+        json.dump(doc, open(vb, "w"), indent=1)
+        print("-> profiles/value_bench.json: profile_B_configs1")
 print("-> profiles/traffic.json", {k: round(v["hbm_bytes_per_launch"] / 1e6, 1) for k, v in traffic.items() if not k.startswith("_") and v["hbm_bytes_per_launch"]})

@@ -31,14 +31,14 @@ if [ "$NGPU" -ge 2 ]; then
 else
   echo "multi-GPU dry run SKIPPED: $NGPU GPU visible (needs >= 2; nothing in this repo has run on more than one GPU yet)" | tee $OUT/multigpu_skipped.txt
 fi
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o fwdbwd -- env BENCH_NO_SECONDARY=1 python bench.py --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/rocprof.err
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_train -o train -- env BENCH_NO_SECONDARY=1 python bench.py --mode train --no-cpu-baseline > $OUT/bench_prof_train.json 2>> $OUT/rocprof.err
+BENCH_NO_SECONDARY=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o fwdbwd -- python bench.py --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/rocprof.err
+BENCH_NO_SECONDARY=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_train -o train -- python bench.py --mode train --no-cpu-baseline > $OUT/bench_prof_train.json 2>> $OUT/rocprof.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_scores -o scores -- python bench.py --mode scores+dp --full --no-cpu-baseline > $OUT/bench_prof_scores.json 2>> $OUT/rocprof.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_cfg -o cfg -- python tools/gpu_configs.py > $OUT/configs_prof.txt 2>> $OUT/rocprof.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_scores_bwd -o sb -- python tools/scores_bwd_probe.py 2>> $OUT/rocprof.err | grep ' us' > $OUT/scores_bwd.txt
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_$C -o fwdbwd -- env BENCH_NO_SECONDARY=1 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/pmc_$C.err
-  timeout 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_train_$C -o train -- env BENCH_NO_SECONDARY=1 python bench.py --steps 3 --warmup 1 --mode train --no-cpu-baseline > /dev/null 2>> $OUT/pmc_$C.err
+  BENCH_NO_SECONDARY=1 timeout 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_$C -o fwdbwd -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/pmc_$C.err
+  BENCH_NO_SECONDARY=1 timeout 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_train_$C -o train -- python bench.py --steps 3 --warmup 1 --mode train --no-cpu-baseline > /dev/null 2>> $OUT/pmc_$C.err
 done
 # the bench lines LAST, after profiles/traffic.json has been rebuilt (on this box's copy) from the counter passes of this
 # very visit: their roofline.traffic then is the figure measured minutes earlier on the same sources
