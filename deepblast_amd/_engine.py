@@ -53,20 +53,9 @@ class HipEngine:
         self.zero_skip = True
         self._labels = {}
 
-    # kernel ids of sdp_plan (csrc/sdp_api.hip: variant()) -> the symbol rocprofv3 will show for the launch
-    KERNEL_NAMES = {0: "sdp_fwd_kernel", 1: "sdp_bwd_kernel", 2: "sdp_adj_fwd_kernel", 3: "sdp_adj_bwd_kernel", 4: "sdp_bwd_lat_kernel",
-                    5: "sdp_fwd_x_kernel", 6: "sdp_fwd_lat_kernel", 7: "sdp_bwd_x_kernel", 8: "sdp_bwd_x_lat_kernel", 9: "sdp_fwd_x_tp_kernel",
-                    10: "sdp_adj_fwd_loss_kernel", 11: "sdp_fwd_g_kernel", 12: "sdp_bwd_g_kernel", 14: "sdp_adj_bwd_g_kernel",
-                    15: "sdp_bwd_lat_g_kernel", 18: "sdp_bwd_x_g_kernel", 19: "sdp_bwd_x_lat_g_kernel", 20: "sdp_fwd_x_tp_g_kernel",
-                    21: "sdp_fwd_p_kernel", 22: "sdp_fwd_x_tp_p_kernel", 23: "sdp_bwd_p_kernel", 24: "sdp_bwd_x_p_kernel",
-                    25: "sdp_fwd_pg_kernel", 26: "sdp_fwd_x_tp_pg_kernel", 27: "sdp_bwd_pg_kernel", 28: "sdp_bwd_x_pg_kernel",
-                    36: "sdp_bwd_pipe_kernel", 37: "sdp_fwd_c_kernel", 38: "sdp_fwd_x_tp_c_kernel", 39: "sdp_fwd_lat_c_kernel",
-                    40: "sdp_fwd_x_c_kernel", 41: "sdp_val_kernel", 42: "sdp_val_c_kernel", 43: "sdp_val_g_kernel",
-                    44: "sdp_val_lat_kernel", 45: "sdp_val_lat_c_kernel"}
-
     def _label(self, pass_, B, N, M, has_lens, exact, dev, default):
         """Name of the kernel a launch will use (for the launch hook: bench.py's per-kernel timers must carry the names the
-        rocprofv3 summaries carry).  Asked of the library's own launch policy (sdp_plan), once per problem."""
+        rocprofv3 summaries carry).  Asked of the library's own launch policy (sdp_plan, sdp_kernel_name), once per problem."""
         if self.launch_hook is None:
             return default
         key = (pass_, B, N, M, bool(has_lens), bool(exact), dev)
@@ -76,7 +65,8 @@ class HipEngine:
             kid = ctypes.c_int(-1)
             cus = torch.cuda.get_device_properties(dev).multi_processor_count
             rc = self.lib.sdp_plan(pass_, B, N, M, 1 if has_lens else 0, 1 if exact else 0, cus, ctypes.byref(kid), None, None, None)
-            got = self.KERNEL_NAMES.get(kid.value, default) if rc == 0 else default
+            name = self.lib.sdp_kernel_name(kid.value) if rc == 0 else None
+            got = name.decode() if name else default
             self._labels[key] = got
         return got
 

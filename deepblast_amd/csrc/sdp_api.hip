@@ -65,59 +65,71 @@ int fail_hip(hipError_t e, const char *what)
     return (int)e;
 }
 
-struct Variant {
-    const void *kernel;
-    int K, maxw, id;
+// One row of sdp_builds.def: what a build of the sweep is.  BUILDS is that table, and the only thing here that knows a build's
+// number: the launch policy (plan) asks for a build by its properties (find).
+struct Build {
+    int id;
+    const char *name;
+    void (*kernel)(const sdp::Params);
+    int pass, K, maxw, flags;   // flags: sdp::bf
 };
+using namespace sdp::bf;
+#define SDP_IN_GROUP(g) 1
+#define SDP_BUILD(ID, NAME, PASS, K, MAXW, FLAGS) {ID, #NAME, NAME, sdp::PASS, K, MAXW, FLAGS},
+constexpr Build BUILDS[] = {
+#include "sdp_builds.def"
+};
+#undef SDP_IN_GROUP
+constexpr int NBUILDS = sizeof(BUILDS) / sizeof(BUILDS[0]);
 
-// kernel builds: [0] fwd (throughput: K=32, <= 4 waves), [1] bwd (throughput: K=32, <= 4 waves), [2] adj-fwd,
-// [3] adj-bwd, [4] bwd (latency: K=16, <= 8 waves), [5] fwd writing the exact (float2) state for the adjoint
-// sweeps, [6] fwd (latency: K=16, <= 8 waves), [7] / [8] bwd reading the exact state (throughput / latency), [9] fwd writing the exact state (throughput)
-Variant variant(int id)
+// the columns that tell the builds of one pass apart (LINES follows from the pass and LAT)
+constexpr int SELECT = QX | GEN | PARTS | NOPIPE | NOCLEAN | VALUE | LAT;
+// ... and what a wanted property means to a pass whose builds do not have the column:
+constexpr int settle(int pass, int want)
 {
-    switch (id) {
-    case 0: return {(const void *)sdp_fwd_kernel, SDP_K_FWD, SDP_MAXW_FWD, 0};
-    case 1: return {(const void *)sdp_bwd_kernel, SDP_K_BWD, SDP_MAXW_BWD_Q, 1};
-    case 2: return {(const void *)sdp_adj_fwd_kernel, SDP_K_AFWD, SDP_MAXW_AFWD, 2};
-    case 3: return {(const void *)sdp_adj_bwd_kernel, SDP_K_ABWD, SDP_MAXW_ABWD, 3};
-    case 5: return {(const void *)sdp_fwd_x_kernel, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, 5};
-    case 6: return {(const void *)sdp_fwd_lat_kernel, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, 6};
-    case 7: return {(const void *)sdp_bwd_x_kernel, SDP_K_BWD, SDP_MAXW_BWD, 7};
-    case 8: return {(const void *)sdp_bwd_x_lat_kernel, SDP_K_BWD_LAT, SDP_MAXW_BWD_LAT, 8};
-    case 9: return {(const void *)sdp_fwd_x_tp_kernel, SDP_K_FWD, SDP_MAXW_FWD, 9};
-    case 10: return {(const void *)sdp_adj_fwd_loss_kernel, SDP_K_AFWD, 4, 10};  // adj-fwd with the loss seed formed in the kernel
-    // general-pitch instantiations (staged blocks aligned to lines of memory through run-time per-row offsets): id + 11
-    case 11: return {(const void *)sdp_fwd_g_kernel, SDP_K_FWD, SDP_MAXW_FWD, 11};
-    case 12: return {(const void *)sdp_bwd_g_kernel, SDP_K_BWD, SDP_MAXW_BWD_Q, 12};   // (general pitch: 210 registers since round 6 -- the flush's index arrays are gone -- so eight waves fit, like the aligned build's)
-    case 14: return {(const void *)sdp_adj_bwd_g_kernel, SDP_K_ABWD, SDP_MAXW_ABWD, 14};
-    case 15: return {(const void *)sdp_bwd_lat_g_kernel, SDP_K_BWD_LAT, SDP_MAXW_BWD_LAT, 15};
-    case 18: return {(const void *)sdp_bwd_x_g_kernel, SDP_K_BWD, SDP_MAXW_BWD, 18};
-    case 19: return {(const void *)sdp_bwd_x_lat_g_kernel, SDP_K_BWD_LAT, SDP_MAXW_BWD_LAT, 19};
-    case 20: return {(const void *)sdp_fwd_x_tp_g_kernel, SDP_K_FWD, SDP_MAXW_FWD, 20};
-    // PARTS instantiations of the throughput builds (a pair over several workgroups): 21 + (fwd, fwd exact, bwd, bwd exact), + 4 general pitch
-    case 21: return {(const void *)sdp_fwd_p_kernel, SDP_K_FWD, SDP_MAXW_FWD, 21};
-    case 22: return {(const void *)sdp_fwd_x_tp_p_kernel, SDP_K_FWD, SDP_MAXW_FWD, 22};
-    case 23: return {(const void *)sdp_bwd_p_kernel, SDP_K_BWD, SDP_MAXW_BWD, 23};
-    case 24: return {(const void *)sdp_bwd_x_p_kernel, SDP_K_BWD, SDP_MAXW_BWD, 24};
-    case 25: return {(const void *)sdp_fwd_pg_kernel, SDP_K_FWD, SDP_MAXW_FWD, 25};
-    case 26: return {(const void *)sdp_fwd_x_tp_pg_kernel, SDP_K_FWD, SDP_MAXW_FWD, 26};
-    case 27: return {(const void *)sdp_bwd_pg_kernel, SDP_K_BWD, SDP_MAXW_BWD, 27};
-    case 28: return {(const void *)sdp_bwd_x_pg_kernel, SDP_K_BWD, SDP_MAXW_BWD, 28};
-    case 36: return {(const void *)sdp_bwd_pipe_kernel, SDP_K_BWD, SDP_MAXW_BWD_Q, 36};   // [1] with the chunk as one software pipeline (long pairs)
-    // [0] / [9] with the cleaning of what lies beside the matrix (per-pair lengths, partial strips; sdp_kernels.hip "need_clean")
-    case 37: return {(const void *)sdp_fwd_c_kernel, SDP_K_FWD, SDP_MAXW_FWD, 37};
-    case 38: return {(const void *)sdp_fwd_x_tp_c_kernel, SDP_K_FWD, SDP_MAXW_FWD, 38};
-    case 39: return {(const void *)sdp_fwd_lat_c_kernel, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, 39};   // [6] ...
-    case 40: return {(const void *)sdp_fwd_x_c_kernel, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, 40};     // [5] ...
-    // the value-only forward sweep (sdp_forward_value_f32: Vt, no state): [0] / [37] / [11] / [6] / [39] with the state path compiled out
-    case 41: return {(const void *)sdp_val_kernel, SDP_K_FWD, SDP_MAXW_FWD, 41};
-    case 42: return {(const void *)sdp_val_c_kernel, SDP_K_FWD, SDP_MAXW_FWD, 42};
-    case 43: return {(const void *)sdp_val_g_kernel, SDP_K_FWD, SDP_MAXW_FWD, 43};
-    case 44: return {(const void *)sdp_val_lat_kernel, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, 44};
-    case 45: return {(const void *)sdp_val_lat_c_kernel, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, 45};
-    default: return {(const void *)sdp_bwd_lat_kernel, SDP_K_BWD_LAT, SDP_MAXW_BWD_LAT, 4};
+    // general pitch: builds whose staged blocks keep the column-aligned geometry at any pitch have no twin -- the latency forward
+    // builds, the adjoint forward
+    if ((pass == sdp::PASS_FWD && (want & LAT)) || pass == sdp::PASS_AFWD) want &= ~GEN;
+    // only the forward sweep cleans, and its general-pitch and parts builds always do
+    if (pass != sdp::PASS_FWD || (want & (GEN | PARTS))) want &= ~NOCLEAN;
+    // only the packed throughput backward build exists with and without the pipelined chunk
+    if (pass != sdp::PASS_BWD || (want & (QX | LAT | GEN | PARTS))) want &= ~NOPIPE;
+    return want;
+}
+// the one build of `pass` with the wanted properties; nullptr if there is none, or more than one
+constexpr const Build *find(int pass, int want)
+{
+    want = settle(pass, want);
+    const Build *hit = nullptr;
+    for (const Build &b : BUILDS)
+        if (b.pass == pass && (b.flags & SELECT) == want) {
+            if (hit) return nullptr;
+            hit = &b;
+        }
+    return hit;
+}
+// Checked when this file is compiled: no id twice, and every build plan() can ask for exists exactly once -- any combination of
+// `free` beside `fixed`.  A row added to or taken from sdp_builds.def that leaves the policy without its build, or with two, fails here.
+constexpr bool served(int pass, int fixed, int free)
+{
+    for (int s = free;; s = (s - 1) & free) {
+        if (!find(pass, fixed | s)) return false;
+        if (!s) return true;
     }
 }
+constexpr bool ids_differ()
+{
+    for (int i = 0; i < NBUILDS; ++i)
+        for (int j = 0; j < i; ++j)
+            if (BUILDS[i].id == BUILDS[j].id) return false;
+    return true;
+}
+static_assert(ids_differ(), "sdp_builds.def: two builds with one id");
+static_assert(served(sdp::PASS_FWD, 0, LAT | QX | NOCLEAN | GEN | NOPIPE) && served(sdp::PASS_FWD, VALUE, LAT | NOCLEAN | GEN | NOPIPE) &&
+                  served(sdp::PASS_BWD, 0, LAT | QX | NOCLEAN | GEN | NOPIPE) && served(sdp::PASS_FWD, PARTS, QX | GEN) &&
+                  served(sdp::PASS_BWD, PARTS, QX | GEN) && served(sdp::PASS_AFWD, 0, QX | NOCLEAN | GEN | NOPIPE) &&
+                  served(sdp::PASS_ABWD, 0, NOCLEAN | GEN | NOPIPE),
+              "sdp_builds.def: the launch policy can ask for a build that does not exist, or exists twice");
 
 int num_cus(int device)
 {
@@ -150,36 +162,26 @@ int check_shape(int B, int N, int M, int variant)
 // What a launch will use: which kernel build, how many waves per pair, how much LDS.  Pure function of the
 // problem and the CU count (no device access), so that the policy can be tested without a GPU (sdp_plan).
 struct Plan {
-    Variant v;
+    const Build *v;
     int W;
     size_t lds, stage_off;
     int parts;   // strips per workgroup when the pairs are spread over several workgroups (0: one workgroup per pair)
 };
 
-// kernel id -> its general-pitch instantiation (or itself if it has none: builds whose staged blocks keep the
-// column-aligned geometry -- latency forward builds, the adjoint forward)
-int general_id(int id)
-{
-    switch (id) {
-    case 0: case 37: return 11;
-    case 1: return 12;
-    case 3: return 14;
-    case 4: return 15;
-    case 7: return 18;
-    case 8: return 19;
-    case 9: case 38: return 20;
-    default: return id;
-    }
-}
+// What a launch does about the state: the packed state (two 20-bit weights per cell), the exact (float2) state, the adjoint forward
+// sweep's fused loss seed, or none at all -- the value-only forward sweep, which is the forward sweep without a state: no state
+// format to pick, no state buffer to keep bridge rows in (no parts), nothing to route.
+enum StateKind { ST_PACKED, ST_EXACT, ST_SEED, ST_VALUE };
 
 // Strips per part when a pair is spread over several workgroups (sdp_kernels.hip, "PARTS"): one strip per wave of the
 // 4-wave throughput builds.
 constexpr int PART_STRIPS = 4;
 inline int parts_per_pair(int N) { return (sdp::state_nstrips(N) + PART_STRIPS - 1) / PART_STRIPS; }
 
-Plan plan(int pass, int B, int N, int M, bool has_lens, bool exact_state, int cus, int forced_waves, bool fused_seed = false,
-          bool general_pitch = false, int allow_parts = 1 /* 0 never, 1 where it pays, 2 wherever it is possible */)
+Plan plan(int pass, int B, int N, int M, bool has_lens, StateKind st, int cus, int forced_waves, bool general_pitch = false,
+          int allow_parts = 1 /* 0 never, 1 where it pays, 2 wherever it is possible */)
 {
+    const bool exact_state = st == ST_EXACT;
     const int nstrips = sdp::state_nstrips(N);
     const int mcap = (M + 63) / 64 * 64;
     // Waves per pair.  A batch that occupies the GPU is bound by HBM/fabric traffic and runs best with one wave
@@ -192,7 +194,10 @@ Plan plan(int pass, int B, int N, int M, bool has_lens, bool exact_state, int cu
     // up to 64 pairs and is at 170-190 us from 80 on, where the throughput build takes 148-151 -- ~72 pairs; the backward sweep's
     // 8-wave form is level with its 4-wave form up to 128 pairs
     const bool full = (pass == sdp::PASS_FWD ? B * 7 >= cus * 2 : B * 2 >= cus) && !(has_lens && B <= 2 * cus);
-    Variant v = variant(pass);
+    // The build, by what it is (sdp_builds.def): the decisions below gather its properties in `want`, and find() settles the ones a
+    // pass's builds do not have.  To begin with the pass's throughput build, without edge cleaning and without the pipelined chunk.
+    int want = NOCLEAN | NOPIPE | (st == ST_VALUE ? VALUE : 0);
+    const Build *v = find(pass, want);
     int W = forced_waves;
     if (W <= 0) {
         W = (sweep12 || pass == sdp::PASS_AFWD) ? (full ? 4 : 8) : SDP_DEFAULT_WAVES;  // (adj-bwd is compiled for <= 4)
@@ -207,29 +212,24 @@ Plan plan(int pass, int B, int N, int M, bool has_lens, bool exact_state, int cu
         const int w4 = nstrips < 4 ? nstrips : 4;
         // (the packed backward build runs up to 8 waves since round 5, its general-pitch twin since round 6 -- the exact-state twins
         //  only 4: a launch that will end up in one of those is judged by their limit)
-        const int maxw = (pass == sdp::PASS_BWD && exact_state) ? SDP_MAXW_BWD : v.maxw;
-        if (W > maxw || lds_bytes(pass, v.K, w4, mcap, nullptr) > 160 * 1024) v = variant(pass == sdp::PASS_FWD ? 6 : 4);
+        const int maxw = (pass == sdp::PASS_BWD && exact_state) ? SDP_MAXW_BWD : v->maxw;
+        if (W > maxw || lds_bytes(pass, v->K, w4, mcap, nullptr) > 160 * 1024) want |= LAT;
+        if (exact_state) want |= QX;
     }
-    if (pass == sdp::PASS_FWD && exact_state) v = variant(v.id == 0 ? 9 : 5);
-    if (pass == sdp::PASS_BWD && exact_state) v = variant(v.id == 1 ? 7 : 8);
-    const int nin = (pass == sdp::PASS_AFWD && fused_seed) ? 3 : 0;   // three staged planes (ref, pred, G)
-    if (nin) v = variant(10);
+    const int nin = (pass == sdp::PASS_AFWD && st == ST_SEED) ? 3 : 0;   // three staged planes (ref, pred, G)
+    if (nin) want |= QX;
     // the aligned-pitch forward builds come without any edge cleaning (sdp_kernels.hip "need_clean"); per-pair lengths or partial
     // strips take their twins that carry it
-    if (pass == sdp::PASS_FWD && (has_lens || (N & 63) != 0)) {
-        if (v.id == 0) v = variant(37);
-        else if (v.id == 9) v = variant(38);
-        else if (v.id == 6) v = variant(39);
-        else if (v.id == 5) v = variant(40);
-    }
-    if (general_pitch) v = variant(general_id(v.id));
+    if (pass == sdp::PASS_FWD && (has_lens || (N & 63) != 0)) want &= ~NOCLEAN;
+    if (general_pitch) want |= GEN;
     // The packed backward sweep's pipelined twin (sdp_kernels.hip, sdp_bwd_pipe_kernel) trades instruction issue for memory
     // latency.  Steady-state A/B over 24 shapes (tools/steady.py, +- 0.3 us; profiles/r05_steady_pipe.txt): it pays 2.3 % where
     // every CU holds ONE pair of long rows (256 x 1024^2, 256 x 512 x 1024), is level at 256 x 768 x 640 / 300 x 2000 / 192 x 1024^2, and
     // costs 1.1-3.7 % everywhere else -- shorter rows (the headline 256 x 512^2: 279.0 vs 272.5 us; 256 x 2048 x 256: 2.7 %), fewer
     // pairs than CUs (128 x 1024^2), more (384 x 1024^2, 512 x 768^2), 8 waves per pair (64 x 512^2).  So: only there.
     const bool bwd_pipe_pays = W == 4 && B <= cus && B * 8 >= cus * 7 && M >= 1024 && (long long)N * M >= 450000;
-    if (v.id == 1 && bwd_pipe_pays) v = variant(36);
+    if (bwd_pipe_pays) want &= ~NOPIPE;   // (find: a general-pitch launch has no such twin and keeps its build)
+    v = find(pass, want);
     // A pair over several workgroups (sdp_kernels.hip, "PARTS"): parts of four strips, each on a CU of its own, one strip
     // per wave of the 4-wave throughput builds, instead of one CU taking all the pair's strips in rounds.  It pays only
     // where CUs would otherwise idle AND the pair is long enough for the extra lag per bridge (measured, round 3, us
@@ -244,7 +244,7 @@ Plan plan(int pass, int B, int N, int M, bool has_lens, bool exact_state, int cu
     // only the backward sweep of pairs of four parts.  The adjoint pair (float64
     // carries) keeps one workgroup per pair.
     int parts = 0;
-    const bool parts_fit = sweep12 && forced_waves <= 0 && nstrips > PART_STRIPS;
+    const bool parts_fit = sweep12 && st != ST_VALUE && forced_waves <= 0 && nstrips > PART_STRIPS;
     // Round 5, re-measured after the backward sweep's changes (profiles/r05_parts_table.txt; us, one workgroup per pair -> parts):
     // with per-pair lengths the BACKWARD sweep no longer gains from parts anywhere but at BASELINE configs[2] (540 -> 512-522,
     // and 515 when only the forward sweep uses them) and loses elsewhere (<= 640^2: 213 -> 236, <= 512^2: 146 -> 160, 64 pairs
@@ -254,18 +254,18 @@ Plan plan(int pass, int B, int N, int M, bool has_lens, bool exact_state, int cu
     const bool parts_pay = B <= cus && (has_lens ? (pass == sdp::PASS_FWD && nstrips > 2 * PART_STRIPS)
                                                  : (pass == sdp::PASS_BWD && nstrips > 3 * PART_STRIPS && (long long)B * parts_per_pair(N) <= cus));
     if (parts_fit && (allow_parts == 2 || (allow_parts == 1 && parts_pay))) {
-        const Variant tv = variant(21 + (pass == sdp::PASS_FWD ? 0 : 2) + (exact_state ? 1 : 0) + (general_pitch ? 4 : 0));
-        if (lds_bytes(pass, tv.K, PART_STRIPS, mcap, nullptr) <= 160 * 1024) {
+        const Build *tv = find(pass, (want & (QX | GEN)) | PARTS);
+        if (lds_bytes(pass, tv->K, PART_STRIPS, mcap, nullptr) <= 160 * 1024) {
             v = tv;
             W = PART_STRIPS;
             parts = PART_STRIPS;
         }
     }
-    if (W > v.maxw) W = v.maxw;
+    if (W > v->maxw) W = v->maxw;
     if (W > nstrips) W = nstrips;
     size_t off = 0, lds = 0;
     for (;; --W) {  // fewer waves if the boundary rows (long M) plus staging exceed the 160 KiB of LDS
-        lds = lds_bytes(pass, v.K, W, mcap, &off, nin);
+        lds = lds_bytes(pass, v->K, W, mcap, &off, nin);
         if (lds <= 160 * 1024 || W == 1) break;
     }
     // Two-wave workgroups (more pairs than CUs) are meant to share a CU in PAIRS, one wave per SIMD.  Since round 5 the backward
@@ -273,41 +273,6 @@ Plan plan(int pass, int B, int N, int M, bool has_lens, bool exact_state, int cu
     // speed, other CUs short of work: 247 -> 262 us at 512 x 512^2.  Asking for half a CU's LDS keeps it at two.
     if (sweep12 && W == 2 && B > cus && lds < 80 * 1024) lds = 80 * 1024;
     return {v, W, lds, off, parts};
-}
-
-// The value-only forward sweep (sdp_forward_value_f32).  It runs the forward sweep's builds with the state path compiled out, and
-// its policy is the forward sweep's wherever that keeps one workgroup per pair: the throughput build (K = 32, <= 4 waves) for
-// batches that fill the GPU, the latency build (K = 16, <= 8 waves) for smaller ones, for batches with per-pair lengths that do not
-// queue up and where four waves' staging does not fit beside long boundary rows; two waves per pair where that saves rounds; the
-// twins with the edge cleaning for per-pair lengths and partial strips; the general-pitch twin of the throughput build.  No parts:
-// bridge rows and dispatch map would have to live in a state buffer, and this call has none.  The staged inputs take the LDS they
-// take in the forward sweep (the state never went through LDS), so the wave counts that fit are the same.
-Plan plan_value(int B, int N, int M, bool has_lens, int cus, int forced_waves, bool general_pitch = false)
-{
-    const int pass = sdp::PASS_FWD;
-    const int nstrips = sdp::state_nstrips(N);
-    const int mcap = (M + 63) / 64 * 64;
-    const bool full = B * 7 >= cus * 2 && !(has_lens && B <= 2 * cus);
-    Variant v = variant(41);
-    int W = forced_waves;
-    if (W <= 0) {
-        W = full ? 4 : 8;
-        const int r4 = (B + cus - 1) / cus, r2 = (B + 2 * cus - 1) / (2 * cus);
-        if (full && B > cus && 181 * r2 < 100 * r4) W = 2;
-    }
-    const int w4 = nstrips < 4 ? nstrips : 4;
-    if (W > v.maxw || lds_bytes(pass, v.K, w4, mcap, nullptr) > 160 * 1024) v = variant(44);
-    if (has_lens || (N & 63) != 0) v = variant(v.id == 41 ? 42 : 45);
-    if (general_pitch && v.K == SDP_K_FWD) v = variant(43);   // (the latency builds' staged blocks keep the column-aligned geometry at any pitch)
-    if (W > v.maxw) W = v.maxw;
-    if (W > nstrips) W = nstrips;
-    size_t off = 0, lds = 0;
-    for (;; --W) {
-        lds = lds_bytes(pass, v.K, W, mcap, &off);
-        if (lds <= 160 * 1024 || W == 1) break;
-    }
-    if (W == 2 && B > cus && lds < 80 * 1024) lds = 80 * 1024;   // two-wave workgroups share a CU in pairs (see plan)
-    return {v, W, lds, off, 0};
 }
 
 // Where the 32-step units of the skewed state live (sdp_kernels.hip, "Skewed state addressing"): every (pair, strip) is one
@@ -436,20 +401,30 @@ VariantBits split_variant(int variant)
 
 // raise the dynamic-LDS limit once per (thread, device, kernel) -- it is sticky, and the value is the
 // 160 KiB the hardware has, so concurrent callers cannot disagree
-int raise_lds_limit(const Variant &v, int device)
+int raise_lds_limit(const Build &v, int device)
 {
-    static thread_local unsigned long long lds_raised[46] = {0};  // per kernel id: bit d = done on device d
-    if (device >= 64 || !(lds_raised[v.id] >> device & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    static thread_local unsigned long long lds_raised[NBUILDS] = {0};  // per row of BUILDS: bit d = done on device d
+    const int row = (int)(&v - BUILDS);
+    if (device >= 64 || !(lds_raised[row] >> device & 1ull)) {
+        hipError_t e = hipFuncSetAttribute((const void *)v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return fail_hip(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-        if (device < 64) lds_raised[v.id] |= 1ull << device;
+        if (device < 64) lds_raised[row] |= 1ull << device;
     }
     return 0;
 }
 
-int launch(int pass, sdp::Params &p, int device, void *stream, bool exact_state = false, int forced_waves = 0, bool fused_seed = false,
-           const void *state = nullptr, int route = 0)
+// what a launch is told beside the pass and the kernel parameters
+struct LaunchOpts {
+    StateKind st = ST_PACKED;
+    int forced_waves = 0;          // SDP_WAVES(w) of the caller's `variant`, or 0: the policy's
+    const void *state = nullptr;   // the WHOLE batch's state buffer, in whose tail the bridge rows and the dispatch map of a parts launch
+                                   // live; null where there is none, or only part of one: the launch then keeps one workgroup per pair
+    int route = 0;                 // Params::route
+};
+
+int launch(int pass, sdp::Params &p, int device, void *stream, const LaunchOpts &o)
 {
+    const void *state = o.state;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
     if (int rc = pending_handoff_error(device)) return rc;
@@ -457,8 +432,8 @@ int launch(int pass, sdp::Params &p, int device, void *stream, bool exact_state 
     p.tpad = sdp::state_tpad(p.M);
     p.mcap = (p.M + 63) / 64 * 64;
     state_layout(p);
-    p.route = route;
-    if (route == 2) {   // thin pairs only, exact-state build, inside the packed records (see exact_for): one workgroup per pair, batch order
+    p.route = o.route;
+    if (o.route == 2) {   // thin pairs only, exact-state build, inside the packed records (see exact_for): one workgroup per pair, batch order
         p.st2_ps = p.st_ps;
         p.order = nullptr;
         state = nullptr;
@@ -482,8 +457,8 @@ int launch(int pass, sdp::Params &p, int device, void *stream, bool exact_state 
     if ((g_dbg.load() & 128) && pass == sdp::PASS_BWD) allow_parts = 0;   // (128: ... in the backward sweep only)
     if ((g_dbg.load() & 256) && pass == sdp::PASS_FWD) allow_parts = 0;   // (256: ... in the forward sweep only)
 #endif
-    const Plan pl = plan(pass, p.B, p.N, p.M, p.lens != nullptr, exact_state, num_cus(device), forced_waves, fused_seed, general_pitch, allow_parts);
-    const Variant v = pl.v;
+    const Plan pl = plan(pass, p.B, p.N, p.M, p.lens != nullptr, o.st, num_cus(device), o.forced_waves, general_pitch, allow_parts);
+    const Build &v = *pl.v;
     const int W = pl.W;
     const size_t lds = pl.lds, off = pl.stage_off;
     p.stage_off = (int)off;
@@ -492,7 +467,7 @@ int launch(int pass, sdp::Params &p, int device, void *stream, bool exact_state 
     if (pl.parts) {
         p.parts = pl.parts;
         p.nparts_max = parts_per_pair(p.N);
-        p.xb = bridge_in_state(state, p.B, p.N, p.M, exact_state);
+        p.xb = bridge_in_state(state, p.B, p.N, p.M, o.st == ST_EXACT);
         p.xb_row = sdp::xb_row_granules(p.M);
         // every granule "not written yet" (tag 0x7f7f7f7f): enqueued on the caller's stream like the launch itself.  A
         // kernel of our own, not hipMemsetAsync: captured into a graph (torch.cuda.graph) the memset node did not take effect
@@ -535,7 +510,7 @@ int launch(int pass, sdp::Params &p, int device, void *stream, bool exact_state 
             e = hipStreamWaitEvent((hipStream_t)stream, last[device], 0);
             if (e != hipSuccess) return fail_hip(e, "hipStreamWaitEvent(previous parts launch)");
         }
-        e = hipLaunchKernel(v.kernel, dim3(grid), dim3(64 * W), args, lds, (hipStream_t)stream);
+        e = hipLaunchKernel((const void *)v.kernel, dim3(grid), dim3(64 * W), args, lds, (hipStream_t)stream);
         if (e != hipSuccess) return fail_hip(e, "hipLaunchKernel");
         if (track) {
             if (!have[device]) {
@@ -548,38 +523,22 @@ int launch(int pass, sdp::Params &p, int device, void *stream, bool exact_state 
         }
         return 0;
     }
-    e = hipLaunchKernel(v.kernel, dim3(grid), dim3(64 * W), args, lds, (hipStream_t)stream);
+    e = hipLaunchKernel((const void *)v.kernel, dim3(grid), dim3(64 * W), args, lds, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "hipLaunchKernel");
     return 0;
 }
 
-// The value-only forward sweep: the forward sweep's launch without a state -- no parts, no routing of thin pairs (the state
-// format is all that routing is about), the launch order of a long variable-length batch in the caller's workspace.
-int launch_value(sdp::Params &p, int device, void *stream, int forced_waves)
+// The forward or the backward sweep on a state: one launch, or two where thin long pairs are routed to the exact-state build (exact_for)
+int launch_on_state(int pass, sdp::Params &p, int device, void *stream, bool exact, int forced_waves, const void *state)
 {
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-    if (int rc = pending_handoff_error(device)) return rc;
-    p.nstrips_max = sdp::state_nstrips(p.N);
-    p.tpad = sdp::state_tpad(p.M);
-    p.mcap = (p.M + 63) / 64 * 64;
-    state_layout(p);   // (never used: no state is addressed)
-    p.status = status_words(device);
-#ifdef SDP_EXPERIMENTS
-    p.dbg = g_dbg.load();
-    p.trace = g_trace.load();
-#else
-    p.dbg = 0;
-#endif
-    auto misaligned = [](const void *ptr) { return ptr != nullptr && ((uintptr_t)ptr & 127u) != 0; };
-    const bool general_pitch = (p.M & 31) != 0 || misaligned(p.sin0) || misaligned(p.sin1);
-    const Plan pl = plan_value(p.B, p.N, p.M, p.lens != nullptr, num_cus(device), forced_waves, general_pitch);
-    p.stage_off = (int)pl.stage_off;
-    if (int rc = raise_lds_limit(pl.v, device)) return rc;
-    void *args[] = {&p};
-    e = hipLaunchKernel(pl.v.kernel, dim3((unsigned)p.B), dim3(64 * pl.W), args, pl.lds, (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(e, "hipLaunchKernel");
-    return 0;
+    LaunchOpts o;
+    o.st = exact ? ST_EXACT : ST_PACKED, o.forced_waves = forced_waves, o.state = state;
+    if (!routes_thin(exact, p.N, p.M, p.lens)) return launch(pass, p, device, stream, o);
+    o.route = 1;
+    if (int rc = launch(pass, p, device, stream, o)) return rc;
+    LaunchOpts thin;
+    thin.st = ST_EXACT, thin.route = 2;
+    return launch(pass, p, device, stream, thin);
 }
 
 // dynamic-LDS limits of the scores kernels, once per (thread, device): sticky attributes, set before any launch that
@@ -662,36 +621,35 @@ size_t sdp_state_d_bytes_v(int B, int N, int M, int variant)
 int sdp_plan(int pass, int B, int N, int M, int has_lens, int exact_state, int cus, int *kernel_id, int *chunk,
              int *waves, size_t *lds)
 {
-    const bool fused_seed = (pass & SDP_PLAN_FUSED_SEED) != 0;
-    pass &= ~SDP_PLAN_FUSED_SEED;
-    if (pass == sdp::PLAN_VALUE && !fused_seed) {   // the value-only forward sweep (sdp_forward_value_f32); exact_state does not apply
-        if (int rc = check_shape(B, N, M, SDP_NW)) return rc;
-        if (cus <= 0) return fail(SDP_E_SHAPE, "sdp_plan: cus must be positive");
-        const Plan pl = plan_value(B, N, M, has_lens != 0, cus, 0);
-        if (kernel_id) *kernel_id = pl.v.id;
-        if (chunk) *chunk = pl.v.K;
-        if (waves) *waves = pl.W;
-        if (lds) *lds = pl.lds;
-        return 0;
-    }
-    if (pass < 0 || pass > 3) return fail(SDP_E_VARIANT, "sdp_plan: pass must be 0..3, or 4 for the value-only forward sweep");
+    const bool fused_seed = (pass & SDP_PLAN_FUSED_SEED) != 0, general_pitch = (pass & SDP_PLAN_GENERAL_PITCH) != 0;
+    pass &= ~(SDP_PLAN_FUSED_SEED | SDP_PLAN_GENERAL_PITCH);
+    if (pass < 0 || pass > sdp::PLAN_VALUE) return fail(SDP_E_VARIANT, "sdp_plan: pass must be 0..3, or 4 for the value-only forward sweep");
     if (fused_seed && pass != sdp::PASS_AFWD) return fail(SDP_E_VARIANT, "sdp_plan: SDP_PLAN_FUSED_SEED needs pass 2 (adjoint forward)");
     if (int rc = check_shape(B, N, M, SDP_NW)) return rc;
     if (cus <= 0) return fail(SDP_E_SHAPE, "sdp_plan: cus must be positive");
     const bool exact = (pass == sdp::PASS_FWD || pass == sdp::PASS_BWD) ? exact_for(exact_state != 0, N, M) : exact_state != 0;
-    const Plan pl = plan(pass, B, N, M, has_lens != 0, exact, cus, 0, fused_seed);
-    if (kernel_id) *kernel_id = pl.v.id;
-    if (chunk) *chunk = pl.v.K;
+    // (the value-only forward sweep, sdp_forward_value_f32, is the forward sweep with no state; exact_state does not apply to it)
+    const StateKind st = pass == sdp::PLAN_VALUE ? ST_VALUE : fused_seed ? ST_SEED : exact ? ST_EXACT : ST_PACKED;
+    const Plan pl = plan(pass == sdp::PLAN_VALUE ? sdp::PASS_FWD : pass, B, N, M, has_lens != 0, st, cus, 0, general_pitch);
+    if (kernel_id) *kernel_id = pl.v->id;
+    if (chunk) *chunk = pl.v->K;
     if (waves) *waves = pl.W;
     if (lds) *lds = pl.lds;
     return 0;
+}
+
+const char *sdp_kernel_name(int kernel_id)
+{
+    for (const Build &b : BUILDS)
+        if (b.id == kernel_id) return b.name;
+    return nullptr;
 }
 
 int sdp_plan_parts(int pass, int B, int N, int M, int has_lens, int exact_state, int cus)
 {
     if (pass < 0 || pass > 3 || check_shape(B, N, M, SDP_NW) || cus <= 0) return 0;
     const bool exact = (pass == sdp::PASS_FWD || pass == sdp::PASS_BWD) ? exact_for(exact_state != 0, N, M) : exact_state != 0;
-    return plan(pass, B, N, M, has_lens != 0, exact, cus, 0).parts;
+    return plan(pass, B, N, M, has_lens != 0, exact ? ST_EXACT : ST_PACKED, cus, 0).parts;
 }
 
 int sdp_init(int device)
@@ -699,11 +657,8 @@ int sdp_init(int device)
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
     if (device >= 0 && device < MAX_DEV && !status_words(device)) return fail(SDP_E_SELFTEST, "sdp_init: could not create the host-pinned status words");
-    for (int id = 0; id <= 45; ++id) {   // (21-28: the parts instantiations, 36: the pipelined backward twin, 37-40: the cleaning forward twins, 41-45: the value-only forward builds)
-        const Variant v = variant(id);
-        if (v.id != id) continue;   // ids without a build of their own map to the default
-        if (int rc = raise_lds_limit(v, device)) return rc;
-    }
+    for (const Build &b : BUILDS)
+        if (int rc = raise_lds_limit(b, device)) return rc;
     return raise_scores_limits(device);
 }
 
@@ -761,9 +716,7 @@ int sdp_forward_f32(const float *theta, const float *A, float *state, float *Vt,
         if (e != hipSuccess) return fail_hip(e, "sdp_order_kernel");
         if (B > num_cus(device)) p.order = order;   // (with parts the launch takes it from the state by itself)
     }
-    if (!routes_thin(exact, N, M, lens)) return launch(sdp::PASS_FWD, p, device, stream, exact, vb.waves, false, state);
-    if (int rc = launch(sdp::PASS_FWD, p, device, stream, false, vb.waves, false, state, 1)) return rc;
-    return launch(sdp::PASS_FWD, p, device, stream, true, 0, false, nullptr, 2);
+    return launch_on_state(sdp::PASS_FWD, p, device, stream, exact, vb.waves, state);
 }
 
 size_t sdp_forward_value_ws_bytes(int B, int N, int M)
@@ -799,7 +752,9 @@ int sdp_forward_value_f32(const float *theta, const float *A, float *Vt, void *w
         if (e != hipSuccess) return fail_hip(e, "sdp_order_kernel");
         p.order = order;
     }
-    return launch_value(p, device, stream, vb.waves);
+    LaunchOpts o;
+    o.st = ST_VALUE, o.forced_waves = vb.waves;
+    return launch(sdp::PASS_FWD, p, device, stream, o);
 }
 
 int sdp_backward_f32(const float *Et, const float *state, float *E, int B, int N, int M, const int32_t *lens,
@@ -823,9 +778,7 @@ int sdp_backward_f32(const float *Et, const float *state, float *E, int B, int N
     p.lens = lens;
     p.B = B, p.N = N, p.M = M, p.variant = variant, p.flags = vb.flags;
     if (lens != nullptr && B > num_cus(device)) p.order = order_in_state(state, B, N, M, exact);
-    if (!routes_thin(exact, N, M, lens)) return launch(sdp::PASS_BWD, p, device, stream, exact, vb.waves, false, state);
-    if (int rc = launch(sdp::PASS_BWD, p, device, stream, false, vb.waves, false, state, 1)) return rc;
-    return launch(sdp::PASS_BWD, p, device, stream, true, 0, false, nullptr, 2);
+    return launch_on_state(sdp::PASS_BWD, p, device, stream, exact, vb.waves, state);
 }
 
 size_t sdp_state_pair_stride(int N, int M, int exact_state)
@@ -862,7 +815,9 @@ int sdp_backward_range_f32(const float *Et, const float *state, float *E, int B,
     // state = nullptr: a launch over part of the batch never spreads pairs over several workgroups -- the bridge rows
     // live behind the record of the batch's LAST pair, and located from a sub-range they would fall into the records of
     // the pairs that follow it
-    return launch(sdp::PASS_BWD, p, device, stream, exact, vb.waves, false, nullptr);
+    LaunchOpts o;
+    o.st = exact ? ST_EXACT : ST_PACKED, o.forced_waves = vb.waves;
+    return launch(sdp::PASS_BWD, p, device, stream, o);
 }
 
 int sdp_adjoint_forward_f32(const float *state, const float *Ztheta, const float *ZA, float *Vtd, float *state_d,
@@ -886,7 +841,9 @@ int sdp_adjoint_forward_f32(const float *state, const float *Ztheta, const float
     p.lens = lens;
     p.B = B, p.N = N, p.M = M, p.variant = variant, p.flags = vb.flags;
     if (lens != nullptr && B > num_cus(device)) p.order = order_in_state(state, B, N, M, true);
-    return launch(sdp::PASS_AFWD, p, device, stream, false, vb.waves);
+    LaunchOpts o;
+    o.forced_waves = vb.waves;
+    return launch(sdp::PASS_AFWD, p, device, stream, o);
 }
 
 int sdp_adjoint_forward_loss_f32(const float *state, const float *ref, const float *pred, const float *G, const float *scale,
@@ -912,7 +869,9 @@ int sdp_adjoint_forward_loss_f32(const float *state, const float *ref, const flo
     p.lens = lens;
     p.B = B, p.N = N, p.M = M, p.variant = variant, p.flags = vb.flags;
     if (lens != nullptr && B > num_cus(device)) p.order = order_in_state(state, B, N, M, true);
-    return launch(sdp::PASS_AFWD, p, device, stream, false, vb.waves, true);
+    LaunchOpts o;
+    o.st = ST_SEED, o.forced_waves = vb.waves;
+    return launch(sdp::PASS_AFWD, p, device, stream, o);
 }
 
 int sdp_adjoint_backward_f32(const float *E, const float *state, const float *state_d, float *Ed, int B, int N,
@@ -935,7 +894,9 @@ int sdp_adjoint_backward_f32(const float *E, const float *state, const float *st
     p.lens = lens;
     p.B = B, p.N = N, p.M = M, p.variant = variant, p.flags = vb.flags;
     if (lens != nullptr && B > num_cus(device)) p.order = order_in_state(state, B, N, M, true);
-    return launch(sdp::PASS_ABWD, p, device, stream, false, vb.waves);
+    LaunchOpts o;
+    o.forced_waves = vb.waves;
+    return launch(sdp::PASS_ABWD, p, device, stream, o);
 }
 
 // ---- float64 tensors (sdp.h): the reference-arithmetic kernels of sdp_ref.hip with float64 storage ----

@@ -68,6 +68,12 @@ namespace sdp {
 enum { PASS_FWD = 0, PASS_BWD = 1, PASS_AFWD = 2, PASS_ABWD = 3 };
 constexpr int PLAN_VALUE = 4;   // sdp_plan's number for the value-only forward sweep (a forward sweep to the kernels: PASS_FWD)
 
+// what a build of the sweep is, as the rows of sdp_builds.def state it (explained there): the template's boolean arguments by name,
+// and LAT, which is no template argument
+namespace bf {
+enum { QX = 1, LINES = 2, GEN = 4, PARTS = 8, NOPIPE = 16, NOCLEAN = 32, VALUE = 64, LAT = 128 };
+}
+
 constexpr int max_waves(int pass)
 {
     return pass == PASS_FWD ? SDP_MAXW_FWD : (pass == PASS_BWD ? SDP_MAXW_BWD : (pass == PASS_AFWD ? SDP_MAXW_AFWD : SDP_MAXW_ABWD));
@@ -176,42 +182,11 @@ __host__ __device__ inline size_t score_lds_bytes(int rows, int W) { return (siz
 }  // namespace sdp
 
 extern "C" {
-__global__ void sdp_fwd_kernel(const sdp::Params p);
-__global__ void sdp_fwd_lat_kernel(const sdp::Params p);
-__global__ void sdp_fwd_x_kernel(const sdp::Params p);
-__global__ void sdp_fwd_x_tp_kernel(const sdp::Params p);
-__global__ void sdp_fwd_c_kernel(const sdp::Params p);
-__global__ void sdp_fwd_x_tp_c_kernel(const sdp::Params p);
-__global__ void sdp_fwd_lat_c_kernel(const sdp::Params p);
-__global__ void sdp_fwd_x_c_kernel(const sdp::Params p);
-__global__ void sdp_val_kernel(const sdp::Params p);
-__global__ void sdp_val_c_kernel(const sdp::Params p);
-__global__ void sdp_val_g_kernel(const sdp::Params p);
-__global__ void sdp_val_lat_kernel(const sdp::Params p);
-__global__ void sdp_val_lat_c_kernel(const sdp::Params p);
-__global__ void sdp_bwd_kernel(const sdp::Params p);
-__global__ void sdp_bwd_pipe_kernel(const sdp::Params p);
-__global__ void sdp_bwd_lat_kernel(const sdp::Params p);
-__global__ void sdp_bwd_x_kernel(const sdp::Params p);
-__global__ void sdp_bwd_x_lat_kernel(const sdp::Params p);
-__global__ void sdp_adj_fwd_kernel(const sdp::Params p);
-__global__ void sdp_adj_fwd_loss_kernel(const sdp::Params p);
-__global__ void sdp_adj_bwd_kernel(const sdp::Params p);
-__global__ void sdp_fwd_g_kernel(const sdp::Params p);
-__global__ void sdp_fwd_x_tp_g_kernel(const sdp::Params p);
-__global__ void sdp_fwd_p_kernel(const sdp::Params p);
-__global__ void sdp_fwd_x_tp_p_kernel(const sdp::Params p);
-__global__ void sdp_bwd_p_kernel(const sdp::Params p);
-__global__ void sdp_bwd_x_p_kernel(const sdp::Params p);
-__global__ void sdp_fwd_pg_kernel(const sdp::Params p);
-__global__ void sdp_fwd_x_tp_pg_kernel(const sdp::Params p);
-__global__ void sdp_bwd_pg_kernel(const sdp::Params p);
-__global__ void sdp_bwd_x_pg_kernel(const sdp::Params p);
-__global__ void sdp_bwd_g_kernel(const sdp::Params p);
-__global__ void sdp_bwd_lat_g_kernel(const sdp::Params p);
-__global__ void sdp_bwd_x_g_kernel(const sdp::Params p);
-__global__ void sdp_bwd_x_lat_g_kernel(const sdp::Params p);
-__global__ void sdp_adj_bwd_g_kernel(const sdp::Params p);
+// the builds of the sweep: one kernel per row of sdp_builds.def
+#define SDP_IN_GROUP(g) 1
+#define SDP_BUILD(ID, NAME, PASS, K, MAXW, FLAGS) __global__ void NAME(const sdp::Params p);
+#include "sdp_builds.def"
+#undef SDP_IN_GROUP
 __global__ void sdp_ref_fwd_kernel(const float *theta, const float *A, float *Q, float *Vt, const int *lens, int N, int M, int sw);
 __global__ void sdp_ref_bwd_kernel(const float *Et, const float *Q, float *E, const int *lens, int N, int M, int sw, int et_bcast);
 __global__ void sdp_ref_adj_fwd_kernel(const float *Q, const float *Ztheta, const float *ZA, float *Vtd, float *Qd, const int *lens, int N, int M);

@@ -2579,49 +2579,21 @@ __device__ __forceinline__ void sweep(const Params &p)
 }  // namespace sdp
 
 // ----------------------------------------------------------------------------------
-// kernels (one symbol per pass so that rocprofv3 names them)
+// kernels (one symbol per build so that rocprofv3 names them): one per row of sdp_builds.def, which states what each build is
 // ----------------------------------------------------------------------------------
-#define SDP_KERNEL(NAME, PASS, K, MAXW, ...)                                               \
-    extern "C" __global__ void __launch_bounds__((MAXW) * 64) NAME(const sdp::Params p)    \
-    {                                                                                      \
-        sdp::sweep<PASS, K, ##__VA_ARGS__>(p);                                             \
+#define SDP_KERNEL(NAME, PASS, K, MAXW, F, BODY)                                                                                \
+    extern "C" __global__ void __launch_bounds__((MAXW) * 64) NAME(const sdp::Params p)                                        \
+    {                                                                                                                          \
+        using namespace sdp::bf;                                                                                               \
+        if constexpr (BODY)                                                                                                    \
+            sdp::sweep<sdp::PASS, K, ((F) & QX) != 0, ((F) & LINES) != 0, ((F) & GEN) != 0, ((F) & PARTS) != 0, ((F) & NOPIPE) != 0, \
+                       ((F) & NOCLEAN) != 0, ((F) & VALUE) != 0>(p);                                                           \
     }
-
-// (-DSDP_ONLY=<n>: compile ONE kernel, for ISA inspection with `hipcc -S --cuda-device-only` -- tools/isa.sh; never linked)
-#if defined(SDP_ONLY) && SDP_ONLY == 1
-SDP_KERNEL(sdp_bwd_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD_Q, false, false, false, false, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 21
-SDP_KERNEL(sdp_bwd_pipe_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD_Q)
-#elif defined(SDP_ONLY) && SDP_ONLY == 11
-SDP_KERNEL(sdp_bwd_g_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD_Q, false, false, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 18
-SDP_KERNEL(sdp_bwd_x_g_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, true, false, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 15
-SDP_KERNEL(sdp_bwd_lat_g_kernel, sdp::PASS_BWD, SDP_K_BWD_LAT, SDP_MAXW_BWD_LAT, false, false, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 0
-SDP_KERNEL(sdp_fwd_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, false, false, false, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 37
-SDP_KERNEL(sdp_fwd_c_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 6
-SDP_KERNEL(sdp_fwd_lat_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, false, false, false, false, false, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 9
-SDP_KERNEL(sdp_fwd_x_tp_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, true, true, false, false, false, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 7
-SDP_KERNEL(sdp_bwd_x_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 3
-SDP_KERNEL(sdp_adj_bwd_kernel, sdp::PASS_ABWD, SDP_K_ABWD, SDP_MAXW_ABWD)
-#elif defined(SDP_ONLY) && SDP_ONLY == 2
-SDP_KERNEL(sdp_adj_fwd_kernel, sdp::PASS_AFWD, SDP_K_AFWD, SDP_MAXW_AFWD)
-#elif defined(SDP_ONLY) && SDP_ONLY == 41
-SDP_KERNEL(sdp_val_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, false, false, false, true, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 42
-SDP_KERNEL(sdp_val_c_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, false, false, false, false, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 43
-SDP_KERNEL(sdp_val_g_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, true, false, false, false, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 44
-SDP_KERNEL(sdp_val_lat_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, false, false, false, false, false, true, true)
-#elif defined(SDP_ONLY) && SDP_ONLY == 45
-SDP_KERNEL(sdp_val_lat_c_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, false, false, false, false, false, false, true)
+#ifdef SDP_ONLY
+// (-DSDP_ONLY=<id>: the body of the build with that id alone, every other sweep kernel empty, for ISA inspection with
+//  `hipcc -S --cuda-device-only` -- tools/isa.sh; never linked)
+#define SDP_IN_GROUP(g) 1
+#define SDP_BUILD(ID, NAME, PASS, K, MAXW, F) SDP_KERNEL(NAME, PASS, K, MAXW, F, (ID) == (SDP_ONLY))
 #else
 // (-DSDP_GROUP=<g>: compile one group of kernels -- deepblast_amd/build.py builds the groups of this file in parallel and links
 //  them; without it, everything.  Group 0 holds the small kernels at the end of the file.)
@@ -2629,79 +2601,9 @@ SDP_KERNEL(sdp_val_lat_c_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT,
 #define SDP_GROUP (-1)
 #endif
 #define SDP_IN_GROUP(g) (SDP_GROUP < 0 || SDP_GROUP == (g))
-// template arguments after MAXW: QX (exact state / fused loss seed), LINES (throughput forward builds: line-aligned input blocks),
-// GEN (general pitch), PARTS (a pair over several workgroups), NOPIPE (packed backward sweep without the pipelined chunk)
-// (... VALUE, last: the forward sweep without any state output)
-// (... NOCLEAN: the aligned throughput forward builds without the edge cleaning -- full strips, no per-pair lengths; their _c twins carry it)
-#if SDP_IN_GROUP(1)
-SDP_KERNEL(sdp_fwd_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, false, false, false, true)
-SDP_KERNEL(sdp_fwd_lat_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, false, false, false, false, false, true)
-SDP_KERNEL(sdp_fwd_x_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, true, false, false, false, false, true)
-SDP_KERNEL(sdp_fwd_x_tp_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, true, true, false, false, false, true)
+#define SDP_BUILD(ID, NAME, PASS, K, MAXW, F) SDP_KERNEL(NAME, PASS, K, MAXW, F, true)
 #endif
-#if SDP_IN_GROUP(8)
-SDP_KERNEL(sdp_fwd_c_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true)
-SDP_KERNEL(sdp_fwd_x_tp_c_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, true, true)
-SDP_KERNEL(sdp_fwd_lat_c_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT)
-SDP_KERNEL(sdp_fwd_x_c_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, true)
-#endif
-#if SDP_IN_GROUP(2)
-// The packed backward sweep twice: with the chunk as ONE software pipeline (PIPE: deferred flush, stores inside the steps) for
-// long pairs on one wave per SIMD, and without it for everything else -- steady-state A/B, fwd;bwd us, +- 0.3 (tools/steady.py,
-// profiles/r05_steady_pipe.txt; no pipeline -> pipeline): 256 x 1024^2 1064.5 -> 1036.2, 256 x 512 x 1024 665.5 -> 650.7, 256 x 768 x 640
-// 576.1 -> 569.3, 256 x 1024 x 512 602.6 -> 596.6; but 256 x 512^2 272.5 -> 279.0, 64 x 512^2 218.3 -> 224.2, 128 x 512^2 243.3 -> 249.1,
-// 512 x 256^2 163.4 -> 169.6, 128 x 1024^2 (8 waves) 816.3 -> 825.1.  sdp_api.hip plan() picks (bwd_pipe_pays).
-SDP_KERNEL(sdp_bwd_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD_Q, false, false, false, false, true)
-SDP_KERNEL(sdp_bwd_pipe_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD_Q)
-SDP_KERNEL(sdp_bwd_lat_kernel, sdp::PASS_BWD, SDP_K_BWD_LAT, SDP_MAXW_BWD_LAT)
-SDP_KERNEL(sdp_bwd_x_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, true)
-SDP_KERNEL(sdp_bwd_x_lat_kernel, sdp::PASS_BWD, SDP_K_BWD_LAT, SDP_MAXW_BWD_LAT, true)
-#endif
-#if SDP_IN_GROUP(3)
-SDP_KERNEL(sdp_adj_bwd_g_kernel, sdp::PASS_ABWD, SDP_K_ABWD, SDP_MAXW_ABWD, false, false, true)
-SDP_KERNEL(sdp_adj_fwd_kernel, sdp::PASS_AFWD, SDP_K_AFWD, SDP_MAXW_AFWD)
-SDP_KERNEL(sdp_adj_fwd_loss_kernel, sdp::PASS_AFWD, SDP_K_AFWD, 4, true)
-SDP_KERNEL(sdp_adj_bwd_kernel, sdp::PASS_ABWD, SDP_K_ABWD, SDP_MAXW_ABWD)
-#endif
-// PARTS instantiations: the throughput builds with the bridge between workgroups (a pair spread over several CUs)
-#if SDP_IN_GROUP(4)
-SDP_KERNEL(sdp_fwd_p_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, false, true)
-SDP_KERNEL(sdp_fwd_x_tp_p_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, true, true, false, true)
-SDP_KERNEL(sdp_fwd_pg_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, true, true)
-SDP_KERNEL(sdp_fwd_x_tp_pg_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, true, true, true, true)
-#endif
-#if SDP_IN_GROUP(5)
-SDP_KERNEL(sdp_bwd_p_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, false, false, false, true)
-SDP_KERNEL(sdp_bwd_x_p_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, true, false, false, true)
-SDP_KERNEL(sdp_bwd_pg_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, false, false, true, true)
-SDP_KERNEL(sdp_bwd_x_pg_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, true, false, true, true)
-#endif
-// value-only forward builds (VALUE = true: Vt and nothing else, sdp_forward_value_f32): the throughput build without and with the edge
-// cleaning and its general-pitch twin, the latency build without and with the cleaning -- the packed-state forward builds 0 / 37 / 11 / 6 / 39
-#if SDP_IN_GROUP(9)
-SDP_KERNEL(sdp_val_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, false, false, false, true, true)
-SDP_KERNEL(sdp_val_c_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, false, false, false, false, true)
-SDP_KERNEL(sdp_val_g_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, true, false, false, false, true)
-#endif
-#if SDP_IN_GROUP(10)
-SDP_KERNEL(sdp_val_lat_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, false, false, false, false, false, true, true)
-SDP_KERNEL(sdp_val_lat_c_kernel, sdp::PASS_FWD, SDP_K_FWD_LAT, SDP_MAXW_FWD_LAT, false, false, false, false, false, false, true)
-#endif
-// general-pitch instantiations (GEN = true) of the kernels that stage outputs, and of the line-aligned forward builds
-#if SDP_IN_GROUP(6)
-SDP_KERNEL(sdp_fwd_g_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, false, true, true)
-SDP_KERNEL(sdp_fwd_x_tp_g_kernel, sdp::PASS_FWD, SDP_K_FWD, SDP_MAXW_FWD, true, true, true)
-#endif
-#if SDP_IN_GROUP(7)
-SDP_KERNEL(sdp_bwd_g_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD_Q, false, false, true)
-SDP_KERNEL(sdp_bwd_lat_g_kernel, sdp::PASS_BWD, SDP_K_BWD_LAT, SDP_MAXW_BWD_LAT, false, false, true)
-SDP_KERNEL(sdp_bwd_x_g_kernel, sdp::PASS_BWD, SDP_K_BWD, SDP_MAXW_BWD, true, false, true)
-SDP_KERNEL(sdp_bwd_x_lat_g_kernel, sdp::PASS_BWD, SDP_K_BWD_LAT, SDP_MAXW_BWD_LAT, true, false, true)
-#endif
-#endif
-#ifndef SDP_IN_GROUP
-#define SDP_IN_GROUP(g) 1
-#endif
+#include "sdp_builds.def"
 #if SDP_IN_GROUP(0)
 
 // ----------------------------------------------------------------------------------

@@ -396,19 +396,21 @@ int sdp_selftest(int device);
  * reported yet, else 0.  Host-side read, no synchronisation: synchronise the stream first to cover its launches. */
 int sdp_device_status(int device, int32_t info[4]);
 
-/* Diagnostic: what a launch of pass (0 fwd, 1 bwd, 2 adj-fwd, 3 adj-bwd) would use on a device with `cus` compute
- * units -- kernel build (0 fwd throughput, 1 bwd throughput, 2 adj-fwd, 3 adj-bwd, 4 bwd latency, 5 fwd exact
- * state (latency), 6 fwd latency, 7 / 8 bwd reading the exact state (throughput / latency), 9 fwd exact state
- * (throughput)), chunk length, waves per pair,
- * dynamic LDS bytes.  Pure function, needs no device.  (Reported for tensors whose rows and planes start on 128-byte
- * lines -- M a multiple of 32; other launches use the "general pitch" instantiations of the same builds, ids 11-20.
- * Ids 21-28: the throughput builds with the bridge between workgroups, see sdp_plan_parts.)
- * pass 2 | SDP_PLAN_FUSED_SEED: the adjoint forward sweep with the fused loss seed (sdp_adjoint_forward_loss_f32, build
+/* Diagnostic: what a launch of pass (0 fwd, 1 bwd, 2 adj-fwd, 3 adj-bwd, 4 the value-only forward sweep of
+ * sdp_forward_value_f32) would use on a device with `cus` compute units -- kernel build, chunk length, waves per pair, dynamic
+ * LDS bytes.  Pure function, needs no device.  The builds and their ids are the rows of deepblast_amd/csrc/sdp_builds.def, which
+ * states what each one is (sdp_kernel_name gives an id's symbol): 0 / 1 the throughput forward / backward builds, 6 / 4 the
+ * latency ones, 9 / 5 forward writing the exact state (throughput / latency), 7 / 8 backward reading it, 2 / 3 the adjoint pair,
+ * 10 adjoint forward with the fused loss seed, 11-20 general-pitch twins, 21-28 a pair over several workgroups (sdp_plan_parts),
+ * 36 the pipelined packed backward build, 37-40 the forward builds with the edge cleaning (per-pair lengths, N not a multiple of
+ * 64), 41-45 the value-only forward builds.  For pass 4 exact_state is ignored.  Or-ed into `pass`:
+ * SDP_PLAN_FUSED_SEED (pass 2 only): the adjoint forward sweep with the fused loss seed (sdp_adjoint_forward_loss_f32, build
  * 10), which stages three planes instead of two.
- * pass 4: the value-only forward sweep (sdp_forward_value_f32) -- builds 41 throughput, 42 throughput with the edge cleaning
- * (per-pair lengths, N not a multiple of 64), 43 their general-pitch twin, 44 / 45 latency without / with the cleaning;
- * exact_state is ignored. */
+ * SDP_PLAN_GENERAL_PITCH: the answer for a launch whose M is not a multiple of 32 or whose planes do not start on 128-byte
+ * lines -- the "general pitch" twin of the build, where it has one; without the flag, the answer for rows and planes on 128-byte
+ * lines.  (Added after SDP_VERSION 106 without a version change, like sdp_kernel_name: look that symbol up to detect both.) */
 #define SDP_PLAN_FUSED_SEED 0x100
+#define SDP_PLAN_GENERAL_PITCH 0x200
 int sdp_plan(int pass, int B, int N, int M, int has_lens, int exact_state, int cus, int *kernel_id, int *chunk,
              int *waves, size_t *lds);
 
@@ -422,6 +424,9 @@ int sdp_plan(int pass, int B, int N, int M, int has_lens, int exact_state, int c
  * launches wait for the previous one of their kind on the same device, whatever its stream (two of them sharing the chip
  * could starve each other's producers); during stream capture that ordering is the graph's / the caller's. */
 int sdp_plan_parts(int pass, int B, int N, int M, int has_lens, int exact_state, int cus);
+
+/* The symbol of the kernel build with that id (what rocprofv3 shows for its launches), or NULL if no build has the id. */
+const char *sdp_kernel_name(int kernel_id);
 
 #ifdef SDP_EXPERIMENTS
 /* Only in libraries built with -DSDP_EXPERIMENTS (never the shipped one): timing experiments that produce WRONG

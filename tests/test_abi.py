@@ -170,17 +170,15 @@ def test_launch_plan_policy(lib):
     assert _plan(lib, 1, 256, 512, 2048, exact=1)[0] in (7, 8)
 
 
-# sdp_api.hip general_id (and the parts twins, 21-24 -> 25-28): the general-pitch instantiation a launch takes in place of the
-# build sdp_plan reports when M is not a multiple of 32
-GENERAL_PITCH_ID = {0: 11, 37: 11, 1: 12, 3: 14, 4: 15, 7: 18, 8: 19, 9: 20, 38: 20, 21: 25, 22: 26, 23: 27, 24: 28}
+GENERAL_PITCH = 0x200   # include/sdp.h: SDP_PLAN_GENERAL_PITCH -- the build a launch takes when M is not a multiple of 32 or a plane starts off a 128-byte line
 
 
 def _exact_state_builds(lib, B, N, M, lens):
     """{(pass, kernel id, waves)} of the four passes of the training path (exact state) on a 256-CU device"""
     out = set()
     for pass_ in range(4):
-        kid, _, waves, _ = _plan(lib, pass_, B, N, M, lens, exact=1)
-        out.add((pass_, kid if M % 32 == 0 else GENERAL_PITCH_ID.get(kid, kid), waves))
+        kid, _, waves, _ = _plan(lib, pass_ | (GENERAL_PITCH if M % 32 else 0), B, N, M, lens, exact=1)
+        out.add((pass_, kid, waves))
     return out
 
 
@@ -208,12 +206,6 @@ def test_second_order_cases_reach_every_exact_state_build(lib):
     assert {(0, 5, 8), (0, 40, 5), (1, 19, 8), (2, 2, 8), (3, 14, 4), (0, 22, 4), (0, 26, 4), (1, 24, 4), (1, 28, 4), (0, 20, 2)} <= reachable
 
 
-# The general-pitch build a packed-state launch takes in place of the one sdp_plan reports (sdp_api.hip: plan): general_id, the parts
-# twins 21 / 23 -> 25 / 27 -- and the pipelined backward build 36, which plan only picks in place of build 1, so a general-pitch
-# launch that sdp_plan reports as 36 runs build 12
-PACKED_GENERAL_PITCH_ID = {0: 11, 37: 11, 1: 12, 36: 12, 4: 15, 21: 25, 23: 27}
-
-
 def _packed_state_builds(lib, B, N, M, lens, offset=0):
     """{(pass, kernel id, waves)} of the forward and backward sweeps on the packed state (256 CUs), or the empty set where the
     padded shape takes the exact state as a whole (sdp_api.hip: exact_for -- sdp_state_bytes then sizes the float2 state).  A
@@ -223,8 +215,8 @@ def _packed_state_builds(lib, B, N, M, lens, offset=0):
         return set()
     out = set()
     for pass_ in (0, 1):
-        kid, _, waves, _ = _plan(lib, pass_, B, N, M, lens)
-        out.add((pass_, PACKED_GENERAL_PITCH_ID.get(kid, kid) if (M % 32 or offset % 32) else kid, waves))
+        kid, _, waves, _ = _plan(lib, pass_ | (GENERAL_PITCH if (M % 32 or offset % 32) else 0), B, N, M, lens)
+        out.add((pass_, kid, waves))
     return out
 
 
@@ -273,27 +265,62 @@ def test_first_order_cases_reach_every_packed_state_build(lib):
     assert _packed_state_builds(lib, 3, 2049, 2048, 0) == set() and _packed_state_builds(lib, 3, 40, 1024, 1) == set()
 
 
-def _variant_table():
-    """{kernel id: symbol} of the `case N: return {(const void *)SYMBOL, K, maxw, N};` lines of variant() in csrc/sdp_api.hip (and of
-    its `default:` line, which is build 4: the id is the last field of the Variant)"""
-    src = open(os.path.join(ROOT, "deepblast_amd", "csrc", "sdp_api.hip")).read()
-    body = re.search(r"\nVariant variant\(int id\)\n\{(.*?)\n\}\n", src, flags=re.S)
-    assert body, "variant() not found in sdp_api.hip"
-    table = {}
-    for label, sym, kid in re.findall(r"(case\s+\d+|default):\s*return\s*\{\s*\(const void \*\)\s*(\w+)\s*,[^{}]*?(\d+)\s*\};", body.group(1)):
-        assert label == "default" or int(label.split()[1]) == int(kid), (label, sym, kid)
-        assert int(kid) not in table, kid
-        table[int(kid)] = sym
-    assert len(table) == body.group(1).count("return {") and {0, 4, 36, 40} <= set(table), table
-    return table
+# The one hand-written copy of the relation between a build and its general-pitch twin (deepblast_amd/csrc/sdp_builds.def states the
+# builds, sdp_api.hip: plan / settle pick): a general-pitch build always cleans, so 0 and 37 share 11; the pipelined backward build
+# has no twin of its own; the latency forward builds, the adjoint forward builds and the value sweep's latency builds keep the
+# column-aligned geometry at any pitch and map to themselves.
+GENERAL_PITCH_TWIN = {0: 11, 37: 11, 1: 12, 36: 12, 3: 14, 4: 15, 7: 18, 8: 19, 9: 20, 38: 20, 21: 25, 22: 26, 23: 27, 24: 28, 41: 43, 42: 43}
 
 
-def test_kernel_names_are_the_builds_the_library_launches(monkeypatch):
-    """bench.py's per-kernel timers label a launch with Engine.KERNEL_NAMES[sdp_plan's id]: the table must name exactly the builds
-    of variant() -- no id of a build that is gone, none missing -- or a launch carries another kernel's name (or the default one)."""
-    from deepblast_amd._engine import HipEngine
-    assert HipEngine.KERNEL_NAMES == _variant_table()
+def test_general_pitch_plan_is_the_aligned_plan_with_the_twin_build(lib):
+    """sdp_plan(pass | SDP_PLAN_GENERAL_PITCH) over the grid of test_first_order_cases_reach_every_packed_state_build, packed and
+    exact state, every pass: chunk, waves and LDS are those of sdp_plan(pass) -- twins are compiled for the same chunk length and
+    wave limit -- and the id is the twin's.  Without the flag the answer is pinned by tests/test_value.py against the golden plans."""
+    hdr = open(os.path.join(ROOT, "include", "sdp.h")).read()
+    assert re.search(r"#define\s+SDP_PLAN_GENERAL_PITCH\s+0x200\b", hdr)
+    Bs = [1, 2, 3, 8, 40, 64, 72, 73, 74, 100, 127, 128, 200, 224, 225, 256, 257, 300, 384, 512, 513, 600, 768, 1024]
+    Ns = [1, 2, 31, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 320, 321, 384, 385, 448, 449, 512, 513, 576, 577, 640,
+          768, 769, 1020, 1022, 1023, 1024, 1025, 2048, 4097]
+    Ms = [1, 7, 31, 32, 33, 64, 65, 96, 100, 512, 513, 960, 1020, 1022, 1023, 1024, 1025, 1500, 1536, 2000, 2048]
+    seen = set()
+    for B in Bs:
+        for N in Ns:
+            for M in Ms:
+                for lens in (0, 1):
+                    for pass_, exact in ((0, 0), (0, 1), (1, 0), (1, 1), (2, 1), (2 | 0x100, 1), (3, 1), (4, 0)):
+                        kid, chunk, waves, lds = _plan(lib, pass_, B, N, M, lens, exact)
+                        got = _plan(lib, pass_ | GENERAL_PITCH, B, N, M, lens, exact)
+                        assert got == (GENERAL_PITCH_TWIN.get(kid, kid), chunk, waves, lds), (pass_, B, N, M, lens, exact, kid, got)
+                        seen.add(kid)
+    assert set(GENERAL_PITCH_TWIN) - {4} <= seen, sorted(set(GENERAL_PITCH_TWIN) - seen)   # (4: not reachable by the policy since round 5)
+    assert lib.sdp_plan_parts(0 | GENERAL_PITCH, 256, 1022, 1020, 1, 0, 256) == 0   # (the flag is sdp_plan's)
+
+
+def _table_rows():
+    """[(id, symbol)] of the SDP_BUILD(id, symbol, ...) rows of deepblast_amd/csrc/sdp_builds.def"""
+    src = open(os.path.join(ROOT, "deepblast_amd", "csrc", "sdp_builds.def")).read()
+    return [(int(i), sym) for i, sym in re.findall(r"^SDP_BUILD\((\d+), (\w+),", src, flags=re.M)]
+
+
+def test_kernel_names_are_the_builds_the_library_launches(lib, monkeypatch):
+    """bench.py's per-kernel timers label a launch with sdp_kernel_name(sdp_plan's id): the library must name exactly the builds of
+    its table -- no id of a build that is gone, none missing -- and every name must be a kernel it holds."""
+    rows = _table_rows()
+    ids = [i for i, _ in rows]
+    assert len(rows) >= 36 and len(set(ids)) == len(ids) and {0, 4, 36, 40, 45} <= set(ids), rows
+    for kid in range(-2, 80):
+        name = lib.sdp_kernel_name(kid)
+        assert (name is not None) == (kid in ids), kid
+    for kid, sym in rows:
+        assert lib.sdp_kernel_name(kid) == sym.encode(), (kid, sym)
+        assert hasattr(lib, sym), f"{sym}: no such kernel in the library"   # (a kernel's host handle is an exported data symbol)
+    # every id sdp_plan reports has a name (the grids of the coverage tests see every build but 4 / 15)
+    for pass_ in (0, 1, 2, 2 | 0x100, 3, 4):
+        for flag in (0, GENERAL_PITCH):
+            for (B, N, M, lens, exact) in [(256, 512, 512, 0, 0), (16, 500, 100, 1, 1), (256, 1024, 1024, 1, 0), (16, 1024, 1024, 0, 1), (600, 512, 2048, 1, 0)]:
+                assert lib.sdp_kernel_name(_plan(lib, pass_ | flag, B, N, M, lens, exact)[0]), (pass_, flag, B, N, M)
     # _label asks the library's own launch policy (sdp_plan) on the device's CU count
+    from deepblast_amd._engine import HipEngine
     import torch
 
     class _Props:

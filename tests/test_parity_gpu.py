@@ -263,7 +263,7 @@ def test_where_the_fp32_reference_is_the_noisy_one():
 
 # Second order against the float64 reference on every exact-state build the library launches for the four passes (sdp_plan,
 # exact_state = 1, 256 CUs) at every wave count it gives them, and on the general-pitch twins the launch swaps in where M is not a
-# multiple of 32 (sdp_api.hip: general_id).  tests/test_abi.py::test_second_order_cases_reach_every_exact_state_build checks,
+# multiple of 32 (sdp_plan | SDP_PLAN_GENERAL_PITCH).  tests/test_abi.py::test_second_order_cases_reach_every_exact_state_build checks,
 # without a device, that this list reaches each (pass, build, waves) of a grid of shapes.
 #   (B, N, M, variant, per-pair lengths, theta scale, A scale, A offset, extras: "za" nonzero ZA, "et" non-uniform Et, "inf" forbidden gaps)
 F64_CASES = [

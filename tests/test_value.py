@@ -62,15 +62,14 @@ VALUE_BUILDS = {41: ("sdp_val_kernel", 32, 4), 42: ("sdp_val_c_kernel", 32, 4), 
 
 
 def value_build(lib, B, N, M, lens, offset=0):
-    """(kernel id, waves) a value launch takes on 256 CUs: sdp_plan's answer, with the general-pitch twin of the throughput builds
-    where M is not a multiple of 32 or a plane starts off a 128-byte line (sdp_api.hip: plan_value)"""
-    kid, _, waves, _ = _plan(lib, 4, B, N, M, lens)
-    return (43 if (M % 32 or offset % 32) and kid in (41, 42) else kid), waves
+    """(kernel id, waves) a value launch takes on 256 CUs: sdp_plan's answer, for general pitch (SDP_PLAN_GENERAL_PITCH) where M is
+    not a multiple of 32 or a plane starts off a 128-byte line"""
+    kid, _, waves, _ = _plan(lib, 4 | (0x200 if (M % 32 or offset % 32) else 0), B, N, M, lens)
+    return kid, waves
 
 
 def test_value_plan_names_a_build_and_fits(lib):
-    from test_abi import _variant_table
-    table = _variant_table()
+    table = {kid: lib.sdp_kernel_name(kid).decode() for kid in range(64) if lib.sdp_kernel_name(kid)}
     for kid, (sym, _, _) in VALUE_BUILDS.items():
         assert table[kid] == sym
     for B in GRID_BS:
@@ -93,18 +92,20 @@ def test_value_plan_names_a_build_and_fits(lib):
 
 def test_plan_of_the_four_sweeps_is_the_parent_commits(lib):
     """passes 0-3 (and the fused-seed plan, and sdp_plan_parts) answer what tools/gen_golden_plan.py recorded from the library of
-    the commit before the value sweep was added"""
+    the commit before the value sweep was added; pass 4 what it recorded from the library of the last commit on which the value
+    sweep had a policy function of its own (plan_value), before that was merged into plan()"""
     import importlib.util
     spec = importlib.util.spec_from_file_location("gen_golden_plan", os.path.join(ROOT, "tools", "gen_golden_plan.py"))
     gen = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(gen)
-    with open(os.path.join(ROOT, "tests", "golden", "plan_passes_0_3.json")) as fh:
-        want = json.load(fh)
-    assert (want["Bs"], want["Ns"], want["Ms"], want["cus"]) == (gen.BS, gen.NS, gen.MS, gen.CUS)
-    got = gen.table(lib)
-    assert len(got) == len(want["index"]) > 30000
-    bad = [(i, g, want["rows"][k]) for i, (g, k) in enumerate(zip(got, want["index"])) if g != want["rows"][k]]
-    assert not bad, bad[:5]
+    for path, passes, count in ((gen.OUT, gen.PASSES, 35200), (gen.OUT_VALUE, gen.PASSES_VALUE, 7040)):
+        with open(path) as fh:
+            want = json.load(fh)
+        assert (want["Bs"], want["Ns"], want["Ms"], want["cus"]) == (gen.BS, gen.NS, gen.MS, gen.CUS)
+        got = gen.table(lib, passes)
+        assert len(got) == len(want["index"]) == count
+        bad = [(i, g, want["rows"][k]) for i, (g, k) in enumerate(zip(got, want["index"])) if g != want["rows"][k]]
+        assert not bad, (os.path.basename(path), bad[:5])
 
 
 def test_value_cases_reach_every_value_build(lib):

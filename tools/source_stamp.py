@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Identity of the kernel sources a measurement belongs to: sha256 over deepblast_amd/csrc/* and include/sdp.h, plus
+"""Identity of the kernel sources a measurement belongs to: sha256 over deepblast_amd/csrc/* (sdp_builds.def included) and include/sdp.h, plus
 the launch plan (kernel build ids) of the headline configuration.  bench.py compares it with profiles/traffic.json."""
 import ctypes
 import hashlib
@@ -8,7 +8,7 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = ["deepblast_amd/csrc/sdp_kernels.hip", "deepblast_amd/csrc/sdp_kernels.h", "deepblast_amd/csrc/sdp_api.hip", "deepblast_amd/csrc/sdp_comm.hip",
+FILES = ["deepblast_amd/csrc/sdp_kernels.hip", "deepblast_amd/csrc/sdp_kernels.h", "deepblast_amd/csrc/sdp_builds.def", "deepblast_amd/csrc/sdp_api.hip", "deepblast_amd/csrc/sdp_comm.hip",
          "deepblast_amd/csrc/sdp_ref.hip", "include/sdp.h"]
 
 
@@ -28,14 +28,11 @@ def plan_ids(B=256, N=512, M=512, cus=256):
     sys.path.insert(0, ROOT)
     from deepblast_amd import _lib
     lib = _lib.load()
-    names = {0: "sdp_fwd_kernel", 1: "sdp_bwd_kernel", 2: "sdp_adj_fwd_kernel", 3: "sdp_adj_bwd_kernel", 4: "sdp_bwd_lat_kernel",
-             5: "sdp_fwd_x_kernel", 6: "sdp_fwd_lat_kernel", 7: "sdp_bwd_x_kernel", 8: "sdp_bwd_x_lat_kernel", 9: "sdp_fwd_x_tp_kernel",
-             36: "sdp_bwd_pipe_kernel", 37: "sdp_fwd_c_kernel", 38: "sdp_fwd_x_tp_c_kernel", 39: "sdp_fwd_lat_c_kernel", 40: "sdp_fwd_x_c_kernel"}
     out = {}
     for label, pass_, exact in (("fwd", 0, 0), ("bwd", 1, 0), ("fwd_exact", 0, 1), ("bwd_exact", 1, 1), ("adj_fwd", 2, 0), ("adj_bwd", 3, 0)):
         kid, chunk, waves, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
         lib.sdp_plan(pass_, B, N, M, 0, exact, cus, ctypes.byref(kid), ctypes.byref(chunk), ctypes.byref(waves), ctypes.byref(lds))
-        out[label] = {"kernel": names.get(kid.value, str(kid.value)), "chunk": chunk.value, "waves": waves.value, "lds_bytes": lds.value}
+        out[label] = {"kernel": (lib.sdp_kernel_name(kid.value) or str(kid.value).encode()).decode(), "chunk": chunk.value, "waves": waves.value, "lds_bytes": lds.value}
     return out
 
 

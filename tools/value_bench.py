@@ -98,7 +98,7 @@ def sweeps(doc):
             kid, chunk, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
             eng.lib.sdp_plan(pass_, B_, th.shape[1], th.shape[2], int(ln is not None), 0, torch.cuda.get_device_properties(0).multi_processor_count,
                              ctypes.byref(kid), ctypes.byref(chunk), ctypes.byref(w), None)
-            plan[label] = {"kernel": eng.KERNEL_NAMES.get(kid.value), "chunk": chunk.value, "waves": w.value,
+            plan[label] = {"kernel": (eng.lib.sdp_kernel_name(kid.value) or b"").decode() or None, "chunk": chunk.value, "waves": w.value,
                            "parts": eng.lib.sdp_plan_parts(0, B_, th.shape[1], th.shape[2], int(ln is not None), 0, 256) if pass_ == 0 else 0}
         row = {"A_us": mmm(r["A"]), "B_us": mmm(r["B"]), "B_over_A": mmm(ratios), "A_us_reps": r["A"], "B_us_reps": r["B"],
                "B_faster_in_every_rep": bool(max(ratios) < 1.0), "cells": cells, "max_rel_diff_A_B": err, "plan": plan,
