@@ -25,8 +25,12 @@ from . import _engine
 
 def _validate(theta, A, operator, allow_none_operator):
     # error behaviour of the reference GPU variant (nw_cuda.py:171-175)
-    if operator != 'softmax' and not (allow_none_operator and operator is None):
-        raise NotImplementedError("HIP variant only supports 'softmax' operator")
+    if operator == 'hardmax':
+        # the max-plus sweep (make_hard_functions) is an add-and-compare recurrence held to its fp32 definition bit for bit
+        if theta.dtype != torch.float32 or A.dtype != torch.float32:
+            raise TypeError(f"the 'hardmax' operator takes torch.float32 tensors only; got {theta.dtype} and {A.dtype}")
+    elif operator != 'softmax' and not (allow_none_operator and operator is None):
+        raise NotImplementedError("HIP variant only supports the 'softmax' and 'hardmax' operators")
     # float32 (the reference's GPU classes take nothing else, nw_cuda.py:174-175) or float64 (its CPU classes take what they
     # are given, and its own tests hand them float64: tests/test_nw.py:46-90) -- both tensors alike
     if theta.dtype not in (torch.float32, torch.float64) or A.dtype != theta.dtype:
@@ -119,6 +123,87 @@ def make_functions(variant, prefix, allow_none_operator=False):
     return Function, FunctionBackward
 
 
+def _path_sum(states, counts, Z, only_gaps=False):
+    """Per pair, the sum of Z (B, N, M) over the PATH cells of a hard walk (states (B, cap, 3), counts (B,)); only_gaps: over
+    the path cells whose state is x or y.  The path is the tail of a pair's list (the padding precedes it); the walk leaves
+    the number of path cells in the scratch row cap - 1 (engine.hard_walk)."""
+    B, cap, _ = states.shape
+    st = states.long()
+    k = torch.arange(cap, device=states.device)[None, :]
+    cnt = counts.long()[:, None]
+    on = (k < cnt) & (k >= cnt - st[:, cap - 1, 0][:, None])
+    if only_gaps:
+        on = on & (st[..., 2] != 1)
+    i = st[..., 0].clamp(0, Z.shape[1] - 1)
+    j = st[..., 1].clamp(0, Z.shape[2] - 1)
+    picked = Z[torch.arange(B, device=states.device)[:, None], i, j]
+    return torch.where(on, picked, torch.zeros_like(picked)).sum(dim=1)
+
+
+def make_hard_functions(variant, prefix):
+    """The (Function, FunctionBackward) pair of the 'hardmax' operator for one variant: the shape of the soft pair above,
+
+        Function.forward(theta, A, operator, lens, ymx)          -> Vt            saves (theta, A, pointers)
+        Function.backward(Et)                                    -> (E, A, ...)   via FunctionBackward.apply
+        FunctionBackward.forward(theta, A, Et, P, op, lens, ymx) -> (E, A)        saves the walk (states, counts)
+        FunctionBackward.backward(Ztheta, ZA)                    -> (0, None, Vtd, ...)
+
+    with V[i,j] = theta[i,j] + max(A[i,j] + V[i-1,j], V[i-1,j-1], A[i,j] + V[i,j-1]) (first maximum in the order x, m, y).  E is
+    Et on the one optimal path and +0 elsewhere.  The "gradient" handed back for A is A itself, the soft pair's pass-through
+    convention (nw.py:337-339,355); the TRUE gradient of the hard operator w.r.t. A is Et on the path's x and y cells, and is
+    readable from the states (Decoder.optimal_paths).  The Hessian of a maximum of linear functions is zero: the second-order
+    gradient for theta is all zeros, and Vtd = sum of Ztheta over the path (+ ZA over its x / y cells, when given).
+    ymx: the tensors are a transposed problem (_Decoder._transposed) -- ties are then scanned y, m, x so that the path is the
+    one the untransposed sweep finds."""
+
+    class HardFunctionBackward(torch.autograd.Function):
+
+        @staticmethod
+        def forward(ctx, theta, A, Et, P, operator, lens=None, ymx=False):
+            eng = _engine.get_engine()
+            if Et.device != theta.device:
+                raise ValueError(f"Et is on {Et.device}, expected {theta.device}")
+            E, states, counts = eng.hard_walk(P, tuple(theta.shape), variant, lens, Et=Et.detach(), ymx=ymx)
+            ctx.save_for_backward(states, counts)
+            ctx.set_materialize_grads(False)
+            return E, A
+
+        @staticmethod
+        def backward(ctx, Ztheta, ZA):
+            states, counts = ctx.saved_tensors
+            if Ztheta is None and ZA is None:
+                return None, None, None, None, None, None, None
+            ref = Ztheta if Ztheta is not None else ZA
+            Vtd = torch.zeros(states.shape[0], dtype=ref.dtype, device=ref.device)
+            if Ztheta is not None:
+                Vtd = Vtd + _path_sum(states, counts, Ztheta)
+            if ZA is not None:
+                Vtd = Vtd + _path_sum(states, counts, ZA, only_gaps=True)
+            return torch.zeros_like(ref), None, Vtd, None, None, None, None
+
+    class HardFunction(torch.autograd.Function):
+
+        @staticmethod
+        def forward(ctx, theta, A, operator, lens=None, ymx=False):
+            _validate(theta, A, operator, False)
+            eng = _engine.get_engine()
+            Vt, P = eng.hard_forward(theta.detach(), A.detach(), variant, lens, ymx=ymx)
+            ctx.save_for_backward(theta, A, P)
+            ctx.others = (operator, lens, ymx)
+            return Vt
+
+        @staticmethod
+        def backward(ctx, Et):
+            theta, A, P = ctx.saved_tensors
+            operator, lens, ymx = ctx.others
+            E, A = HardFunctionBackward.apply(theta, A, Et, P, operator, lens, ymx)
+            return E, A, None, None, None
+
+    HardFunction.__name__ = HardFunction.__qualname__ = prefix + "HardFunction"
+    HardFunctionBackward.__name__ = HardFunctionBackward.__qualname__ = prefix + "HardFunctionBackward"
+    return HardFunction, HardFunctionBackward
+
+
 def traceback(grad, rule="cpu"):
     """Greedy arg-max walk over one (N, M) expected-alignment matrix -> [(i, j, state)].
 
@@ -173,6 +258,7 @@ class _Decoder(nn.Module):
     """Common body of NeedlemanWunschDecoder / SmithWatermanDecoder (nw_cuda.py:265-325)."""
 
     _function = None
+    _hard_function = None          # the pair's Function for operator='hardmax' (make_hard_functions)
     _variant = None                # SDP_NW / SDP_SW, for the calls that go to the engine without an autograd Function (score)
     _allow_none_operator = False
 
@@ -201,7 +287,11 @@ class _Decoder(nn.Module):
         `fill` (with lengths): True = the gradient E is zero outside each pair's n_b x m_b block (the contract);
         False = those cells are NOT written and hold whatever the allocator handed out (include/sdp.h: SDP_NO_FILL) --
         for callers that mask by the same lengths (a loss that slices [:x_len, :y_len], `traceback_batch(E, lengths)`):
-        the zero fill of a padded batch moves as many bytes as the sweep itself."""
+        the zero fill of a padded batch moves as many bytes as the sweep itself.
+        operator='hardmax': Vt is the optimal (max-plus) alignment score, its gradient Et on the one optimal path and +0 on
+        every other cell -- always written in full (`fill` is accepted and ignored), exact (`arithmetic` makes no difference)."""
+        if self.operator == 'hardmax':
+            return self._hard_apply(theta, A, lengths)
         tr = self._transposed(theta, A, lengths)
         if tr is not None:
             theta, A, lengths = tr
@@ -228,6 +318,8 @@ class _Decoder(nn.Module):
         eng = _engine.get_engine()
         with torch.no_grad():
             theta, A = theta.detach(), A.detach()
+            if self.operator == 'hardmax':
+                return eng.hard_forward_value(theta, A, self._variant, lengths, ymx=tr is not None)
             if self.arithmetic == "reference":
                 return eng.forward(theta, A, self._variant, lengths, exact_state=_engine.REF)[0]
             return eng.forward_value(theta, A, self._variant, lengths)
@@ -250,7 +342,42 @@ class _Decoder(nn.Module):
             lengths = torch.stack([lengths[:, 1], lengths[:, 0]], dim=1)
         return theta.transpose(1, 2), A.transpose(1, 2), lengths
 
+    def _hard_apply(self, theta, A, lengths):
+        """operator='hardmax': the transposed route carries the tie-order flag, so that the path does not depend on the way
+        a problem is swept"""
+        tr = self._transposed(theta, A, lengths)
+        if tr is not None:
+            theta, A, lengths = tr
+        return self._hard_function.apply(theta, A, self.operator, lengths, tr is not None)
+
+    def optimal_paths(self, theta, A, lengths=None):
+        """The optimal (hard-max) alignment of every pair under the scores given -> (Vt (B,), states (B, cap, 3) int32, counts
+        (B,) int32), device tensors without an autograd graph: pair b's list is states[b, :counts[b]], rows (i, j, state) from
+        (0, 0) on, in traceback()'s format (the path preceded by its padding).  Available on every decoder whatever its
+        `operator`: it is the max-plus recurrence over theta and A.  No E is allocated: one sweep that stores 2 bits per cell,
+        one walk per pair."""
+        _validate(theta, A, 'hardmax', False)
+        tr = self._transposed(theta, A, lengths)
+        if tr is not None:
+            theta, A, lengths = tr
+        eng = _engine.get_engine()
+        with torch.no_grad():
+            theta, A = theta.detach(), A.detach()
+            Vt, P = eng.hard_forward(theta, A, self._variant, lengths, ymx=tr is not None)
+            _, states, counts = eng.hard_walk(P, tuple(theta.shape), self._variant, lengths, ymx=tr is not None, want_E=False)
+            if tr is not None:
+                states = states[..., [1, 0, 2]].contiguous()
+        return Vt, states, counts
+
+    def optimal_alignments(self, theta, A, lengths=None):
+        """optimal_paths() as traceback_batch() returns its walks: (Vt, list of B lists of (i, j, state))."""
+        Vt, states, counts = self.optimal_paths(theta, A, lengths)
+        states, counts = states.cpu().numpy(), counts.cpu().numpy()
+        return Vt, [[tuple(int(v) for v in row) for row in states[b, :counts[b]]] for b in range(len(counts))]
+
     def _forward_for_decode(self, theta, A, lengths, fill=True):
+        if self.operator == 'hardmax':
+            return self._hard_apply(theta, A, lengths)
         tr = self._transposed(theta, A, lengths)
         if tr is not None:
             theta, A, lengths = tr

@@ -383,6 +383,72 @@ class HipEngine:
         _lib.check(rc, "sdp_traceback_rule_i32")
         return states, counts
 
+    # ---- the hard-max operator (include/sdp.h: sdp_hard_*) -------------------------------
+    def _hard_variant(self, variant, ymx):
+        w = self.force_waves.get("hard", 0)
+        return variant | (_lib.SDP_HARD_TIES_YMX if ymx else 0) | (_lib.SDP_WAVES(w) if w else 0)
+
+    def hard_forward(self, theta, A, variant, lens=None, ymx=False):
+        """-> (Vt (B,), state): the max-plus sweep and its 2-bit pointers (opaque int32 tensor of sdp_hard_state_bytes).
+        ymx: theta and A are a TRANSPOSED problem -- ties are scanned so that the path is the untransposed sweep's."""
+        dev = self._dev(theta)
+        self._check(theta, theta=theta, A=A)
+        theta, A = theta.contiguous(), A.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        nbytes = self.lib.sdp_hard_state_bytes(B, N, M)
+        state = torch.empty(max(nbytes, 4) // 4, dtype=torch.int32, device=theta.device)
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        with torch.cuda.device(dev), self._bracket("sdp_hard_fwd_kernel"):
+            rc = self.lib.sdp_hard_forward_f32(_ptr(theta), _ptr(A), _ptr(state), _ptr(Vt), B, N, M, _ptr(lens),
+                                               self._hard_variant(variant, ymx), dev, self._stream(dev))
+        _lib.check(rc, "sdp_hard_forward_f32")
+        return Vt, state
+
+    def hard_forward_value(self, theta, A, variant, lens=None, ymx=False):
+        """-> Vt (B,) alone: the same sweep with the pointers compiled out (the same bits)."""
+        dev = self._dev(theta)
+        self._check(theta, theta=theta, A=A)
+        theta, A = theta.contiguous(), A.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        with torch.cuda.device(dev), self._bracket("sdp_hard_val_kernel"):
+            rc = self.lib.sdp_hard_forward_value_f32(_ptr(theta), _ptr(A), _ptr(Vt), B, N, M, _ptr(lens),
+                                                     self._hard_variant(variant, ymx), dev, self._stream(dev))
+        _lib.check(rc, "sdp_hard_forward_value_f32")
+        return Vt
+
+    def hard_walk(self, state, shape, variant, lens=None, Et=None, ymx=False, want_E=True, want_states=True, E_out=None,
+                  states_out=None):
+        """The walk along the pointers of hard_forward -> (E (B,N,M) or None, states (B,cap,3) int32 or None, counts (B,) or None).
+        E: Et[b] on pair b's path, +0 on every other cell of its plane (always written in full); states / counts: the path
+        and its padding in traceback()'s format.  E_out / states_out: buffers to write into instead of fresh ones."""
+        dev = self._dev(state)
+        B, N, M = shape
+        lens = self._lens(lens, B, state.device)
+        E = states = counts = None
+        if want_E:
+            if Et is None:
+                raise ValueError("hard_walk: E needs Et")
+            if Et.device != state.device:
+                raise ValueError(f"Et is on {Et.device}, expected {state.device}")
+            Et = Et.detach().to(torch.float32).expand(B).contiguous()
+            E = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if E_out is None else E_out
+            if tuple(E.shape) != (B, N, M) or E.dtype != torch.float32 or not E.is_contiguous() or E.device != state.device:
+                raise ValueError("E_out must be a contiguous float32 (B, N, M) tensor on the state's device")
+        if want_states:
+            cap = self.lib.sdp_traceback_capacity(N, M)
+            states = torch.empty((B, cap, 3), dtype=torch.int32, device=state.device) if states_out is None else states_out
+            if tuple(states.shape) != (B, cap, 3) or states.dtype != torch.int32 or not states.is_contiguous() or states.device != state.device:
+                raise ValueError(f"states_out must be a contiguous int32 ({B}, {cap}, 3) tensor on the state's device")
+            counts = torch.empty(B, dtype=torch.int32, device=state.device)
+        with torch.cuda.device(dev), self._bracket("sdp_hard_walk_kernel"):
+            rc = self.lib.sdp_hard_walk_f32(_ptr(state), _ptr(Et) if want_E else None, _ptr(E), _ptr(states), _ptr(counts), B, N, M,
+                                            _ptr(lens), self._hard_variant(variant, ymx) & ~0xf000, dev, self._stream(dev))
+        _lib.check(rc, "sdp_hard_walk_f32")
+        return E, states, counts
+
     def alignment_targets(self, codes, code_lens, lens, shape, dm, P, G, flags, status):
         """Enqueue sdp_alignment_targets on the current stream (include/sdp.h): codes (B, L) uint8, code_lens (B,) int32,
         lens (B, 2) int32 or None; dm / P fp32, G bool or fp32 (flags), each (B, N, M) or None; status (B,) int32."""

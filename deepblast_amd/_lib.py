@@ -14,6 +14,7 @@ SDP_NW, SDP_SW = 0, 1
 SDP_NO_ZERO_SKIP, SDP_NO_FILL = 0x800, 0x10000   # include/sdp.h: flags of the backward sweeps
 SDP_TARGETS_GAP_MASK, SDP_TARGETS_G_F32 = 0x1, 0x2  # include/sdp.h: flags of sdp_alignment_targets
 SDP_SCORE_NO_GAPS, SDP_SCORE_PRED_WALK = 0x1, 0x2    # include/sdp.h: flags of sdp_alignment_stats
+SDP_HARD_TIES_YMX = 0x20000                          # include/sdp.h: flag of the sdp_hard_* entries (a transposed problem)
 
 _c_f32p = ctypes.c_void_p
 _c_i32p = ctypes.c_void_p
@@ -83,6 +84,13 @@ SIGNATURES = {
     "sdp_alignment_stats": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, ctypes.c_int, ctypes.c_void_p, _c_i32p, ctypes.c_int,
                                            _c_i32p, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32p,
                                            ctypes.c_void_p, _c_i32p, ctypes.c_void_p, _c_i32p, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_hard_state_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "sdp_hard_forward_f32": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_void_p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_hard_forward_value_f32": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32p,
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_hard_walk_f32": (ctypes.c_int, [ctypes.c_void_p, _c_f32p, _c_f32p, _c_i32p, _c_i32p, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "sdp_selftest": (ctypes.c_int, [ctypes.c_int]),
     "sdp_device_status": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
 }

@@ -10,6 +10,7 @@
 #include <atomic>
 #include <mutex>
 
+#include "sdp_hard.h"
 #include "sdp_kernels.h"
 
 namespace {
@@ -1246,6 +1247,82 @@ int sdp_selftest(int device)
         snprintf(g_err, sizeof(g_err), "sdp_selftest: hardware semantics mismatch, mask 0x%x", bad);
         return SDP_E_SELFTEST;
     }
+    return 0;
+}
+
+// ---- the hard-max operator (csrc/sdp_hard.hip) ----
+// `variant` of the three entries: SDP_NW / SDP_SW | SDP_HARD_TIES_YMX | SDP_WAVES(w); anything else is refused
+static int hard_variant(int variant, int B, int N, int M, bool &ymx, int &waves, int &lo)
+{
+    ymx = (variant & SDP_HARD_TIES_YMX) != 0;
+    waves = (variant >> 12) & 0xf;
+    variant &= ~(SDP_HARD_TIES_YMX | (0xf << 12));
+    if (int rc = check_shape(B, N, M, variant)) return rc;
+    lo = variant == SDP_SW ? 2 : 1;
+    return 0;
+}
+
+// waves of a workgroup: one per strip in flight, as many as the boundary rows fit LDS for
+static int hard_waves(int forced, int N, int M)
+{
+    int w = sdp_hard::strips(N) < sdp_hard::MAX_WAVES ? sdp_hard::strips(N) : sdp_hard::MAX_WAVES;
+    if (forced > 0 && forced < w) w = forced;
+    while (w > 1 && sdp_hard::forward_lds_bytes(w, M) > (size_t)sdp_hard::LDS_BUDGET) --w;
+    return w;
+}
+
+size_t sdp_hard_state_bytes(int B, int N, int M)
+{
+    if (B <= 0 || N <= 0 || M <= 0 || M > sdp::MAX_COLS) return 0;
+    return (size_t)B * sdp_hard::strips(N) * sdp_hard::words(M) * sdp_hard::STRIP * 4;
+}
+
+static int hard_forward(const float *theta, const float *A, void *state, float *Vt, int B, int N, int M, const int32_t *lens,
+                        int variant, int device, void *stream, bool pointers)
+{
+    bool ymx;
+    int waves, lo;
+    if (int rc = hard_variant(variant, B, N, M, ymx, waves, lo)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    const int W = hard_waves(waves, N, M);
+    auto kernel = pointers ? (ymx ? sdp_hard_fwd_t_kernel : sdp_hard_fwd_kernel) : (ymx ? sdp_hard_val_t_kernel : sdp_hard_val_kernel);
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(64 * W), sdp_hard::forward_lds_bytes(W, M), (hipStream_t)stream, theta, A,
+                       static_cast<uint32_t *>(state), Vt, lens, N, M, lo, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, pointers ? "sdp_hard_fwd_kernel" : "sdp_hard_val_kernel");
+    return 0;
+}
+
+int sdp_hard_forward_f32(const float *theta, const float *A, void *state, float *Vt, int B, int N, int M, const int32_t *lens,
+                         int variant, int device, void *stream)
+{
+    if (!theta || !A || !state || !Vt) return fail(SDP_E_NULLPTR, "sdp_hard_forward_f32: null pointer");
+    return hard_forward(theta, A, state, Vt, B, N, M, lens, variant, device, stream, true);
+}
+
+int sdp_hard_forward_value_f32(const float *theta, const float *A, float *Vt, int B, int N, int M, const int32_t *lens, int variant,
+                               int device, void *stream)
+{
+    if (!theta || !A || !Vt) return fail(SDP_E_NULLPTR, "sdp_hard_forward_value_f32: null pointer");
+    return hard_forward(theta, A, nullptr, Vt, B, N, M, lens, variant, device, stream, false);
+}
+
+int sdp_hard_walk_f32(const void *state, const float *Et, float *E, int32_t *states, int32_t *counts, int B, int N, int M,
+                      const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!state || (!E && !states) || (E && !Et) || (states && !counts))
+        return fail(SDP_E_NULLPTR, "sdp_hard_walk_f32: null pointer (state; E with Et, or states with counts, or both)");
+    bool ymx;
+    int waves, lo;
+    if (int rc = hard_variant(variant, B, N, M, ymx, waves, lo)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    hipLaunchKernelGGL(sdp_hard_walk_kernel, dim3(B), dim3(64), sdp_hard::walk_lds_bytes(M), (hipStream_t)stream,
+                       static_cast<const uint32_t *>(state), Et, E, states, counts, lens, N, M, lo, sdp_traceback_capacity(N, M),
+                       ymx ? 1 : 0);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "sdp_hard_walk_kernel");
     return 0;
 }
 

@@ -183,6 +183,9 @@ def decode_loss(decoder, loss, theta, A, first, x_len, y_len, G, lengths=None, f
     from ._engine import NW, SW
     from .sw import SmithWatermanDecoder
     variant = SW if isinstance(decoder, SmithWatermanDecoder) else NW
+    if getattr(decoder, "operator", None) == "hardmax":
+        raise NotImplementedError("decode_loss has nothing to train with a 'hardmax' decoder: the gradient of a loss on the hard "
+                                  "alignment matrix with respect to theta is identically zero")
     if getattr(decoder, "arithmetic", "fast") != "fast":
         raise NotImplementedError("decode_loss runs the tuned sweeps only; with arithmetic='reference' use "
                                   "loss(first, decoder.decode(theta, A), x_len, y_len, G)")

@@ -8,8 +8,10 @@ from . import _dp
 from ._engine import NW
 
 NeedlemanWunschFunction, NeedlemanWunschFunctionBackward = _dp.make_functions(NW, "NeedlemanWunsch")
+NeedlemanWunschHardFunction, NeedlemanWunschHardFunctionBackward = _dp.make_hard_functions(NW, "NeedlemanWunsch")
 
 
 class NeedlemanWunschDecoder(_dp._Decoder):
     _function = NeedlemanWunschFunction
+    _hard_function = NeedlemanWunschHardFunction
     _variant = NW

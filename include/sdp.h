@@ -357,6 +357,43 @@ int sdp_alignment_stats(const uint8_t *true_codes, const int32_t *true_lens, int
                         int Lp, const int32_t *offsets, const int32_t *widths, int W, int B, int flags, int32_t *counts,
                         double *stats, int32_t *hits, double *identity, int32_t *status, int device, void *stream);
 
+/* The hard-max operator (csrc/sdp_hard.hip; the reference's operator table names it, deepblast/ops.py, and none of its
+ * classes can run it): the zero-temperature limit of the sweeps above, i.e. the classical Needleman-Wunsch / Smith-Waterman
+ * optimum and its single best path.  Added after SDP_VERSION 106 without a version change: look the symbols up to detect them.
+ * With (n, m) = lens[b] or (N, M), lo = 1 (SDP_NW) or 2 (SDP_SW), V (n+1) x (m+1) zero, 1-based:
+ *     for i in lo..n, j in lo..m:  c = (A[i-1,j-1] + V[i-1,j], V[i-1,j-1], A[i-1,j-1] + V[i,j-1])    states x = 0, m = 1, y = 2
+ *                                  k = the FIRST maximum of c (strict '>'),  P[i,j] = k,  V[i,j] = theta[i-1,j-1] + c[k]
+ *     Vt = V[n,m]  (0 when no cell exists)
+ * Every '+' is one rounded fp32 addition: the results are the bits of that loop.  -inf in A is legal, NaN unspecified.
+ * The path: from (n, m), while i >= lo and j >= lo: record (i-1, j-1, P[i,j]) and step to the predecessor P[i,j] names.
+ *   state    sdp_hard_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: 2 bits per cell, private layout
+ *            (DESIGN.md 3.12); written by sdp_hard_forward_f32, read by sdp_hard_walk_f32 with the same B, N, M, lens, variant.
+ *   variant  SDP_NW / SDP_SW | SDP_HARD_TIES_YMX | SDP_WAVES(w); any other flag is refused (SDP_E_VARIANT).
+ *            SDP_HARD_TIES_YMX: for a problem handed over TRANSPOSED (theta^T, A^T, swapped lens; what callers do when M exceeds
+ *            sdp_max_cols() and N does not): ties are scanned in the order y, m, x of the tensors given -- x, m, y of the
+ *            original -- and the walk names the states and orders the padding as the original problem's walk would, so that
+ *            (j, i, state) of its rows is the original's list and E^T the original's E.
+ * sdp_hard_forward_value_f32: Vt alone, no state (the same sweep with the pointers compiled out; the same bits).
+ * sdp_hard_walk_f32: one wavefront per pair.
+ *   E        (B, N, M) or NULL: the pair's whole plane is written -- Et[b] on the path, +0 everywhere else, always (there is
+ *            no SDP_NO_FILL here).  Needs Et (B,).
+ *   states   (B, sdp_traceback_capacity(N, M), 3) int32 or NULL, counts (B,) int32: the path, start first, preceded by the
+ *            padding sdp_traceback_i32 appends -- from the path's first cell (or from (n-1, m-1) when the path is empty)
+ *            (i-1, j, x) while i > 0, then (i, j-1, y) while j > 0 -- so the list starts at (0, 0); rows past counts[b] are
+ *            scratch, except the last one (no list reaches it), which receives (number of path cells, i and j of the path's
+ *            first cell): the path is the LAST that many rows of the list.  Padding cells are not part of E.  An empty pair
+ *            (n or m < 1) gets counts[b] = 0 and nothing else.
+ * One workgroup per pair, rows unbounded, M <= sdp_max_cols(); errors as for the other sweeps (SDP_E_NULLPTR, SDP_E_SHAPE,
+ * SDP_E_MAXCOLS, SDP_E_VARIANT, SDP_E_TOOBIG). */
+#define SDP_HARD_TIES_YMX 0x20000
+size_t sdp_hard_state_bytes(int B, int N, int M);
+int sdp_hard_forward_f32(const float *theta, const float *A, void *state, float *Vt, int B, int N, int M, const int32_t *lens,
+                         int variant, int device, void *stream);
+int sdp_hard_forward_value_f32(const float *theta, const float *A, float *Vt, int B, int N, int M, const int32_t *lens, int variant,
+                               int device, void *stream);
+int sdp_hard_walk_f32(const void *state, const float *Et, float *E, int32_t *states, int32_t *counts, int B, int N, int M,
+                      const int32_t *lens, int variant, int device, void *stream);
+
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept
  * for callers who are short of memory, not of time; deepblast_amd.losses uses the unfused kernels by default.
