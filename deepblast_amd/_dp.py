@@ -42,17 +42,6 @@ def _validate(theta, A, operator, allow_none_operator):
         raise ValueError(f"theta and A must live on the same device; got {theta.device} and {A.device}")
 
 
-def _same_device(ref, **others):
-    """Raw pointers cross the C ABI: every tensor of a call must be fp32 on the device the kernel runs on."""
-    for name, t in others.items():
-        if t is None:
-            continue
-        if t.device != ref.device:
-            raise ValueError(f"{name} is on {t.device}, expected {ref.device}")
-        if t.dtype != ref.dtype:
-            raise TypeError(f"{name} must be {ref.dtype}, got {t.dtype}")
-
-
 def make_functions(variant, prefix, allow_none_operator=False):
     """Build the (Function, FunctionBackward) pair for one variant."""
 
@@ -92,7 +81,7 @@ def make_functions(variant, prefix, allow_none_operator=False):
                 _, Q = eng.forward(theta.detach(), A.detach(), variant, lens, exact_state=True)
             if Ztheta is None:
                 Ztheta = torch.zeros_like(E)
-            _same_device(E, Ztheta=Ztheta, ZA=ZA)
+            _engine.check_args(E, E.dtype, Ztheta=Ztheta, ZA=ZA)
             ref = exact_state == _engine.REF
             Vtd, Qd = eng.adjoint_forward(Q, Ztheta, ZA, variant, lens, ref=ref)
             Ed = eng.adjoint_backward(E, Q, Qd, variant, lens, ref=ref)
@@ -153,7 +142,7 @@ def make_hard_functions(variant, prefix):
     convention (nw.py:337-339,355); the TRUE gradient of the hard operator w.r.t. A is Et on the path's x and y cells, and is
     readable from the states (Decoder.optimal_paths).  The Hessian of a maximum of linear functions is zero: the second-order
     gradient for theta is all zeros, and Vtd = sum of Ztheta over the path (+ ZA over its x / y cells, when given).
-    ymx: the tensors are a transposed problem (_Decoder._transposed) -- ties are then scanned y, m, x so that the path is the
+    ymx: the tensors are a transposed problem (_Decoder._oriented) -- ties are then scanned y, m, x so that the path is the
     one the untransposed sweep finds."""
 
     class HardFunctionBackward(torch.autograd.Function):
@@ -290,18 +279,25 @@ class _Decoder(nn.Module):
         the zero fill of a padded batch moves as many bytes as the sweep itself.
         operator='hardmax': Vt is the optimal (max-plus) alignment score, its gradient Et on the one optimal path and +0 on
         every other cell -- always written in full (`fill` is accepted and ignored), exact (`arithmetic` makes no difference)."""
+        return self._apply(theta, A, lengths, fill, for_decode=False)
+
+    def _apply(self, theta, A, lengths, fill, for_decode):
+        """The body of forward() and of decode()'s forward.  for_decode: decode() is differentiated again by its callers
+        (training: a loss on the alignment matrix), so the state is saved in the exact form all four sweeps can share;
+        forward() saves the compact one.  Function.apply gets no trailing argument that has its default value."""
+        theta, A, lengths, transposed = self._oriented(theta, A, lengths)
         if self.operator == 'hardmax':
-            return self._hard_apply(theta, A, lengths)
-        tr = self._transposed(theta, A, lengths)
-        if tr is not None:
-            theta, A, lengths = tr
-        if self.arithmetic == "reference":
-            return self._function.apply(theta, A, self.operator, lengths, _engine.REF)
-        if lengths is None:
-            return self._function.apply(theta, A, self.operator)
-        if not fill:
-            return self._function.apply(theta, A, self.operator, lengths, False, True)
-        return self._function.apply(theta, A, self.operator, lengths)
+            # the transposed route carries the tie-order flag, so that the path does not depend on the way a problem is swept
+            return self._hard_function.apply(theta, A, self.operator, lengths, transposed)
+        reference = self.arithmetic == "reference"
+        exact_state = _engine.REF if reference else for_decode
+        if lengths is not None and not fill and (for_decode or not reference):   # (forward() with reference arithmetic always fills)
+            args = (lengths, exact_state, True)
+        elif exact_state:
+            args = (lengths, exact_state)
+        else:
+            args = () if lengths is None else (lengths,)
+        return self._function.apply(theta, A, self.operator, *args)
 
     def score(self, theta, A, lengths=None):
         """theta, A: (B, N, M) on a ROCm device -> Vt (B,), the alignment scores alone -- what the reference's
@@ -312,43 +308,34 @@ class _Decoder(nn.Module):
         forward(); problems wider than the column limit are swept transposed.  arithmetic="reference" decoders run the
         reference-rounding forward and drop its state (that mode has no fast path)."""
         _validate(theta, A, self.operator, type(self)._allow_none_operator)
-        tr = self._transposed(theta, A, lengths)
-        if tr is not None:
-            theta, A, lengths = tr
+        theta, A, lengths, transposed = self._oriented(theta, A, lengths)
         eng = _engine.get_engine()
         with torch.no_grad():
             theta, A = theta.detach(), A.detach()
             if self.operator == 'hardmax':
-                return eng.hard_forward_value(theta, A, self._variant, lengths, ymx=tr is not None)
+                return eng.hard_forward_value(theta, A, self._variant, lengths, ymx=transposed)
             if self.arithmetic == "reference":
                 return eng.forward(theta, A, self._variant, lengths, exact_state=_engine.REF)[0]
             return eng.forward_value(theta, A, self._variant, lengths)
 
     @staticmethod
-    def _transposed(theta, A, lengths):
+    def _oriented(theta, A, lengths):
         """More columns than the sweeps take (the boundary rows of a strip live in LDS: sdp_max_cols() = 2048, the limit of the
         reference's GPU classes, nw_cuda.py:11) but not more rows: the recurrence is symmetric in its two axes -- V[i,j] =
         theta[i,j] + lse(A[i,j] + V[i-1,j], V[i-1,j-1], A[i,j] + V[i,j-1]), one gap score for both directions (nw.py:46-62) --
         so the problem is swept on the TRANSPOSED tensors (N has no limit) and autograd transposes every gradient back: E, the
         pass-through A, the second-order results.  The parity oracle nw.py has no column limit.  -> (theta^T, A^T, lengths
-        with their columns swapped), or None when no transposition is needed (or would not help: both sides too long)."""
+        with their columns swapped, True), or the arguments as they came and False when no transposition is needed (or would
+        not help: both sides too long)."""
         if theta.dim() != 3 or A.shape != theta.shape:
-            return None
+            return theta, A, lengths, False
         cap = _engine.get_engine().max_cols()
         if theta.shape[2] <= cap or theta.shape[1] > cap:
-            return None
+            return theta, A, lengths, False
         if lengths is not None:
             lengths = torch.as_tensor(lengths)
             lengths = torch.stack([lengths[:, 1], lengths[:, 0]], dim=1)
-        return theta.transpose(1, 2), A.transpose(1, 2), lengths
-
-    def _hard_apply(self, theta, A, lengths):
-        """operator='hardmax': the transposed route carries the tie-order flag, so that the path does not depend on the way
-        a problem is swept"""
-        tr = self._transposed(theta, A, lengths)
-        if tr is not None:
-            theta, A, lengths = tr
-        return self._hard_function.apply(theta, A, self.operator, lengths, tr is not None)
+        return theta.transpose(1, 2), A.transpose(1, 2), lengths, True
 
     def optimal_paths(self, theta, A, lengths=None):
         """The optimal (hard-max) alignment of every pair under the scores given -> (Vt (B,), states (B, cap, 3) int32, counts
@@ -357,15 +344,13 @@ class _Decoder(nn.Module):
         `operator`: it is the max-plus recurrence over theta and A.  No E is allocated: one sweep that stores 2 bits per cell,
         one walk per pair."""
         _validate(theta, A, 'hardmax', False)
-        tr = self._transposed(theta, A, lengths)
-        if tr is not None:
-            theta, A, lengths = tr
+        theta, A, lengths, transposed = self._oriented(theta, A, lengths)
         eng = _engine.get_engine()
         with torch.no_grad():
             theta, A = theta.detach(), A.detach()
-            Vt, P = eng.hard_forward(theta, A, self._variant, lengths, ymx=tr is not None)
-            _, states, counts = eng.hard_walk(P, tuple(theta.shape), self._variant, lengths, ymx=tr is not None, want_E=False)
-            if tr is not None:
+            Vt, P = eng.hard_forward(theta, A, self._variant, lengths, ymx=transposed)
+            _, states, counts = eng.hard_walk(P, tuple(theta.shape), self._variant, lengths, ymx=transposed, want_E=False)
+            if transposed:
                 states = states[..., [1, 0, 2]].contiguous()
         return Vt, states, counts
 
@@ -374,19 +359,6 @@ class _Decoder(nn.Module):
         Vt, states, counts = self.optimal_paths(theta, A, lengths)
         states, counts = states.cpu().numpy(), counts.cpu().numpy()
         return Vt, [[tuple(int(v) for v in row) for row in states[b, :counts[b]]] for b in range(len(counts))]
-
-    def _forward_for_decode(self, theta, A, lengths, fill=True):
-        if self.operator == 'hardmax':
-            return self._hard_apply(theta, A, lengths)
-        tr = self._transposed(theta, A, lengths)
-        if tr is not None:
-            theta, A, lengths = tr
-        # decode() is differentiated again by its callers (training: loss on the alignment matrix): save the
-        # state in the exact form all four sweeps can share
-        xs = _engine.REF if self.arithmetic == "reference" else True
-        if lengths is not None and not fill:
-            return self._function.apply(theta, A, self.operator, lengths, xs, True)
-        return self._function.apply(theta, A, self.operator, lengths, xs)
 
     def traceback(self, grad):
         return traceback(grad, self.traceback_rule)
@@ -416,7 +388,7 @@ class _Decoder(nn.Module):
         """Expected alignment matrix dVt/dtheta, differentiable (nw_cuda.py:319-325).  `lengths`, `fill`: see forward()
         (the gradient that flows back through the result, Ed, is always zero outside the blocks)."""
         with torch.enable_grad():
-            nll = self._forward_for_decode(theta, A, lengths, fill)
+            nll = self._apply(theta, A, lengths, fill, for_decode=True)
             v = torch.sum(nll)
             v_grad, _ = torch.autograd.grad(v, (theta, A), create_graph=True)
         return v_grad

@@ -8,8 +8,7 @@ the backward one launch.
 """
 import torch
 
-from . import _lib
-from ._engine import get_engine, _ptr
+from ._engine import get_engine
 
 CROSS_ENTROPY, PATH, ALIGNMENT = 0, 1, 2
 
@@ -25,47 +24,44 @@ def _lens(x_len, y_len, B, device):
     return torch.stack([x, y], dim=1).to(device).contiguous()
 
 
+def _per_pair(first, pred, G, lens, kind):
+    """One launch (sdp_loss_forward_f32: per-pair float64 sums and cell counts over the masked blocks) -> (the B loss terms,
+    scale (B,) float64: d(batch mean)/d(pair b's sum), which both backward kernels multiply into their per-cell factor)."""
+    eng = get_engine()
+    B, N, M = pred.shape
+    acc = torch.empty(B, dtype=torch.float64, device=pred.device)
+    cnt = torch.empty(B, dtype=torch.int32, device=pred.device)
+    eng.call("sdp_loss_forward_f32", "sdp_loss_fwd_kernel", eng.device_of(pred), first, pred, G, lens, acc, cnt, B, N, M, kind)
+    if kind == CROSS_ENTROPY:
+        return -(acc / cnt.to(torch.float64)), -1.0 / (cnt.to(torch.float64) * B)   # -mean(pos + neg), losses.py:44
+    per_pair = torch.sqrt(acc)                                                      # torch.norm of the masked vector
+    sign = 1.0 if kind == PATH else -1.0
+    return per_pair, torch.where(per_pair > 0, sign / (per_pair * B), torch.zeros_like(per_pair))
+
+
 class _MaskedLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, first, pred, G, lens, kind):
-        eng = get_engine()
-        dev = eng._dev(pred)
+        get_engine().device_of(pred)   # (refuses a CPU tensor before anything else)
         if pred.dtype != torch.float32:
             raise TypeError("HIP variant only supports torch.float32 type")
         first = first.detach().to(torch.float32).contiguous()
         G = G.detach().to(torch.float32).contiguous()
         p = pred.detach().contiguous()
-        B, N, M = p.shape
-        acc = torch.empty(B, dtype=torch.float64, device=p.device)
-        cnt = torch.empty(B, dtype=torch.int32, device=p.device)
-        with torch.cuda.device(dev), eng._bracket("sdp_loss_fwd_kernel"):
-            rc = eng.lib.sdp_loss_forward_f32(_ptr(first), _ptr(p), _ptr(G), _ptr(lens), _ptr(acc), _ptr(cnt), B, N, M, kind,
-                                              dev, eng._stream(dev))
-        _lib.check(rc, "sdp_loss_forward_f32")
-        if kind == CROSS_ENTROPY:
-            per_pair = -(acc / cnt.to(torch.float64))          # -mean(pos + neg), losses.py:44
-            scale = (-1.0 / (cnt.to(torch.float64) * B))
-        else:
-            per_pair = torch.sqrt(acc)                           # torch.norm of the masked vector
-            sign = 1.0 if kind == PATH else -1.0
-            scale = torch.where(per_pair > 0, sign / (per_pair * B), torch.zeros_like(per_pair))
+        per_pair, scale = _per_pair(first, p, G, lens, kind)
         ctx.save_for_backward(first, p, G, lens, scale.to(torch.float32))
         ctx.kind = kind
-        return (per_pair.sum() / B).to(torch.float32)
+        return (per_pair.sum() / p.shape[0]).to(torch.float32)
 
     @staticmethod
     def backward(ctx, gout):
         first, p, G, lens, scale = ctx.saved_tensors
         eng = get_engine()
-        dev = eng._dev(p)
         B, N, M = p.shape
         grad = torch.empty_like(p)
         sc = (scale * gout.to(torch.float32)).contiguous()
-        with torch.cuda.device(dev), eng._bracket("sdp_loss_bwd_kernel"):
-            rc = eng.lib.sdp_loss_backward_f32(_ptr(first), _ptr(p), _ptr(G), _ptr(lens), _ptr(sc), _ptr(grad), B, N, M,
-                                               ctx.kind, dev, eng._stream(dev))
-        _lib.check(rc, "sdp_loss_backward_f32")
+        eng.call("sdp_loss_backward_f32", "sdp_loss_bwd_kernel", eng.device_of(p), first, p, G, lens, sc, grad, B, N, M, ctx.kind)
         return None, grad, None, None, None
 
 
@@ -112,7 +108,6 @@ class _DecodeLoss(torch.autograd.Function):
             raise TypeError(f"decode_loss supports torch.float32 tensors only, got {theta.dtype}; with float64 use "
                             "loss(first, decoder.decode(theta, A), x_len, y_len, G)")
         eng = get_engine()
-        dev = eng._dev(theta)
         first = first.detach().to(torch.float32).contiguous()
         G = G.detach().to(torch.float32).contiguous()
         th, a = theta.detach(), A.detach()
@@ -125,19 +120,7 @@ class _DecodeLoss(torch.autograd.Function):
         # and the per-pair scale would read E between the two blocks, so E is zero-filled as decode() fills it.
         lean = (not fill) and lens_dp is not None and lens_dp is lens_loss
         E = eng.backward(ones, Q, (B, N, M), variant, lens_dp, exact_state=True, **({"no_fill": True} if lean else {}))
-        acc = torch.empty(B, dtype=torch.float64, device=th.device)
-        cnt = torch.empty(B, dtype=torch.int32, device=th.device)
-        with torch.cuda.device(dev), eng._bracket("sdp_loss_fwd_kernel"):
-            rc = eng.lib.sdp_loss_forward_f32(_ptr(first), _ptr(E), _ptr(G), _ptr(lens_loss), _ptr(acc), _ptr(cnt), B, N, M, kind,
-                                              dev, eng._stream(dev))
-        _lib.check(rc, "sdp_loss_forward_f32")
-        if kind == CROSS_ENTROPY:
-            per_pair = -(acc / cnt.to(torch.float64))
-            scale = (-1.0 / (cnt.to(torch.float64) * B))
-        else:
-            per_pair = torch.sqrt(acc)
-            sign = 1.0 if kind == PATH else -1.0
-            scale = torch.where(per_pair > 0, sign / (per_pair * B), torch.zeros_like(per_pair))
+        per_pair, scale = _per_pair(first, E, G, lens_loss, kind)
         ctx.save_for_backward(Q, E, first, G, lens_loss, scale.to(torch.float32))
         ctx.others = (kind, variant, lens_dp, lens_dp is lens_loss)   # (saved tensors come back as new objects: remember the identity)
         ctx.mark_non_differentiable(E)
@@ -189,8 +172,8 @@ def decode_loss(decoder, loss, theta, A, first, x_len, y_len, G, lengths=None, f
     if getattr(decoder, "arithmetic", "fast") != "fast":
         raise NotImplementedError("decode_loss runs the tuned sweeps only; with arithmetic='reference' use "
                                   "loss(first, decoder.decode(theta, A), x_len, y_len, G)")
-    if decoder._transposed(theta, A, None) is not None:
-        # more columns than the sweeps take, but not more rows: decode() sweeps the transposed problem (_dp.py: _transposed),
+    if decoder._oriented(theta, A, None)[3]:
+        # more columns than the sweeps take, but not more rows: decode() sweeps the transposed problem (_dp.py: _oriented),
         # and so does this op -- with the loss's operands and both sets of lengths transposed too.  A masked sum over the
         # block is the same sum over its transpose, so the loss value does not change; E is handed back transposed.
         if lengths is not None:

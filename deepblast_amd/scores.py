@@ -17,8 +17,7 @@ fill the chip -- are left to library GEMMs (torch.bmm).
 """
 import torch
 
-from . import _lib
-from ._engine import get_engine, _ptr
+from ._engine import check_args, get_engine
 
 
 class _Scores(torch.autograd.Function):
@@ -26,8 +25,8 @@ class _Scores(torch.autograd.Function):
     @staticmethod
     def forward(ctx, zx, zy, gx, gy):
         eng = get_engine()
-        dev = eng._dev(zx)
-        eng._check(zx, zx=zx, zy=zy, gx=gx, gy=gy)
+        dev = eng.device_of(zx)
+        check_args(zx, torch.float32, zx=zx, zy=zy, gx=gx, gy=gy)
         if zx.dim() != 3 or zy.dim() != 3 or zx.shape[0] != zy.shape[0] or zx.shape[2] != zy.shape[2]:
             raise ValueError(f"zx must be (B,N,D) and zy (B,M,D); got {tuple(zx.shape)} and {tuple(zy.shape)}")
         if gx.shape != zx.shape or gy.shape != zy.shape:
@@ -43,10 +42,8 @@ class _Scores(torch.autograd.Function):
         t256 = -(-N // 256) * -(-M // 256)
         wide = (x6 and 16 * t256 <= 5 * (-(-N // 128) * -(-M // 128))
                 and t256 * 2 * B >= 2 * torch.cuda.get_device_properties(dev).multi_processor_count)   # 256 x 256 tiles (sdp_api.hip)
-        with torch.cuda.device(dev), eng._bracket(("sdp_scores_x6w_kernel" if wide else "sdp_scores_x6_kernel") if x6 else "sdp_scores_kernel"):
-            rc = eng.lib.sdp_scores_f32(_ptr(zx_), _ptr(zy_), _ptr(gx_), _ptr(gy_), _ptr(theta), _ptr(A), B, N, M, D, dev,
-                                        eng._stream(dev))
-        _lib.check(rc, "sdp_scores_f32")
+        eng.call("sdp_scores_f32", ("sdp_scores_x6w_kernel" if wide else "sdp_scores_x6_kernel") if x6 else "sdp_scores_kernel", dev,
+                 zx_, zy_, gx_, gy_, theta, A, B, N, M, D)
         ctx.save_for_backward(zx_, zy_, gx_, gy_, theta, A)
         return theta, A
 
@@ -114,7 +111,6 @@ def _native_backward(zx, zy, gx, gy, theta, A, g_theta, g_A):
     embeddings for D: a zero cotangent column contributes nothing, a zero embedding column neither) and the results sliced;
     views that are not aligned are copied.  Round 5: until then such shapes went to torch.bmm."""
     eng = get_engine()
-    dev = eng._dev(zx)
     B, N, D = zx.shape
     M = zy.shape[1]
     M4, D4 = -(-M // 4) * 4, -(-D // 4) * 4
@@ -127,16 +123,14 @@ def _native_backward(zx, zy, gx, gy, theta, A, g_theta, g_A):
         zx, zy, gx, gy = (_pad_last(t, D4) for t in (zx, zy, gx, gy))
     aligned = lambda t: t if (t is None or (t.is_contiguous() and (t.data_ptr() & 15) == 0)) else t.clone(memory_format=torch.contiguous_format)
     gt, ga, theta, A, zx, zy, gx, gy = (aligned(t) for t in (gt, ga, theta, A, zx, zy, gx, gy))
-    ws = torch.empty(eng.lib.sdp_scores_backward_ws_bytes(B, N, M4) // 4, dtype=torch.float32, device=zx.device)
+    ws = torch.empty(eng.scores_backward_ws_bytes(B, N, M4) // 4, dtype=torch.float32, device=zx.device)
     new = lambda like: torch.empty_like(like)
     dzx, dzy = (new(zx), new(zy)) if gt is not None else (None, None)
     dgx, dgy = (new(gx), new(gy)) if ga is not None else (None, None)
     tensors = (gt, ga, theta, A, zx, zy, gx, gy, ws, dzx, dzy, dgx, dgy)
     if any(t is not None and (t.data_ptr() & 15) for t in tensors):   # (cannot happen with torch's allocator; never a silent wrong launch)
         raise RuntimeError("deepblast_amd.scores: a tensor of the native backward is not 16-byte aligned")
-    with torch.cuda.device(dev), eng._bracket("sdp_scores_bwd"):
-        rc = eng.lib.sdp_scores_backward_f32(*[_ptr(t) for t in tensors], B, N, M4, D4, dev, eng._stream(dev))
-    _lib.check(rc, "sdp_scores_backward_f32")
+    eng.call("sdp_scores_backward_f32", "sdp_scores_bwd", eng.device_of(zx), *tensors, B, N, M4, D4)
     cut = lambda t, rows: None if t is None else (t[:, :rows, :D] if (t.shape[1] != rows or D4 != D) else t)
     return cut(dzx, N), cut(dzy, M), cut(dgx, N), cut(dgy, M)
 

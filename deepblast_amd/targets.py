@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._engine import get_engine, _ptr
+from ._engine import get_engine
 
 # tmstate_f inverted, indexed by the int state (deepblast.constants: x = 0, m = 1, y = 2): x -> '1', m -> ':', y -> '2'
 _CODE_OF_STATE = np.frombuffer(b"1:2", dtype=np.uint8)
