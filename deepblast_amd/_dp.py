@@ -9,7 +9,8 @@ Mirrors the reference's Function pair (deepblast/nw_cuda.py:168-262, nw.py:315-3
 
 and keeps its gradient-flow quirks: the first-order "gradient" returned
 for A is A itself (nw.py:337-339,355); the second-order gradient w.r.t. A is None
-(nw.py:386); Et may be non-uniform.
+(nw.py:386); Et may be non-uniform.  Decoders built with gap_gradient=True replace both quirks by the true gradients
+(_Decoder.__init__): the second output of FunctionBackward is then G = E * (Qx + Qy) and its backward returns Gd for A.
 
 Differences that are part of the design, not of the maths: `Q` is an opaque state tensor
 (library-private layout; 5 bytes per cell -- two 20-bit weights -- on the inference path, float2 when decode() announces
@@ -48,26 +49,33 @@ def make_functions(variant, prefix, allow_none_operator=False):
     class FunctionBackward(torch.autograd.Function):
 
         @staticmethod
-        def forward(ctx, theta, A, Et, Q, operator, lens=None, exact_state=False, no_fill=False):
+        def forward(ctx, theta, A, Et, Q, operator, lens=None, exact_state=False, no_fill=False, gap_gradient=False):
             eng = _engine.get_engine()
             if Et.device != theta.device:
                 raise ValueError(f"Et is on {Et.device}, expected {theta.device}")
             E = eng.backward(Et.detach(), Q, tuple(theta.shape), variant, lens, exact_state=exact_state, **({"no_fill": True} if no_fill else {}))
+            if gap_gradient:
+                # the true gradient for A instead of the pass-through: G = Et . dVt/dA = E * (Qx + Qy), one elementwise pass
+                second = eng.gap_gradient(E, Q, tuple(theta.shape), variant, lens, exact_state=exact_state, no_fill=no_fill)
+            else:
+                second = A
             # exact state: the adjoint sweeps can use Q as it is; compact state: they need theta and A to get it
             if exact_state:
                 ctx.save_for_backward(Q, E)
             else:
                 ctx.save_for_backward(theta, A, E)
-            ctx.others = (operator, lens, exact_state)
+            ctx.others = (operator, lens, exact_state, gap_gradient)
             # The cotangent of the pass-through A output is all zeros whenever nothing consumes it (the
             # reference materialises it, nw.py:357-383, and feeds the zeros to the adjoint sweep).  Asking
             # autograd not to materialise lets the kernel skip reading a (B,N,M) tensor of zeros.
             ctx.set_materialize_grads(False)
-            return E, A
+            return E, second
 
         @staticmethod
         def backward(ctx, Ztheta, ZA):
-            _, lens, exact_state = ctx.others
+            _, lens, exact_state, gap_gradient = ctx.others
+            if gap_gradient and Ztheta is None and ZA is None:
+                return (None,) * 9
             eng = _engine.get_engine()
             if exact_state:
                 Q, E = ctx.saved_tensors
@@ -83,39 +91,70 @@ def make_functions(variant, prefix, allow_none_operator=False):
                 Ztheta = torch.zeros_like(E)
             _engine.check_args(E, E.dtype, Ztheta=Ztheta, ZA=ZA)
             ref = exact_state == _engine.REF
+            # Smith-Waterman with gap_gradient: the reference's adjoint pair (sw.py:140-161, 199-202) keeps row 1 / column 1 of
+            # the padded table, which its forward and backward loops skip -- a tangent there flows into Vd, and Ed is formed there,
+            # although E and G are identically zero on that border and theta, A of the border reach nothing.  The true
+            # Hessian-vector product is the same pair on tangents that are zero on the border, with Ed zero on the border (Gd is).
+            true_sw = gap_gradient and variant == _engine.SW
+            if true_sw:
+                Ztheta, ZA = _without_border(Ztheta), _without_border(ZA)
             Vtd, Qd = eng.adjoint_forward(Q, Ztheta, ZA, variant, lens, ref=ref)
             Ed = eng.adjoint_backward(E, Q, Qd, variant, lens, ref=ref)
-            return Ed, None, Vtd, None, None, None, None, None
+            if true_sw:
+                Ed[:, 0] = 0
+                Ed[:, :, 0] = 0
+            # gap_gradient: ZA is the cotangent ZG of G, and the gradient of <Ztheta, E> + <ZG, G> with respect to A is
+            # Gd = Ed * (Qx + Qy) + E * (Qdx + Qdy) -- no graph behind it (no third order)
+            Gd = eng.gap_gradient2(E, Ed, Q, Qd, variant, lens, ref=ref) if gap_gradient else None
+            return Ed, Gd, Vtd, None, None, None, None, None, None
 
     class Function(torch.autograd.Function):
 
         @staticmethod
-        def forward(ctx, theta, A, operator, lens=None, exact_state=False, no_fill=False):
+        def forward(ctx, theta, A, operator, lens=None, exact_state=False, no_fill=False, gap_gradient=False):
             _validate(theta, A, operator, allow_none_operator)
             if theta.dtype == torch.float64:
                 exact_state = _engine.F64   # (truthy: the state serves all four sweeps, as with exact_state=True)
             eng = _engine.get_engine()
             Vt, Q = eng.forward(theta.detach(), A.detach(), variant, lens, exact_state=exact_state)
             ctx.save_for_backward(theta, A, Q)
-            ctx.others = (operator, lens, exact_state, no_fill)
+            ctx.others = (operator, lens, exact_state, no_fill, gap_gradient)
             return Vt
 
         @staticmethod
         def backward(ctx, Et):
             theta, A, Q = ctx.saved_tensors
-            operator, lens, exact_state, no_fill = ctx.others
-            E, A = FunctionBackward.apply(theta, A, Et, Q, operator, lens, exact_state, no_fill)
-            return E, A, None, None, None, None
+            operator, lens, exact_state, no_fill, gap_gradient = ctx.others
+            E, A = FunctionBackward.apply(theta, A, Et, Q, operator, lens, exact_state, no_fill, *((True,) if gap_gradient else ()))
+            return E, A, None, None, None, None, None
 
     Function.__name__ = Function.__qualname__ = prefix + "Function"
     FunctionBackward.__name__ = FunctionBackward.__qualname__ = prefix + "FunctionBackward"
     return Function, FunctionBackward
 
 
+def _without_border(Z):
+    """A copy of a (B, N, M) tangent with row 0 and column 0 zeroed (None stays None)."""
+    if Z is None:
+        return None
+    Z = Z.clone(memory_format=torch.contiguous_format)
+    Z[:, 0] = 0
+    Z[:, :, 0] = 0
+    return Z
+
+
 def _path_sum(states, counts, Z, only_gaps=False):
     """Per pair, the sum of Z (B, N, M) over the PATH cells of a hard walk (states (B, cap, 3), counts (B,)); only_gaps: over
     the path cells whose state is x or y.  The path is the tail of a pair's list (the padding precedes it); the walk leaves
     the number of path cells in the scratch row cap - 1 (engine.hard_walk)."""
+    on, b, i, j = _path_cells(states, counts, Z.shape, only_gaps)
+    picked = Z[b, i, j]
+    return torch.where(on, picked, torch.zeros_like(picked)).sum(dim=1)
+
+
+def _path_cells(states, counts, shape, only_gaps):
+    """-> (on (B, cap) bool: the row of `states` is a path cell (only_gaps: one whose state is x or y), and index tensors b, i, j
+    that address it in a (B, N, M) tensor of `shape` (clamped where the row is none)."""
     B, cap, _ = states.shape
     st = states.long()
     k = torch.arange(cap, device=states.device)[None, :]
@@ -123,10 +162,18 @@ def _path_sum(states, counts, Z, only_gaps=False):
     on = (k < cnt) & (k >= cnt - st[:, cap - 1, 0][:, None])
     if only_gaps:
         on = on & (st[..., 2] != 1)
-    i = st[..., 0].clamp(0, Z.shape[1] - 1)
-    j = st[..., 1].clamp(0, Z.shape[2] - 1)
-    picked = Z[torch.arange(B, device=states.device)[:, None], i, j]
-    return torch.where(on, picked, torch.zeros_like(picked)).sum(dim=1)
+    i = st[..., 0].clamp(0, shape[1] - 1)
+    j = st[..., 1].clamp(0, shape[2] - 1)
+    return on, torch.arange(B, device=states.device)[:, None].expand(B, cap), i, j
+
+
+def _path_gaps(states, counts, Et, shape):
+    """The true gradient of the hard operator with respect to A: (B, N, M), Et[b] on the x and y cells of pair b's path, +0 on
+    every other cell (a path visits a cell once: plain indexed assignment)."""
+    on, b, i, j = _path_cells(states, counts, shape, only_gaps=True)
+    G = torch.zeros(shape, dtype=torch.float32, device=states.device)
+    G[b[on], i[on], j[on]] = Et.detach().to(torch.float32).expand(shape[0])[:, None].expand_as(on)[on]
+    return G
 
 
 def make_hard_functions(variant, prefix):
@@ -136,6 +183,9 @@ def make_hard_functions(variant, prefix):
         Function.backward(Et)                                    -> (E, A, ...)   via FunctionBackward.apply
         FunctionBackward.forward(theta, A, Et, P, op, lens, ymx) -> (E, A)        saves the walk (states, counts)
         FunctionBackward.backward(Ztheta, ZA)                    -> (0, None, Vtd, ...)
+
+    (gap_gradient, the last argument of both: the second output of FunctionBackward is the true gradient G instead of A, and
+    the second-order gradient for A is zeros instead of None -- _Decoder.__init__)
 
     with V[i,j] = theta[i,j] + max(A[i,j] + V[i-1,j], V[i-1,j-1], A[i,j] + V[i,j-1]) (first maximum in the order x, m, y).  E is
     Et on the one optimal path and +0 elsewhere.  The "gradient" handed back for A is A itself, the soft pair's pass-through
@@ -148,11 +198,14 @@ def make_hard_functions(variant, prefix):
     class HardFunctionBackward(torch.autograd.Function):
 
         @staticmethod
-        def forward(ctx, theta, A, Et, P, operator, lens=None, ymx=False):
+        def forward(ctx, theta, A, Et, P, operator, lens=None, ymx=False, gap_gradient=False):
             eng = _engine.get_engine()
             if Et.device != theta.device:
                 raise ValueError(f"Et is on {Et.device}, expected {theta.device}")
             E, states, counts = eng.hard_walk(P, tuple(theta.shape), variant, lens, Et=Et.detach(), ymx=ymx)
+            if gap_gradient:
+                A = _path_gaps(states, counts, Et, tuple(theta.shape))
+            ctx.gap_gradient = gap_gradient
             ctx.save_for_backward(states, counts)
             ctx.set_materialize_grads(False)
             return E, A
@@ -161,32 +214,33 @@ def make_hard_functions(variant, prefix):
         def backward(ctx, Ztheta, ZA):
             states, counts = ctx.saved_tensors
             if Ztheta is None and ZA is None:
-                return None, None, None, None, None, None, None
+                return (None,) * 8
             ref = Ztheta if Ztheta is not None else ZA
             Vtd = torch.zeros(states.shape[0], dtype=ref.dtype, device=ref.device)
             if Ztheta is not None:
                 Vtd = Vtd + _path_sum(states, counts, Ztheta)
             if ZA is not None:
                 Vtd = Vtd + _path_sum(states, counts, ZA, only_gaps=True)
-            return torch.zeros_like(ref), None, Vtd, None, None, None, None
+            # (gap_gradient: ZA is the cotangent of G; the second-order gradient for A is zero like theta's)
+            return torch.zeros_like(ref), torch.zeros_like(ref) if ctx.gap_gradient else None, Vtd, None, None, None, None, None
 
     class HardFunction(torch.autograd.Function):
 
         @staticmethod
-        def forward(ctx, theta, A, operator, lens=None, ymx=False):
+        def forward(ctx, theta, A, operator, lens=None, ymx=False, gap_gradient=False):
             _validate(theta, A, operator, False)
             eng = _engine.get_engine()
             Vt, P = eng.hard_forward(theta.detach(), A.detach(), variant, lens, ymx=ymx)
             ctx.save_for_backward(theta, A, P)
-            ctx.others = (operator, lens, ymx)
+            ctx.others = (operator, lens, ymx, gap_gradient)
             return Vt
 
         @staticmethod
         def backward(ctx, Et):
             theta, A, P = ctx.saved_tensors
-            operator, lens, ymx = ctx.others
-            E, A = HardFunctionBackward.apply(theta, A, Et, P, operator, lens, ymx)
-            return E, A, None, None, None
+            operator, lens, ymx, gap_gradient = ctx.others
+            E, A = HardFunctionBackward.apply(theta, A, Et, P, operator, lens, ymx, *((True,) if gap_gradient else ()))
+            return E, A, None, None, None, None
 
     HardFunction.__name__ = HardFunction.__qualname__ = prefix + "HardFunction"
     HardFunctionBackward.__name__ = HardFunctionBackward.__qualname__ = prefix + "HardFunctionBackward"
@@ -251,14 +305,30 @@ class _Decoder(nn.Module):
     _variant = None                # SDP_NW / SDP_SW, for the calls that go to the engine without an autograd Function (score)
     _allow_none_operator = False
 
-    def __init__(self, operator, traceback_rule="cpu", arithmetic="fast"):
+    def __init__(self, operator, traceback_rule="cpu", arithmetic="fast", gap_gradient=False):
         """traceback_rule (extension): "cpu" = the walk of the reference's CPU decoders (nw.py:401-444, the parity
         oracle), "cuda" = the walk of its GPU decoders (nw_cuda.py:273-317), for callers that switch over from those.
         arithmetic (extension): "fast" = the tuned sweeps (fp32 exp-domain forward, float64 products in the second-order
         pair: within 1e-4 of the reference wherever the reference is within 1e-4 of its own float64 run, and closer to
         that float64 run than the reference is); "reference" = the reference's arithmetic rounding for rounding
         (include/sdp.h: SDP_REF_ROUNDING) -- unoptimised, for callers who need nw.py's numbers on long saturated
-        alignments, where nw.py's own fp32 roundings move the second-order results by 1-2e-4."""
+        alignments, where nw.py's own fp32 roundings move the second-order results by 1-2e-4.
+        gap_gradient (extension): False = the reference's conventions for the gap scores A -- backward() leaves A itself in
+        A.grad (nw.py:337-339,355) and the second-order gradient for A is None (nw.py:386).  True = the true gradients, for
+        callers that train the gap model.  With Q[i,j,(x,m,y)] the soft-max weights of a cell, E = Et . dVt/dtheta, and Qd, Ed
+        the adjoint pair's results for a tangent (Ztheta, ZA):
+
+            G  = Et . dVt/dA                                  = E * (Qx + Qy)
+            Gd = d/deps G(theta + eps Ztheta, A + eps ZA)      = Ed * (Qx + Qy) + E * (Qdx + Qdy)
+
+        backward() leaves G in A.grad; differentiating again (decode(), a loss on the alignment matrix) leaves Ed in theta.grad
+        and Gd in A.grad -- the gradient of <Ztheta, E> + <ZG, G>, from the adjoint pair run with ZA = ZG.  Smith-Waterman: the
+        pair runs on tangents zeroed on row 0 / column 0 and Ed is zero there, which makes (Ed, Gd) the true Hessian-vector
+        product; the default decoder keeps the reference's second-order pair, which is not (its adjoint loops keep the border
+        its forward skips), so Ed differs between the two on that border and wherever the border's tangent reaches.  Both are one
+        elementwise pass over the state the sweeps left (include/sdp.h: sdp_gap_gradient*); the sweeps and their results are the
+        same bits either way.  Gd carries no graph (no third order).  operator='hardmax': G is Et on the x and y cells of the one
+        optimal path and +0 elsewhere, and the second-order gradients are zeros."""
         super().__init__()
         if traceback_rule not in ("cpu", "cuda"):
             raise ValueError(f"traceback_rule must be 'cpu' or 'cuda', got {traceback_rule!r}")
@@ -267,6 +337,7 @@ class _Decoder(nn.Module):
         self.operator = operator
         self.traceback_rule = traceback_rule
         self.arithmetic = arithmetic
+        self.gap_gradient = bool(gap_gradient)
 
     def forward(self, theta, A, lengths=None, fill=True):
         """theta, A: (B, N, M) fp32 on a ROCm device -> Vt (B,) on the same device.
@@ -288,10 +359,12 @@ class _Decoder(nn.Module):
         theta, A, lengths, transposed = self._oriented(theta, A, lengths)
         if self.operator == 'hardmax':
             # the transposed route carries the tie-order flag, so that the path does not depend on the way a problem is swept
-            return self._hard_function.apply(theta, A, self.operator, lengths, transposed)
+            return self._hard_function.apply(theta, A, self.operator, lengths, transposed, *((True,) if self.gap_gradient else ()))
         reference = self.arithmetic == "reference"
         exact_state = _engine.REF if reference else for_decode
-        if lengths is not None and not fill and (for_decode or not reference):   # (forward() with reference arithmetic always fills)
+        if self.gap_gradient:
+            args = (lengths, exact_state, lengths is not None and not fill and (for_decode or not reference), True)
+        elif lengths is not None and not fill and (for_decode or not reference):   # (forward() with reference arithmetic always fills)
             args = (lengths, exact_state, True)
         elif exact_state:
             args = (lengths, exact_state)

@@ -326,6 +326,43 @@ class HipEngine:
         self.call(entry, label, dev, E, state, state_d, Ed, B, N, M, lens, v)
         return Ed
 
+    # ---- the true gap-score gradient (include/sdp.h: sdp_gap_gradient*) -----------------------
+    def gap_gradient(self, E, state, shape, variant, lens=None, exact_state=False, no_fill=False):
+        """-> G (B,N,M) = E * (Qx + Qy) = Et . dVt/dA, from the E of backward() and the state it read.  exact_state, lens,
+        no_fill: what backward() was given (no_fill: G outside each pair's block is not written either)."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        dtype = _sweep_dtype(state)
+        check_args(state, dtype, (B, N, M), E=E)
+        E = E.contiguous()
+        lens = self._lens(lens, B, state.device)
+        G = torch.empty((B, N, M), dtype=dtype, device=state.device)
+        if dtype == torch.float64:
+            self.call("sdp_gap_gradient_f64", "sdp_gap_rows_f64_kernel", dev, E, state, G, B, N, M, lens, variant)
+        else:
+            flags = self._state_flags(exact_state) | (_lib.SDP_NO_FILL if (no_fill and lens is not None) else 0)
+            self.call("sdp_gap_gradient_f32", "sdp_gap_rows_kernel" if exact_state == REF else "sdp_gap_kernel", dev,
+                      E, state, G, B, N, M, lens, variant | flags)
+        return G
+
+    def gap_gradient2(self, E, Ed, state, state_d, variant, lens=None, ref=False):
+        """-> Gd (B,N,M) = Ed * (Qx + Qy) + E * (Qdx + Qdy), from the inputs and results of the adjoint pair run with ZA = ZG:
+        the gradient of <Ztheta, E> + <ZG, G> with respect to A.  Zero outside each pair's block.  ref: as for adjoint_forward."""
+        dev = self.device_of(state)
+        dtype = _sweep_dtype(state)
+        B, N, M = E.shape
+        check_args(state, dtype, (B, N, M), E=E, Ed=Ed)
+        check_args(state, dtype, state_d=state_d)
+        E, Ed = E.contiguous(), Ed.contiguous()
+        lens = self._lens(lens, B, state.device)
+        Gd = torch.empty((B, N, M), dtype=dtype, device=state.device)
+        if dtype == torch.float64:
+            self.call("sdp_gap_gradient2_f64", "sdp_gap2_rows_f64_kernel", dev, E, Ed, state, state_d, Gd, B, N, M, lens, variant)
+        else:
+            self.call("sdp_gap_gradient2_f32", "sdp_gap2_rows_kernel" if ref else "sdp_gap2_kernel", dev,
+                      E, Ed, state, state_d, Gd, B, N, M, lens, variant | (REF_ROUNDING if ref else 0))
+        return Gd
+
     def traceback(self, grad, lens=None, rule="cpu"):
         """Batched traceback on the device -> (states (B,cap,3) int32, counts (B,) int32).
 

@@ -91,6 +91,10 @@ SIGNATURES = {
                                                   ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "sdp_hard_walk_f32": (ctypes.c_int, [ctypes.c_void_p, _c_f32p, _c_f32p, _c_i32p, _c_i32p, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_gap_gradient_f32": (ctypes.c_int, [_c_f32p] * 3 + [ctypes.c_int] * 3 + [_c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_gap_gradient2_f32": (ctypes.c_int, [_c_f32p] * 5 + [ctypes.c_int] * 3 + [_c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_gap_gradient_f64": (ctypes.c_int, [_c_f32p] * 3 + [ctypes.c_int] * 3 + [_c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_gap_gradient2_f64": (ctypes.c_int, [_c_f32p] * 5 + [ctypes.c_int] * 3 + [_c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "sdp_selftest": (ctypes.c_int, [ctypes.c_int]),
     "sdp_device_status": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
 }

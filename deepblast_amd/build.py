@@ -15,8 +15,10 @@ KERNELS = os.path.join(HERE, "csrc", "sdp_kernels.hip")
 KERNEL_GROUPS = 11   # SDP_GROUP = 0 .. 10 (sdp_kernels.hip, "SDP_IN_GROUP"; 9 and 10: the value-only forward builds)
 SRC = [KERNELS, os.path.join(HERE, "csrc", "sdp_scores.hip"), os.path.join(HERE, "csrc", "sdp_ref.hip"),
        os.path.join(HERE, "csrc", "sdp_comm.hip"), os.path.join(HERE, "csrc", "sdp_targets.hip"),
-       os.path.join(HERE, "csrc", "sdp_score.hip"), os.path.join(HERE, "csrc", "sdp_hard.hip"), os.path.join(HERE, "csrc", "sdp_api.hip")]
+       os.path.join(HERE, "csrc", "sdp_score.hip"), os.path.join(HERE, "csrc", "sdp_hard.hip"), os.path.join(HERE, "csrc", "sdp_gap.hip"),
+       os.path.join(HERE, "csrc", "sdp_api.hip")]
 HDR = [os.path.join(HERE, "csrc", "sdp_kernels.h"), os.path.join(HERE, "csrc", "sdp_builds.def"), os.path.join(HERE, "csrc", "sdp_hard.h"),
+       os.path.join(HERE, "csrc", "sdp_gap.h"),
        os.path.join(ROOT, "include", "sdp.h")]
 OUT = os.path.join(HERE, "libsdp_hip.so")
 

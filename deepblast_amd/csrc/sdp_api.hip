@@ -10,6 +10,7 @@
 #include <atomic>
 #include <mutex>
 
+#include "sdp_gap.h"
 #include "sdp_hard.h"
 #include "sdp_kernels.h"
 
@@ -643,6 +644,14 @@ const char *sdp_kernel_name(int kernel_id)
 {
     for (const Build &b : BUILDS)
         if (b.id == kernel_id) return b.name;
+    switch (kernel_id) {   // the gap-gradient kernels (csrc/sdp_gap.hip): no builds of the sweep, no rows of the table
+    case sdp_gap::ID_GAP: return "sdp_gap_kernel";
+    case sdp_gap::ID_GAP2: return "sdp_gap2_kernel";
+    case sdp_gap::ID_GAP_ROWS: return "sdp_gap_rows_kernel";
+    case sdp_gap::ID_GAP2_ROWS: return "sdp_gap2_rows_kernel";
+    case sdp_gap::ID_GAP_ROWS_F64: return "sdp_gap_rows_f64_kernel";
+    case sdp_gap::ID_GAP2_ROWS_F64: return "sdp_gap2_rows_f64_kernel";
+    }
     return nullptr;
 }
 
@@ -1324,6 +1333,125 @@ int sdp_hard_walk_f32(const void *state, const float *Et, float *E, int32_t *sta
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "sdp_hard_walk_kernel");
     return 0;
+}
+
+// ---- the gap-score gradient (csrc/sdp_gap.hip): G = E (Qx + Qy), Gd = Ed (Qx + Qy) + E (Qdx + Qdy) ----
+// Elementwise passes over the state the sweeps left: where a pair's records live, and in which form, is decided by the code the
+// sweeps decide it with (state_layout, exact_for, routes_thin).
+static int gap_prepare(int device)
+{
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    return pending_handoff_error(device);
+}
+
+static int gap_launched(const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail_hip(e, what);
+}
+
+// threads of a one-thread-per-cell launch over the padded batch, in workgroups; 0 if the grid would not hold them
+static unsigned gap_rows_grid(int B, int N, int M)
+{
+    const size_t wgs = ((size_t)B * N * M + sdp_gap::THREADS - 1) / sdp_gap::THREADS;
+    return wgs > 0x7fffffffu ? 0u : (unsigned)wgs;
+}
+
+static int gap_tiles(void (*kernel)(const sdp_gap::Params), sdp_gap::Params &g, int TS, bool exact, bool route, void *stream, const char *what)
+{
+    sdp::Params p = {};
+    p.N = g.N, p.M = g.M;
+    p.tpad = sdp::state_tpad(g.M);
+    state_layout(p);
+    g.nstrips_max = sdp::state_nstrips(g.N), g.tpad = p.tpad;
+    g.ps = exact ? p.st2_ps : p.st_ps, g.ps_d = p.st2_ps;
+    g.us_q = p.st_us, g.us_x = p.st2_us;
+    g.whole_exact = exact ? 1 : 0, g.route = route ? 1 : 0;
+    auto unaligned = [](const void *ptr) { return ptr != nullptr && ((uintptr_t)ptr & 15u) != 0; };
+    g.vec4 = ((g.M & 3) == 0 && !unaligned(g.E) && !unaligned(g.Ed) && !unaligned(g.G)) ? 1 : 0;
+    const size_t wgs = (size_t)g.B * g.nstrips_max * sdp_gap::tiles(g.M, TS);
+    if (wgs > 0x7fffffffu) return fail(SDP_E_TOOBIG, "too many tiles for one launch");
+    hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(sdp_gap::THREADS), 0, (hipStream_t)stream, g);
+    return gap_launched(what);
+}
+
+int sdp_gap_gradient_f32(const float *E, const float *state, float *G, int B, int N, int M, const int32_t *lens, int variant, int device,
+                         void *stream)
+{
+    if (!E || !state || !G) return fail(SDP_E_NULLPTR, "sdp_gap_gradient_f32: null pointer");
+    if (variant & ~(SDP_SW | SDP_EXACT_STATE | SDP_REF_ROUNDING | SDP_NO_FILL))
+        return fail(SDP_E_VARIANT, "sdp_gap_gradient_f32: variant is SDP_NW / SDP_SW | SDP_EXACT_STATE | SDP_REF_ROUNDING | SDP_NO_FILL");
+    const VariantBits vb = split_variant(variant);
+    if (int rc = check_shape(B, N, M, vb.variant)) return rc;
+    const int sw = vb.variant == SDP_SW, fill = (vb.flags & 2) ? 0 : 1;
+    if (vb.ref) {
+        const unsigned grid = gap_rows_grid(B, N, M);
+        if (!grid) return fail(SDP_E_TOOBIG, "sdp_gap_gradient_f32: too many cells for one launch");
+        if (int rc = gap_prepare(device)) return rc;
+        hipLaunchKernelGGL(sdp_gap_rows_kernel, dim3(grid), dim3(sdp_gap::THREADS), 0, (hipStream_t)stream, E, state, G, lens, B, N, M, sw, fill);
+        return gap_launched("sdp_gap_rows_kernel");
+    }
+    const bool exact = exact_for(vb.exact, N, M);
+    if (int rc = gap_prepare(device)) return rc;
+    sdp_gap::Params g = {};
+    g.E = E, g.state = state, g.G = G, g.lens = lens;
+    g.B = B, g.N = N, g.M = M, g.sw = sw, g.fill = fill;
+    return gap_tiles(sdp_gap_kernel, g, sdp_gap::TS1, exact, routes_thin(exact, N, M, lens), stream, "sdp_gap_kernel");
+}
+
+int sdp_gap_gradient2_f32(const float *E, const float *Ed, const float *state, const float *state_d, float *Gd, int B, int N, int M,
+                          const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!E || !Ed || !state || !state_d || !Gd) return fail(SDP_E_NULLPTR, "sdp_gap_gradient2_f32: null pointer");
+    if (variant & ~(SDP_SW | SDP_REF_ROUNDING))
+        return fail(SDP_E_VARIANT, "sdp_gap_gradient2_f32: variant is SDP_NW / SDP_SW | SDP_REF_ROUNDING (the state is always the exact one)");
+    const VariantBits vb = split_variant(variant);
+    if (int rc = check_shape(B, N, M, vb.variant)) return rc;
+    const int sw = vb.variant == SDP_SW;
+    if (vb.ref) {
+        const unsigned grid = gap_rows_grid(B, N, M);
+        if (!grid) return fail(SDP_E_TOOBIG, "sdp_gap_gradient2_f32: too many cells for one launch");
+        if (int rc = gap_prepare(device)) return rc;
+        hipLaunchKernelGGL(sdp_gap2_rows_kernel, dim3(grid), dim3(sdp_gap::THREADS), 0, (hipStream_t)stream, E, Ed, state, state_d, Gd, lens, B, N, M, sw);
+        return gap_launched("sdp_gap2_rows_kernel");
+    }
+    if (int rc = gap_prepare(device)) return rc;
+    sdp_gap::Params g = {};
+    g.E = E, g.Ed = Ed, g.state = state, g.state_d = state_d, g.G = Gd, g.lens = lens;
+    g.B = B, g.N = N, g.M = M, g.sw = sw, g.fill = 1;
+    return gap_tiles(sdp_gap2_kernel, g, sdp_gap::TS2, true, false, stream, "sdp_gap2_kernel");
+}
+
+int sdp_gap_gradient_f64(const double *E, const double *state, double *G, int B, int N, int M, const int32_t *lens, int variant,
+                         int device, void *stream)
+{
+    if (!E || !state || !G) return fail(SDP_E_NULLPTR, "sdp_gap_gradient_f64: null pointer");
+    bool bc;
+    const int v = f64_variant(variant, "sdp_gap_gradient_f64", bc);
+    if (v < 0 || bc) return v < 0 ? SDP_E_VARIANT : fail(SDP_E_VARIANT, "sdp_gap_gradient_f64: SDP_ET_BROADCAST belongs to the backward sweep");
+    if (int rc = check_shape(B, N, M, v)) return rc;
+    const unsigned grid = gap_rows_grid(B, N, M);
+    if (!grid) return fail(SDP_E_TOOBIG, "sdp_gap_gradient_f64: too many cells for one launch");
+    if (int rc = gap_prepare(device)) return rc;
+    hipLaunchKernelGGL(sdp_gap_rows_f64_kernel, dim3(grid), dim3(sdp_gap::THREADS), 0, (hipStream_t)stream, E, state, G, lens, B, N, M, v == SDP_SW, 1);
+    return gap_launched("sdp_gap_rows_f64_kernel");
+}
+
+int sdp_gap_gradient2_f64(const double *E, const double *Ed, const double *state, const double *state_d, double *Gd, int B, int N,
+                          int M, const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!E || !Ed || !state || !state_d || !Gd) return fail(SDP_E_NULLPTR, "sdp_gap_gradient2_f64: null pointer");
+    bool bc;
+    const int v = f64_variant(variant, "sdp_gap_gradient2_f64", bc);
+    if (v < 0 || bc) return v < 0 ? SDP_E_VARIANT : fail(SDP_E_VARIANT, "sdp_gap_gradient2_f64: SDP_ET_BROADCAST belongs to the backward sweep");
+    if (int rc = check_shape(B, N, M, v)) return rc;
+    const unsigned grid = gap_rows_grid(B, N, M);
+    if (!grid) return fail(SDP_E_TOOBIG, "sdp_gap_gradient2_f64: too many cells for one launch");
+    if (int rc = gap_prepare(device)) return rc;
+    hipLaunchKernelGGL(sdp_gap2_rows_f64_kernel, dim3(grid), dim3(sdp_gap::THREADS), 0, (hipStream_t)stream, E, Ed, state, state_d, Gd, lens, B, N, M,
+                       v == SDP_SW);
+    return gap_launched("sdp_gap2_rows_f64_kernel");
 }
 
 }  // extern "C"

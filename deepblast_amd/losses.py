@@ -153,7 +153,8 @@ def decode_loss(decoder, loss, theta, A, first, x_len, y_len, G, lengths=None, f
     loss    : MatrixCrossEntropy() / SoftPathLoss() / SoftAlignmentLoss() of this module (its `kind` is used)
     lengths : optional (B,2) per-pair sizes for the DP itself (None = the reference's full padded DP)
     The scalar is differentiable w.r.t. theta (the gradient w.r.t. A is None, as in the reference's second-order
-    path, nw.py:386); E is returned for inspection / traceback and is not differentiable through this op.
+    path, nw.py:386 -- unless the decoder was built with gap_gradient=True: the op is then the unfused composition
+    loss(first, decoder.decode(theta, A, lengths), ...) with E zero-filled, and A gets its true gradient); E is returned for inspection / traceback and is not differentiable through this op.
     fill    : with `lengths` EQUAL to (x_len, y_len) -- the usual case -- False (default) leaves E OUTSIDE each pair's block
               unwritten (uninitialised memory, possibly NaN): nothing in this op reads it (the loss slices by x_len / y_len as
               deepblast/losses.py:30-40 does, the sweeps mask by `lengths`), and `decoder.traceback_batch(E, lengths)` does not
@@ -172,6 +173,10 @@ def decode_loss(decoder, loss, theta, A, first, x_len, y_len, G, lengths=None, f
     if getattr(decoder, "arithmetic", "fast") != "fast":
         raise NotImplementedError("decode_loss runs the tuned sweeps only; with arithmetic='reference' use "
                                   "loss(first, decoder.decode(theta, A), x_len, y_len, G)")
+    if getattr(decoder, "gap_gradient", False):
+        # the fused seed (sdp_adjoint_forward_loss_f32) knows no gradient for A: the unfused composition, through which A gets Gd
+        E = decoder.decode(theta, A, lengths)
+        return loss(first, E, x_len, y_len, G), E.detach()
     if decoder._oriented(theta, A, None)[3]:
         # more columns than the sweeps take, but not more rows: decode() sweeps the transposed problem (_dp.py: _oriented),
         # and so does this op -- with the loss's operands and both sets of lengths transposed too.  A masked sum over the

@@ -407,6 +407,32 @@ int sdp_adjoint_forward_loss_f32(const float *state, const float *ref, const flo
                                  const float *scale, int kind, float *Vtd, float *state_d, int B, int N, int M,
                                  const int32_t *lens, int variant, int device, void *stream);
 
+/* The TRUE gradient of the alignment score with respect to the gap scores A (csrc/sdp_gap.hip).  The sweeps hand A itself back
+ * as A's "gradient" and None at second order -- the reference's conventions (nw.py:337-339,355,386) -- and these entries are the
+ * opt-in alternative (deepblast_amd: Decoder(..., gap_gradient=True)).  With Q[i,j,(x,m,y)] the soft-max weights of a cell, E =
+ * Et . dVt/dtheta (sdp_backward_*) and Qd, Ed the adjoint pair's results for a tangent (Ztheta, ZA):
+ *     G  = Et . dVt/dA                              = E (Qx + Qy)
+ *     Gd = d/deps G(theta + eps Ztheta, A + eps ZA)  = Ed (Qx + Qy) + E (Qdx + Qdy)
+ * and the gradient of <Ztheta, E> + <ZG, G> with respect to (theta, A, Et) is (Ed, Gd, Vtd) of the adjoint pair run with ZA = ZG.
+ * Neither is a sweep: one elementwise pass each over buffers the sweeps left, one launch, any batch size.
+ * sdp_gap_gradient_f32: E (B,N,M) and the `state` of sdp_forward_f32 -> G (B,N,M).  variant: SDP_NW / SDP_SW, or-ed with the
+ * flags the state was WRITTEN under (SDP_EXACT_STATE, SDP_REF_ROUNDING) and SDP_NO_FILL; lens as the sweeps were given them.  G is
+ * +0 on row 0 and column 0 of a Smith-Waterman block, +0 wherever E is +-0, and -- with lens -- +0 outside each pair's n x m block
+ * (SDP_NO_FILL: those cells are not written, as for E).  A forbidden gap (A = -inf) has Qx = Qy = 0: G is exactly 0 there.
+ * sdp_gap_gradient2_f32: E, Ed and the states of sdp_adjoint_forward_f32 / its input -> Gd, always zero outside the blocks.
+ * variant: SDP_NW / SDP_SW, or-ed with SDP_REF_ROUNDING; the state is the exact one, as for the adjoint pair.
+ * The _f64 entries take the (B,N,M,3) float64 states of the sdp_*_f64 sweeps; variant SDP_NW / SDP_SW.
+ * Any other bit of `variant`: SDP_E_VARIANT.  (Added after SDP_VERSION 106 without a version change, like the value sweep and the
+ * hard-max entries: look the symbol up.  sdp_kernel_name answers 100-105 for their kernels.) */
+int sdp_gap_gradient_f32(const float *E, const float *state, float *G, int B, int N, int M, const int32_t *lens, int variant,
+                         int device, void *stream);
+int sdp_gap_gradient2_f32(const float *E, const float *Ed, const float *state, const float *state_d, float *Gd, int B, int N,
+                          int M, const int32_t *lens, int variant, int device, void *stream);
+int sdp_gap_gradient_f64(const double *E, const double *state, double *G, int B, int N, int M, const int32_t *lens, int variant,
+                         int device, void *stream);
+int sdp_gap_gradient2_f64(const double *E, const double *Ed, const double *state, const double *state_d, double *Gd, int B, int N,
+                          int M, const int32_t *lens, int variant, int device, void *stream);
+
 /* Collecting results across the GPUs of a node for callers without torch.distributed.  The sweeps need no
  * collective; these four wrap the one RCCL all-gather (over xGMI) that gathers Vt -- or E -- from all ranks, one
  * process per GPU.  Rank 0 calls sdp_comm_unique_id and distributes the 128 bytes to the other ranks by its own means;
@@ -462,7 +488,8 @@ int sdp_plan(int pass, int B, int N, int M, int has_lens, int exact_state, int c
  * could starve each other's producers); during stream capture that ordering is the graph's / the caller's. */
 int sdp_plan_parts(int pass, int B, int N, int M, int has_lens, int exact_state, int cus);
 
-/* The symbol of the kernel build with that id (what rocprofv3 shows for its launches), or NULL if no build has the id. */
+/* The symbol of the kernel build with that id (what rocprofv3 shows for its launches), or NULL if no build has the id.  (100-105:
+ * the gap-gradient kernels, which are no builds of the sweep.) */
 const char *sdp_kernel_name(int kernel_id);
 
 #ifdef SDP_EXPERIMENTS
