@@ -1,8 +1,8 @@
 """Build libsdp_hip.so for gfx950 with hipcc (in-tree, next to this file).
 
-The sweep kernels (csrc/sdp_kernels.hip) are one template instantiated ~30 times; compiled as ONE translation unit that
-takes two minutes.  The file therefore knows `-DSDP_GROUP=<g>` (one group of its kernels per translation unit), and the
-groups, like the other sources, are compiled to objects in parallel and linked: ~35 s on 8 cores."""
+The sweep kernels (csrc/sdp_kernels.hip) are one template instantiated 36 times (csrc/sdp_builds.def); as ONE translation unit
+they take three to four minutes.  The file therefore knows `-DSDP_GROUP=<g>` (one group of its kernels per translation unit), and
+its ten groups, like the nine other sources, are compiled to objects in parallel and linked: ~40 s on 8 cores."""
 import os
 import subprocess
 import sys
@@ -12,12 +12,12 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 KERNELS = os.path.join(HERE, "csrc", "sdp_kernels.hip")
-KERNEL_GROUPS = 11   # SDP_GROUP = 0 .. 10 (sdp_kernels.hip, "SDP_IN_GROUP"; 9 and 10: the value-only forward builds)
-SRC = [KERNELS, os.path.join(HERE, "csrc", "sdp_scores.hip"), os.path.join(HERE, "csrc", "sdp_ref.hip"),
+KERNEL_GROUPS = range(1, 11)   # SDP_GROUP = 1 .. 10: the sections of sdp_builds.def (9 and 10: the value-only forward builds)
+SRC = [KERNELS, os.path.join(HERE, "csrc", "sdp_aux.hip"), os.path.join(HERE, "csrc", "sdp_scores.hip"), os.path.join(HERE, "csrc", "sdp_ref.hip"),
        os.path.join(HERE, "csrc", "sdp_comm.hip"), os.path.join(HERE, "csrc", "sdp_targets.hip"),
        os.path.join(HERE, "csrc", "sdp_score.hip"), os.path.join(HERE, "csrc", "sdp_hard.hip"), os.path.join(HERE, "csrc", "sdp_gap.hip"),
        os.path.join(HERE, "csrc", "sdp_api.hip")]
-HDR = [os.path.join(HERE, "csrc", "sdp_kernels.h"), os.path.join(HERE, "csrc", "sdp_builds.def"), os.path.join(HERE, "csrc", "sdp_hard.h"),
+HDR = [os.path.join(HERE, "csrc", "sdp_kernels.h"), os.path.join(HERE, "csrc", "sdp_device.h"), os.path.join(HERE, "csrc", "sdp_builds.def"), os.path.join(HERE, "csrc", "sdp_hard.h"),
        os.path.join(HERE, "csrc", "sdp_gap.h"),
        os.path.join(ROOT, "include", "sdp.h")]
 OUT = os.path.join(HERE, "libsdp_hip.so")
@@ -38,8 +38,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 
 
 def compile_and_link(out, extra=(), jobs=None):
-    """Objects in parallel (the kernel file once per group), then one link."""
-    units = [(KERNELS, [f"-DSDP_GROUP={g}"]) for g in range(KERNEL_GROUPS)] + [(s, []) for s in SRC if s != KERNELS]
+    """Objects in parallel (the kernel file once per group, every other source once), then one link."""
+    units = [(KERNELS, [f"-DSDP_GROUP={g}"]) for g in KERNEL_GROUPS] + [(s, []) for s in SRC if s != KERNELS]
     with tempfile.TemporaryDirectory(prefix="sdp_build_") as tmp:
         def cc(iu):
             i, (src, defs) = iu

@@ -354,7 +354,7 @@ struct VariantBits {
     bool exact, et_bcast, ref;
     int flags;   // Params::flags: bit 0 SDP_NO_ZERO_SKIP, bit 1 SDP_NO_FILL
 };
-// The packed state keeps two 20-bit weights per cell (absolute error <= 2^-21 per weight, sdp_kernels.hip "The packed state").  Its
+// The packed state keeps two 20-bit weights per cell (absolute error <= 2^-21 per weight, sdp_device.h "The packed state").  Its
 // rounding error travels along an alignment path like a random walk (the 24-bit format of rounds 1-3 instead lost 1.7e-8 of
 // E per step of a SATURATED path, 7.5e-5 at N = M = 2048: the 20-bit fields decode a saturated weight to exactly 1 and do
 // not have that term); tests/test_parity_gpu.py::test_packed_state_at_the_longest_paths_it_serves holds max |dE| at

@@ -23,10 +23,9 @@
 // +0 whatever the stored weights are.  Cells outside a pair's n x m block (per-pair lengths) are written +0 by the tile that
 // covers them, or left alone (SDP_NO_FILL, first order only); row 0 and column 0 of a Smith-Waterman block give +0.
 //
-// The packed-state decoder, the cache policies and the geometry are the sweeps' own: this file is sdp_kernels.hip's device helpers
-// (compiled as a group no sweep kernel belongs to) plus the kernels below.
-#define SDP_GROUP 0x7fff
-#include "sdp_kernels.hip"
+// The packed-state decoder, the cache policies and the geometry are the sweeps' own: this file is the device helpers the sweep
+// shares (sdp_device.h) plus the kernels below.
+#include "sdp_device.h"
 
 #include "sdp_gap.h"
 

@@ -1,5 +1,5 @@
-// sdp_kernels.h -- shared between the kernels (sdp_kernels.hip) and the C-ABI host
-// side (sdp_api.hip).  Not part of the public interface (that is include/sdp.h).
+// sdp_kernels.h -- shared between the kernels (the sweep, sdp_kernels.hip; the small kernels, sdp_aux.hip; both through the device
+// helpers' header sdp_device.h) and the C-ABI host side (sdp_api.hip).  Not part of the public interface (that is include/sdp.h).
 #ifndef SDP_KERNELS_H_
 #define SDP_KERNELS_H_
 
@@ -85,7 +85,7 @@ constexpr int max_waves(int pass)
 constexpr int THIN_LO = 32, THIN_HI = 512, THIN_FITS = 66;
 __host__ __device__ constexpr bool thin_pair(int n, int m) { return (n < m ? n : m) < THIN_LO && (n < m ? m : n) > THIN_HI; }
 constexpr int MAX_COLS = 2048;     // boundary rows live in LDS (4 x MAX_COLS x 8 B = 64 KiB)
-// how a pass represents the values that flow from cell to cell (sdp_kernels.hip, "Carry kinds")
+// how a pass represents the values that flow from cell to cell (sdp_device.h, "carries")
 enum { CK_F64 = 0, CK_F32 = 1, CK_EXP = 2 };
 // bytes of one slot of a boundary row in LDS: 4 where the values are single floats (the fp32 backward sweep), else 8
 __host__ __device__ constexpr int boundary_slot_bytes(int pass) { return pass == PASS_BWD ? 4 : 8; }
@@ -151,7 +151,7 @@ __host__ __device__ inline size_t state_order_bytes(int B) { return ((size_t)B *
 // unit u of (pair b, strip s) starts at (b * nstrips + s) * ps + u * us.  See "Skewed state addressing" in sdp_kernels.hip.
 // Packed Q: two 20-bit fields per cell, 5 bytes; a 16-step block of a lane is 20 dwords, kept as five rows of 1024 B (row j:
 // dwords 4j .. 4j+3 of every lane) -- every wave access is one dwordx4 over contiguous lines; a unit of 32 steps is two blocks,
-// ten rows.  (Rounds 1-3: 24-bit fields, 6 bytes; an 18-bit form was built in round 5 and not adopted: sdp_kernels.hip.)
+// ten rows.  (Rounds 1-3: 24-bit fields, 6 bytes; an 18-bit form was built in round 5 and not adopted: sdp_device.h.)
 constexpr int STATE_UNIT_STEPS = 32;
 constexpr unsigned STATEQ_UNIT_BYTES = 10 * 1024, STATE2_UNIT_BYTES = 32 * 512;
 // (Sharing the ramp rows of neighbouring strips -- no skew padding -- was implemented in round 2 for both formats, measured

@@ -4,7 +4,7 @@
 // O(N*M) loop: deepblast/nw_cuda.py:46-165, sw_cuda.py:46-165) with an anti-diagonal
 // sweep designed for CDNA4.  Results follow the CPU reference deepblast/nw.py (A indexed
 // [i-1,j-1], nw.py:56-58 -- NOT the GPU reference's A[last, j-1], nw_cuda.py:61-63) to
-// <= 1e-4; see "carries" below for the arithmetic each pass uses.
+// <= 1e-4; see "carries" in sdp_device.h for the arithmetic each pass uses.
 //
 // Mapping:
 //   * one workgroup per pair, W <= 8 wavefronts (throughput builds: K = 32, <= 4 waves; latency builds:
@@ -40,347 +40,9 @@
 //
 // No MFMA: this is a scalar recurrence, bounded by HBM bytes and by the length of the
 // dependency chain (N+M-1 steps), not by matrix throughput.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <type_traits>
-
-#include "sdp_kernels.h"
+#include "sdp_device.h"
 
 namespace sdp {
-
-// ----------------------------------------------------------------------------------
-// cross-lane moves (DPP full-wave shifts/rotates; gfx9 family encodings)
-// ----------------------------------------------------------------------------------
-constexpr int DPP_WAVE_SHL1 = 0x130;  // lane i <- lane i+1 ; lane 63 keeps `old`
-constexpr int DPP_WAVE_ROL1 = 0x134;  // lane i <- lane (i+1)%64
-constexpr int DPP_WAVE_SHR1 = 0x138;  // lane i <- lane i-1 ; lane 0 keeps `old`
-constexpr int DPP_WAVE_ROR1 = 0x13C;  // lane i <- lane (i-1)%64
-
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, CTRL, 0xf, 0xf, false);
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double old, double src)
-{
-    const int lo = dpp_i32<CTRL>(__double2loint(old), __double2loint(src));
-    const int hi = dpp_i32<CTRL>(__double2hiint(old), __double2hiint(src));
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ float fast_exp(float x)  // e^x via v_exp_f32 (2^x)
-{
-    return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f);
-}
-__device__ __forceinline__ float fast_log(float x)  // ln x via v_log_f32 (log2 x)
-{
-    return __builtin_amdgcn_logf(x) * 0.69314718055994530942f;
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, unsigned bytes)
-{
-    // raw buffer (stride 0), 32-bit data format; out-of-range loads return 0, stores are dropped
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);
-}
-
-constexpr unsigned OOB = 0x80000000u;  // voffset that is out of range for every buffer we build
-
-// Ablation switches for timing experiments (tools/gpu_tune.py builds variants with -DSDP_ABL=mask);
-// results are wrong when any bit is set.  bit0: no global stores, bit1: no global loads, bit2: no strip
-// hand-off waits, bit3: keep every load/store but replace the recurrence by a copy.
-#ifndef SDP_ABL
-#define SDP_ABL 0
-#endif
-#ifdef SDP_EXPERIMENTS
-#define SDP_EXP_BUILD 1
-#else
-#define SDP_EXP_BUILD 0  // default library: Params::dbg is ignored, no wrong-results switch is reachable
-#endif
-#ifndef SDP_TB_WINDOW
-#define SDP_TB_WINDOW 32  // traceback: edge of the LDS window of E (32 or 64 cells)
-#endif
-// Everything below used to be a compile-time switch of its own (31 of them by round 5).  Each was measured, one setting won, and
-// the losing code paths were deleted in round 6 (their measurements: DESIGN_HISTORY.md, "Switches retired in round 6"; the code:
-// git history).  What is left are the constants the winning settings fold to.
-//   * fp32 backward sweep: a chunk whose carries, boundary values and cotangent are all +0 produces +0 everywhere: its steps are
-//     skipped and its state rows not loaded (bit-identical; the control is the run-time flag SDP_NO_ZERO_SKIP);
-//   * adjoint backward sweep: chunks over which E, the carries and the boundary values are all zero are not run (ZSKIP_A);
-//   * cache policies (gfx950 aux bits: 1 = sc0, 2 = nt, 16 = sc1), profiles/r04_store_policy.txt, r05_steady_policies.txt: every
-//     stream is touched once per sweep -- line-aligned input blocks nt, state loads nt, state stores sc1 (what stays in the
-//     Infinity Cache between the forward and the backward sweep matters), E / Ed stores nt sc1, zero-fill stores default.
-constexpr int AUX_ST_STORE = 16, AUX_ST_LOAD = 2, AUX_IN_LOAD = 0, AUX_LINES_LOAD = 2, AUX_OUT_STORE = 18, AUX_ZERO_FILL = 0;
-constexpr bool ABL_NOSTORE = (SDP_ABL & 1) != 0;
-constexpr bool ABL_NOLOAD = (SDP_ABL & 2) != 0;
-constexpr bool ABL_NOSYNC = (SDP_ABL & 4) != 0;
-constexpr bool ABL_NOMATH = (SDP_ABL & 8) != 0;
-constexpr bool ABL_NOLDS = (SDP_ABL & 16) != 0;  // staged inputs bypass LDS (wrong data, same dependencies)
-// Progress words live in LDS and are polled by other waves.  They are accessed with explicit DS
-// instructions: a volatile access through a generic pointer compiles to flat_load + vmcnt(0),
-// which drains every outstanding prefetch at each poll.
-__device__ __forceinline__ int lds_load_i32(unsigned addr)
-{
-    int v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
-// split form: issue the read, do other LDS reads behind it (a wave's DS instructions execute in order), wait once
-__device__ __forceinline__ int lds_issue_i32(unsigned addr)
-{
-    int v;
-    asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
-__device__ __forceinline__ void lds_wait(int &v)
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v) : : "memory");
-}
-__device__ __forceinline__ void lds_store_i32(unsigned addr, int v)
-{
-    asm volatile("ds_write_b32 %0, %1" : : "v"(addr), "v"(v) : "memory");
-}
-
-template <class X>
-__device__ __forceinline__ void keep(X &x)
-{
-    asm volatile("" : "+v"(x));
-}
-
-// ----------------------------------------------------------------------------------
-// pass descriptions
-// ----------------------------------------------------------------------------------
-// Q formats: the forward sweep writes the weights either compact (Q_PACKED, read by the backward sweep) or as
-// float2 (Q_EXACT, read by the two adjoint sweeps, whose products with the -- possibly large -- directional
-// derivatives need the relative precision of fp32 for small weights as well).
-enum { Q_NONE = 0, Q_PACKED = 1, Q_EXACT = 2 };
-
-template <int PASS, bool QX>
-struct Traits;
-template <bool QX>
-struct Traits<PASS_FWD, QX> {  // nw.py:46-62
-    static constexpr int SIN = 2, SOUT = 0;
-    static constexpr int QIN = Q_NONE, QOUT = QX ? Q_EXACT : Q_PACKED;
-    static constexpr bool DIN = false, DOUT = false;
-    static constexpr bool REV = false;
-};
-template <bool QX>
-struct Traits<PASS_BWD, QX> {  // nw.py:120-135
-    static constexpr int SIN = 0, SOUT = 1;
-    static constexpr int QIN = QX ? Q_EXACT : Q_PACKED, QOUT = Q_NONE;  // QX: the training path's float2 state
-    static constexpr bool DIN = false, DOUT = false;
-    static constexpr bool REV = true;
-};
-template <bool QX>
-struct Traits<PASS_AFWD, QX> {  // nw.py:178-199
-    // QX = true here means: the seed Ztheta is not read but formed from the loss's operands -- three staged planes
-    // (ref, pred, G) instead of (Ztheta, ZA); see "fused loss seed" in the step body
-    static constexpr int SIN = QX ? 3 : 2, SOUT = 0;
-    static constexpr int QIN = Q_EXACT, QOUT = Q_NONE;
-    static constexpr bool DIN = false, DOUT = true;
-    static constexpr bool REV = false;
-};
-template <bool QX>
-struct Traits<PASS_ABWD, QX> {  // nw.py:251-267
-    static constexpr int SIN = 1, SOUT = 1;
-    static constexpr int QIN = Q_EXACT, QOUT = Q_NONE;
-    static constexpr bool DIN = true, DOUT = false;
-    static constexpr bool REV = true;
-};
-
-// The packed state (read by the backward sweep only; see Q_EXACT above): two 20-bit fields per cell, 5 bytes (round 4; rounds
-// 1-3 kept two 24-bit fields, 6 bytes; 18-bit fields were built in round 5, gated by emulation and NOT adopted -- one per cent of
-// time for three quarters of the margin; two unorm16 per cell were rejected in round 1: their rounding error is carried along an
-// alignment path like a random walk and passes 1e-4 on E beyond ~1000 residues.  DESIGN.md section 2, DESIGN_HISTORY.md).
-// A field is the low 20 bits of the float f = 8 + q * (1 - 2^-19): in [8, 16) one ulp is 2^-20, so the fma's own rounding puts q on
-// a grid of 2^-20 (absolute error <= 2^-21 = 4.8e-7 per weight; emulated on the float64 oracle's weights,
-// tools/emu_state_formats.py: max |dE| 9e-7 on the benchmark's scores, 3.4e-6 on peaked ones at 512 x 512 -- the 1e-4 bound is 30x
-// away, and problems with N + M > 4096 take the exact state).  The factor keeps the field below 2^20 for q <= 1 + 9e-7 -- a weight
-// computed as c / sum * u can exceed 1 by a few ulp -- so no clamp is needed; a saturated weight (anything within 2^-21 of 1)
-// decodes to exactly 1, a weight below 2^-21 to exactly 0, so a saturated path loses nothing.  Four cells -- eight fields, x0 y0 x1
-// y1 x2 y2 x3 y3 from bit 0 up -- fill five dwords; the 20 dwords of a 16-step block are stored as five rows of one dwordx4 per
-// lane (sdp_kernels.h).  The derivative state Qd is signed and unbounded and stays float2.
-constexpr float QF_SCALE = 0.99999809265136718750f;    // 1 - 2^-19
-constexpr float QF_UNSCALE = 1.0000019073486328125f;   // 1 + 2^-19 = 1 / (1 - 2^-19) to fp32
-constexpr float QF_BASE = 8.0f;
-// raw bits fx[k], fy[k] of the four cells' biased floats (0x41000000 | field) -> five dwords
-__device__ __forceinline__ void q20_pack4(const unsigned *fx, const unsigned *fy, unsigned *w)
-{
-    // (a left shift pushes the exponent byte out of the dword, and bits 20-23 of a biased float are zero, so only fields
-    //  that stay below bit 24 after their shift need masking)
-    w[0] = (fx[0] & 0xfffffu) | (fy[0] << 20);
-    w[1] = __builtin_amdgcn_ubfe(fy[0], 12, 8) | (fx[1] << 8) | (fy[1] << 28);
-    w[2] = __builtin_amdgcn_ubfe(fy[1], 4, 16) | (fx[2] << 16);
-    w[3] = __builtin_amdgcn_ubfe(fx[2], 16, 4) | ((fy[2] & 0xfffffu) << 4) | (fx[3] << 24);
-    w[4] = __builtin_amdgcn_ubfe(fx[3], 8, 12) | (fy[3] << 12);
-}
-__device__ __forceinline__ float q20_field(unsigned u)  // field in the low 20 bits of u, anything above -> f - 8
-{
-    // gfx9 allows one constant-bus operand per VALU instruction, so the compiler, given two literals ((u & mask) | bias), emits
-    // two instructions; with the bias in a register the bit-field insert does it in one (15.5 -> 13.75 VALU per step).  Same bits.
-    unsigned r;
-    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "s"(0xfffffu), "v"(u), "v"(0x41000000u));
-    return __uint_as_float(r) - 8.0f;
-}
-// (f - 8) of both weights of cell `sub` (0..3) of a five-dword record; the caller multiplies by QF_UNSCALE
-__device__ __forceinline__ float2 q20_unpack(const unsigned *w, int sub)
-{
-    switch (sub) {
-    case 0: return make_float2(q20_field(w[0]), q20_field(__builtin_amdgcn_alignbit(w[1], w[0], 20)));
-    case 1: return make_float2(q20_field(w[1] >> 8), q20_field(__builtin_amdgcn_alignbit(w[2], w[1], 28)));
-    case 2: return make_float2(q20_field(__builtin_amdgcn_alignbit(w[3], w[2], 16)), q20_field(w[3] >> 4));
-    default: return make_float2(q20_field(__builtin_amdgcn_alignbit(w[4], w[3], 24)), q20_field(w[4] >> 12));
-    }
-}
-
-// Exact-state weights: the largest of the three is formed as 1 - (the other two).  c/sum*u goes through an
-// approximate reciprocal and two products (~1.5 ulp): harmless for a weight of 0.3, but a weight that the reference
-// -- which divides in float64 and rounds once (nw.py:21-22,115) -- stores as exactly 1.0 would come out as
-// 1 +- 1e-7, and the adjoint sweeps turn such an error into (1 - q) * a, relative to a difference that should be
-// 0: on long, peaked alignments it reached 1e-3 of Ed.  The small weights carry the same relative error, so the
-// complement is accurate to 1e-7 * (1 - q).  When the match weight qm is the largest nothing has to be done: the
-// readers form qm = 1 - qx - qy anyway.
-typedef float f32x2 __attribute__((ext_vector_type(2)));  // operand of the packed fp32 instructions (v_pk_mul / v_pk_fma)
-
-// 2^(theta log2e) = 2^tt * (1 + c) where tt = fl(theta * fl(log2e)) is what v_exp_f32 was given and
-// c = ln2 * (theta * log2e - tt), the rounding of the product recovered exactly (fma) plus the low part of log2(e).
-// |c| <= |tt| 2^-24: the second-order term is below 1e-12.
-__device__ __forceinline__ f32x2 exp2_residual(f32x2 theta, f32x2 tt)
-{
-    constexpr float L_HI = 1.44269502162933349609375f, L_LO = 1.92596299112661746e-8f, LN2 = 0.69314718055994530942f;
-    f32x2 d = __builtin_elementwise_fma(theta, (f32x2){L_HI, L_HI}, -tt);
-    d = __builtin_elementwise_fma(theta, (f32x2){L_LO, L_LO}, d);
-    return d * (f32x2){LN2, LN2};
-}
-
-__device__ __forceinline__ void q_sharpen(float &wx, float &wy, float wm)
-{
-    const float big = __builtin_fmaxf(wx, wy), small = __builtin_fminf(wx, wy);
-    const float o = 1.0f - (small + wm);
-    const float nb = big > 0.5f ? o : big;
-    const bool xbig = wx >= wy;
-    wx = xbig ? nb : wx;
-    wy = xbig ? wy : nb;
-}
-
-// ----------------------------------------------------------------------------------
-// carries
-// ----------------------------------------------------------------------------------
-// How a pass represents the values that flow from cell to cell (and across strips):
-//   CK_F64 : float64, as the reference does internally (nw.py:49-53,125,182-185,256).
-//   CK_F32 : float32.  Used by the backward sweep: E is a sum of non-negative products of weights
-//            in [0,1], so there is no cancellation and fp32 accumulation stays ~1e-6 of the result.
-//   CK_EXP : scaled exp-domain pair (a, e) with V = e*ln2 + ln(a), a in [0.5,1).  The forward
-//            recurrence  V = theta + log(e^(A+up) + e^diag + e^(A+left))  becomes
-//            alpha = c_theta * (c_A*(u + l) + d): one fma chain with no exp/log on the dependency
-//            chain (the HMM "scaled forward algorithm").  theta and A are split into an integer
-//            power of two (added to the exponent) and a factor in [1,2), and the three operands are
-//            aligned to their largest exponent, so no finite input can overflow or cancel; every
-//            rescale is an exact power of two, so the only rounding is the fp32 fma chain itself.
-// (the enum and boundary_slot_bytes live in sdp_kernels.h: the host sizes the LDS rows by them.  Which pass uses which kind was a
-// build-time choice until round 6; the alternatives -- a float64 forward, a float64 backward, an fp32 adjoint backward -- lost by
-// measurement or by parity in rounds 1-2 and are gone.)
-
-template <int PASS>
-struct Kind {
-    static constexpr int value = PASS == PASS_FWD ? CK_EXP : (PASS == PASS_BWD ? CK_F32 : CK_F64);
-};
-
-typedef unsigned long long u64;  // one boundary slot (LDS) / one edge value in registers
-
-__device__ __forceinline__ u64 pack2(unsigned lo, unsigned hi) { return ((u64)hi << 32) | lo; }
-__device__ __forceinline__ unsigned lo32(u64 x) { return (unsigned)x; }
-__device__ __forceinline__ unsigned hi32(u64 x) { return (unsigned)(x >> 32); }
-
-// V = 0 in the exp-domain representation: 0.5 * 2^1
-// Windowed form of the exp-domain forward (see steps_wf in sweep): values of one chunk are plain floats relative
-// to a per-lane exponent ("frame").  After the K steps every value a lane produced must lie in [WF_LO, WF_HI]:
-//   * overflow anywhere in a step gives inf (or NaN), which stays in the lane's value and trips the upper test;
-//   * the factors 2^theta and 2^A of every step must not exceed WF_FMAX = 2^12 (|theta|, |A| <= 8.3; anything
-//     else, including NaN, goes to the normalised form).  Then a value >= WF_LO = 2^-100 proves that the sum it
-//     was made from was a normal float (>= 2^-112), and values <= WF_HI = 2^110 keep every sum below 2^124, so its
-//     reciprocal is a normal float too.  A = -inf (2^A = 0) is fine.
-// A chunk that fails a test is redone in the per-step-normalised form; nothing was committed before the test.
-// WF_HI also leaves room for the consumers of published values (value * 2^A * 2 + ... stays below 2^128).
-// Values mostly grow along a row (fastest in the lower left corner of the matrix: ~5 bits per step, and 10-20 in a row's first
-// columns), so a lane's frame is placed WF_BIAS bits above the exponent of its current value: it starts the block at
-// 2^-WF_BIAS, with 110 + WF_BIAS bits of room upwards and 100 - WF_BIAS downwards.  Round 4: 40 -> 64.  With 40 the head
-// blocks of the two bottom strips of a 512 x 512 pair failed the range test (rows 400+ gain 152-158 bits in the 16 steps
-// after their first column; cycle stamps: 6 + 5 blocks at 7-10k cycles instead of 2k, all on the pair's critical path --
-// strip 7 cannot start before strip 6's head is through), ~11 % of the launch.  Blocks that fail, by bias (40 / 56 / 64 /
-// 80) on 512 x 512: benchmark scores 8 / 0 / 0 / 0; theta x 8: 191 / 127 / 110 / 73; theta - 2: 0 / 0 / 0 / 159; theta x 8 - 4:
-// 47 / 38 / 35 / 76; A + 0.5: 10 / 0 / 0 / 0 (emulated from the float64 V).  Which form a block runs in does not change a
-// cell's value, and only in the packed state whether its weights are sharpened (see norm_block).
-constexpr unsigned WF_HI = 0x76800000u;  // 2^110
-constexpr unsigned WF_LO = 0x0d800000u;  // 2^-100
-constexpr unsigned WF_FMAX = 0x45800000u;  // 2^12
-#ifndef SDP_WF_BIAS
-#define SDP_WF_BIAS 64
-#endif
-constexpr int WF_BIAS = SDP_WF_BIAS;
-constexpr int WB = 16;  // steps per frame (every chunk length is a multiple)
-constexpr int FRAME_NONE = (int)0x80000000;  // published chunk is not in one frame (per-value exponents apply)
-constexpr float EXP_ONE_A = 0.5f;
-constexpr int EXP_ONE_E = 1;
-constexpr int ZERO_E = -(1 << 29);   // the exponent a zero operand takes in the normalised forward form: below every real one
-
-template <int KIND>
-__device__ __forceinline__ u64 edge_zero()
-{
-    if constexpr (KIND == CK_EXP) return pack2(__float_as_uint(EXP_ONE_A), (unsigned)EXP_ONE_E);
-    else return 0ull;  // +0.0 as f64 and as f32
-}
-
-// bank-spreading permutation of the staged-input ring (see "Staged INPUT geometry"): 0,4,1,5,2,6,3,7
-__device__ __forceinline__ constexpr int ring_pi(int x) { return ((x & 1) << 2) | (x >> 1); }
-
-// per-lane recurrence state carried from step to step
-struct Carry {
-    // CK_F64: a = own V / value sent up, b = previous `up` / own py, c = pm of the previous step
-    double a, b, c;
-    // CK_F32 (reverse): same roles in fp32
-    float fa, fb, fc;
-    // CK_EXP (forward): own (alpha, exponent), and the diagonal predecessor's pair
-    float xa;
-    int xe;
-    float da;
-    int de;
-};
-
-// per-cell terms of the masked alignment losses (used by the loss kernels and by the fused seed of the adjoint forward)
-__device__ __forceinline__ float loss_clamp(float p)
-{
-    const float eps = 3e-8f;  // losses.py:27
-    return fminf(fmaxf(p, eps), 1.0f - eps);
-}
-
-// value of one counted cell (kind as above).  1 - p rounded to fp32 is off by up to 3e-8, which is all of log(1 - p) at
-// p = 3e-8 and 3e-6 of it at p = 0.01 -- a pair whose counted cells are all such would miss the float64 value by that
-// much.  So 1 - p = q + e exactly (Fast2Sum, p <= 1), and log(1 - p) = log(q) + e / q, with e / q taken as e: e != 0 only
-// where p < 1/2, and there the difference, e * p / q, is below 6e-8 of log(1 - p).  (log1pf does the same job, but
-// measured on MI355X at 256 x 512^2 the forward kernel then took 294-314 us instead of 142-146 us.)  The square of kinds 1 and 2 is formed in float64: d itself is an fp32
-// value, so d * d is exact there, where in fp32 it would lose bits below 1e-19 (denormal squares) and vanish below 1e-23
-// -- a pair whose vector is all that small would then get norm 0 instead of the reference's norm
-__device__ __forceinline__ double loss_term(float r, float y, int kind)
-{
-    if (kind == 0) {
-        const float p = loss_clamp(y);
-        const float q = 1.0f - p, e = (1.0f - q) - p;
-        return (double)(r * logf(p) + (1.0f - r) * (logf(q) + e));
-    }
-    const double d = (double)(kind == 1 ? r * y : r - y);
-    return d * d;
-}
-// derivative factor of one counted cell w.r.t. the predicted value
-__device__ __forceinline__ float loss_dterm(float r, float y, float sc, int kind)
-{
-    if (kind == 0) {
-        const float eps = 3e-8f;
-        return (y >= eps && y <= 1.0f - eps) ? sc * (r / y - (1.0f - r) / (1.0f - y)) : 0.f;  // clamp passes the gradient inside only
-    }
-    return kind == 1 ? sc * r * r * y : sc * (r - y);
-}
 
 // ----------------------------------------------------------------------------------
 // the sweep
@@ -523,20 +185,20 @@ __device__ __forceinline__ void sweep(const Params &p)
             if (nabsent > 0 ? !absent : part != 0) return;
             if (absent && wg_part != nparts) return;   // (the first of them does it all: the later ones come last in the dispatch order)
             const int idle = W > nstrips_wg ? W - nstrips_wg : 0;
-            const int parts = absent ? W : (idle > 0 ? idle : W);                            // waves that share the fill,
-            const int part = absent ? wave : (idle > 0 ? wave - nstrips_wg : wave);          // this one's index among them
-            if (part < 0) return;
+            const int fill_waves = absent ? W : (idle > 0 ? idle : W);                       // waves that share the fill,
+            const int fill_wave = absent ? wave : (idle > 0 ? wave - nstrips_wg : wave);     // this one's index among them
+            if (fill_wave < 0) return;
             typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
             constexpr int ZF_AUX = AUX_ZERO_FILL;
             const u32x4 z4 = {0u, 0u, 0u, 0u};
             __amdgpu_buffer_rsrc_t rz = make_rsrc(p.sout + ((SDP_EXP_BUILD && (p.dbg & 2)) ? 0 : (size_t)b) * plane_elems, plane_bytes);
             // rows [n, N): one contiguous run; stores past the end of the plane are dropped dword by dword
             const unsigned tail1 = (unsigned)(p.N * p.M);
-            for (unsigned e = (unsigned)(n * p.M) + (unsigned)(part * 64 + lane) * 4u; e < tail1; e += (unsigned)parts * 256u)
+            for (unsigned e = (unsigned)(n * p.M) + (unsigned)(fill_wave * 64 + lane) * 4u; e < tail1; e += (unsigned)fill_waves * 256u)
                 __builtin_amdgcn_raw_buffer_store_b128(z4, rz, e * 4u, 0, ZF_AUX);
             // rows [0, n): columns [m, M)
             if (m < p.M) {
-                for (int r = part; r < n; r += parts) {
+                for (int r = fill_wave; r < n; r += fill_waves) {
                     const unsigned row = (unsigned)(r * p.M);
                     for (int c = m + 4 * lane; c < p.M; c += 256) {
                         if (c + 4 <= p.M) {
@@ -2596,7 +2258,7 @@ __device__ __forceinline__ void sweep(const Params &p)
 #define SDP_BUILD(ID, NAME, PASS, K, MAXW, F) SDP_KERNEL(NAME, PASS, K, MAXW, F, (ID) == (SDP_ONLY))
 #else
 // (-DSDP_GROUP=<g>: compile one group of kernels -- deepblast_amd/build.py builds the groups of this file in parallel and links
-//  them; without it, everything.  Group 0 holds the small kernels at the end of the file.)
+//  them; without it, everything)
 #ifndef SDP_GROUP
 #define SDP_GROUP (-1)
 #endif
@@ -2604,497 +2266,3 @@ __device__ __forceinline__ void sweep(const Params &p)
 #define SDP_BUILD(ID, NAME, PASS, K, MAXW, F) SDP_KERNEL(NAME, PASS, K, MAXW, F, true)
 #endif
 #include "sdp_builds.def"
-#if SDP_IN_GROUP(0)
-
-// ----------------------------------------------------------------------------------
-// launch order for variable-length batches: order[r] = the pair with the r-th largest n*m (ties: lower index first).
-// Rank by counting -- B is at most a few thousand, the (B,2) lengths sit in L2 -- so no sort, no scratch memory.
-// ----------------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(256) sdp_order_kernel(const int *lens, int *order, int B, int N, int M)
-{
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    auto work = [&](int i) {
-        int n = lens[2 * i], m = lens[2 * i + 1];
-        n = n < 1 ? 1 : (n > N ? N : n);
-        m = m < 1 ? 1 : (m > M ? M : m);
-        return n * m;
-    };
-    const int mine = work(b);
-    int rank = 0;
-    for (int i = 0; i < B; ++i) {
-        const int w = work(i);
-        rank += (w > mine || (w == mine && i < b)) ? 1 : 0;
-    }
-    order[rank] = b;
-}
-
-// ----------------------------------------------------------------------------------
-// bridge rows of a parts launch: every granule "not written yet" (sdp_kernels.h: XB_INVALID in both words)
-// ----------------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(256) sdp_bridge_reset_kernel(unsigned long long *xb, size_t n8)
-{
-    const unsigned long long pattern = ((unsigned long long)sdp::XB_INVALID << 32) | sdp::XB_INVALID;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) xb[i] = pattern;
-}
-
-// ----------------------------------------------------------------------------------
-// dispatch order when pairs are spread over several workgroups ("parts") and have their own lengths: map[h] = pair *
-// nparts_max + part for workgroup h.  Workgroups are handed to CUs in index order as CUs free up, and a part that is on
-// a CU before its producer has reached it only waits there.  So: every pair's part 0 first, then the parts 1, ... -- part
-// k has nothing to do for the first k * 4 * 79 steps (~60 us each) of its pair, about the time the shortest pairs of the
-// batch take to leave their CUs -- and within one k by the critical path that still hangs on the part, longest first
-// ((P - 1 - k) * 4 * 79 + 3 * 79 + m + 63 steps for a pair of P parts and m columns).  A producer always precedes its
-// consumer, so a waiting part never keeps its producer off the chip.  (Ranking by the critical path alone put all parts
-// of the long pairs on CUs at once, most of them waiting: forward sweep of BASELINE configs[2] 600 us instead of 511.)
-// Slots k of pairs with k parts or fewer come at the end of the parts k: in the forward sweep they exit at once, in the
-// backward sweep they zero-fill E outside the pair's block (sorted behind everything else the fill ran at the very end,
-// on the few CUs that were free: 483 instead of 3xx us).  Rank by counting, as above.
-// ----------------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(256) sdp_parts_map_kernel(const int *lens, int *map, int B, int N, int M, int nparts_max, int strips)
-{
-    // one wavefront per workgroup-to-be: its 64 lanes share the scan over the list (ranking 1024 parts with one thread
-    // each took ~50 us -- a tenth of the sweep it was meant to speed up)
-    const int h = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int total = B * nparts_max;
-    if (h >= total) return;
-    auto key = [&](int e) {
-        const int pr = e / nparts_max, k = e % nparts_max;
-        int n = lens[2 * pr], m = lens[2 * pr + 1];
-        n = n < 1 ? 1 : (n > N ? N : n);
-        m = m < 1 ? 1 : (m > M ? M : m);
-        const int np = ((n + 63) / 64 + strips - 1) / strips;
-        return (nparts_max - k) * 65536 + (k < np ? (np - 1 - k) * strips * 79 + (strips - 1) * 79 + m + 63 : 0);
-    };
-    const int mine = key(h);
-    int cnt = 0;
-    for (int e = lane; e < total; e += 64) {
-        const int w = key(e);
-        cnt += (w > mine || (w == mine && e < h)) ? 1 : 0;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-    if (lane == 0) map[cnt] = h;
-}
-
-// ----------------------------------------------------------------------------------
-// batched traceback: the reference's greedy arg-max walk (deepblast/nw.py:401-444,
-// sw.py:328-371).  Integer work, bit-identical to the host version in deepblast_amd/_dp.py::traceback,
-// including Python's negative-index wrap when exactly one of (i, j) is 0; a walk that leaves the matrix
-// (the reference raises IndexError) sets count = -1.
-//
-// One wavefront per pair.  The walk is a chain of <= N+M dependent steps, each reading three neighbours of the
-// current cell; one lane per pair with three global loads per step (round 1) paid a full memory latency per step --
-// 0.9 ms at 256 x 512 x 512, more than twice the two sweeps that produce E.  Here the wave keeps the 32 x 32 window
-// of E whose bottom-right corner is the current cell in LDS (16 coalesced loads per lane, all in flight together);
-// the walk only moves up and left, so it stays inside for 31 ... 62 steps, each three LDS broadcasts and a few scalar
-// compares, before the window is re-centred.  Steps are collected one per lane and written 64 at a time from the END
-// of the pair's buffer backwards (the reference returns the walk reversed; its length is not known in advance), then
-// the wave moves them to the front.  The window is filled through python's index wrap, so the top row / left column
-// (floor values, reads that wrap to the opposite edge) and already-wrapped walks use the same loop.
-// ----------------------------------------------------------------------------------
-// RULE 0: the CPU reference's walk (nw.py:401-444: stop when ALL three neighbours are off the matrix, sentinel -1e5,
-// python's index wrap).  RULE 1: the walk of the reference's GPU classes (nw_cuda.py:273-317, sw_cuda.py:283-327: stop
-// as soon as ANY neighbour is off the matrix -- or holds the sentinel -1e10; no wrap, never an IndexError).
-template <int RULE>
-__device__ __forceinline__ void traceback_walk(const float *grad, int *states, int *counts, const int *lens, int B, int N, int M, int cap)
-{
-    constexpr int TW = SDP_TB_WINDOW, TWL = TW == 64 ? 6 : 5;   // window edge (32 or 64 cells)
-    __shared__ float tile[TW * TW];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    if (b >= B) return;
-    int n = N, m = M;
-    if (lens) {
-        n = __builtin_amdgcn_readfirstlane(lens[2 * b]);
-        m = __builtin_amdgcn_readfirstlane(lens[2 * b + 1]);
-        n = n < 1 ? 1 : (n > N ? N : n);
-        m = m < 1 ? 1 : (m > M ? M : m);
-    }
-    const float *g = grad + (size_t)b * N * M;
-    int *out = states + (size_t)b * cap * 3;
-    const float floor_v = RULE ? -1e10f : -100000.f;
-    // A walk has at most n + m - 1 steps: every step lowers i or j, a step that lowers only i needs i > 0, and j never
-    // goes below 0.  The API passes cap = N + M + 2.
-    if (cap < n + m) {
-        if (lane == 0) counts[b] = -1;
-        return;
-    }
-    bool bad = false;
-    // every value the walk branches on is the same in all 64 lanes, but a load (LDS or global) is a divergent source to
-    // the compiler: these keep the control flow scalar
-    auto uni = [](float v) -> float { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
-    auto all = [](bool c) -> bool { return __builtin_amdgcn_ballot_w64(c) != 0; };   // c is uniform: any lane == all lanes
-    // Steps are recorded as their state only, one per lane; a step moves by (state != 2, state != 0), so the positions
-    // of a group of 64 follow from the position before the group and two prefix counts (the first record, state 1 at
-    // (n-1, m-1), is "a diagonal step from (n, m)").  Groups go to the END of the pair's buffer, last step first.
-    int cnt = 0, my_s = 0;
-    int base_i = n, base_j = m;   // position before the first step of the current group
-    auto flush = [&](int first, int count, int now_i, int now_j) {  // steps first .. first+count-1 -> positions cap-1-step
-        const bool mine = lane < count;
-        const unsigned long long mi = __builtin_amdgcn_ballot_w64(mine && my_s != 2), mj = __builtin_amdgcn_ballot_w64(mine && my_s != 0);
-        const int pi = __builtin_amdgcn_mbcnt_hi((unsigned)(mi >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mi, 0)) + (int)((mi >> lane) & 1);
-        const int pj = __builtin_amdgcn_mbcnt_hi((unsigned)(mj >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mj, 0)) + (int)((mj >> lane) & 1);
-        if (mine) {
-            int *o = out + 3 * (size_t)(cap - 1 - (first + lane));
-            o[0] = base_i - pi, o[1] = base_j - pj, o[2] = my_s;
-        }
-        base_i = now_i, base_j = now_j;
-    };
-    auto record = [&](int st, int now_i, int now_j) {  // now = the position after this step
-        if (lane == (cnt & 63)) my_s = st;
-        ++cnt;
-        if ((cnt & 63) == 0) flush(cnt - 64, 64, now_i, now_j);
-    };
-
-    // The walk in "virtual" coordinates: i and j only decrease and may go below 0, where python's indexing wraps them
-    // to the other edge (nw.py:423 reads grad[i-1, j-1] with i = 0 or j = 0) -- at most once (below -n / -m the
-    // reference raises IndexError: bad).  left is off the matrix for i <= 0, upper for j <= 0, all three for both.
-    // The window is filled through the same wrap, so one loop serves the interior, the edges and the wrapped walk.
-    int i = n - 1, j = m - 1;
-    record(1, i, j);
-    while (true) {
-        if (RULE ? (i <= 0 || j <= 0) : (i <= 0 && j <= 0)) break;   // the reference's stop rule (all three / any one off the matrix)
-        const int r0 = i - (TW - 1), c0 = j - (TW - 1);
-        __syncthreads();  // one wave: orders the LDS reads of the old window before these writes
-        {
-            float v[TW * TW / 64];
-            int vj = c0 + (lane & (TW - 1));
-            vj += vj < 0 ? m : 0;
-            const bool okj = vj >= 0;
-#pragma unroll
-            for (int k = 0; k < TW * TW / 64; ++k) {
-                int vi = r0 + (lane >> TWL) + (64 / TW) * k;
-                vi += vi < 0 ? n : 0;
-                // rows / columns below -n / -m are never read (see `bad` below): clamped address, so that all loads
-                // are in flight together
-                v[k] = __builtin_nontemporal_load(g + (size_t)max(vi, 0) * M + (okj ? vj : 0));
-            }
-#pragma unroll
-            for (int k = 0; k < TW * TW / 64; ++k) tile[((lane >> TWL) + (64 / TW) * k) * TW + (lane & (TW - 1))] = v[k];
-        }
-        __syncthreads();
-        int ti = TW - 1, tj = TW - 1;   // the current cell; the walk stays in the window while both are >= 1
-        bool stop = false;
-        if (TW == 32 && r0 >= 0 && c0 >= 0) {
-            // ---- the whole window is inside the matrix: no floor values, no wrap (round 6) ----
-            // Which way a cell sends the walk depends on the cell alone, so the choices of all 31 x 31 cells of the window are made at
-            // once -- the same three comparisons per cell as in the loop below, sixteen cells per lane -- and kept as two bits per cell
-            // (0 / 1 / 2: the step; 3: the sentinel rule says stop) in ONE register: lane c + 32 h holds column c, rows 16 h .. 16 h + 15.
-            // A step of the walk is then a v_readlane, a shift and a few scalar instructions -- no LDS round trip and no ballot in
-            // the chain of <= N + M dependent steps (it was three broadcast reads and three ballots per step: ~360 cycles).
-            const int cc = lane & 31, hh = lane >> 5;
-            float colv[17];   // rows 16 hh - 1 .. 16 hh + 15 of column cc (row -1 is never a current cell's: clamped)
-#pragma unroll
-            for (int k = 0; k < 17; ++k) colv[k] = tile[max(16 * hh - 1 + k, 0) * TW + cc];
-            unsigned code = 0;
-#pragma unroll
-            for (int k = 1; k < 17; ++k) {
-                // cell (r, cc), r = 16 hh + k - 1: left = (r - 1, cc), diag = (r - 1, cc - 1), upper = (r, cc - 1); column cc - 1 is the
-                // lane below's (column 0 has no current cells: the walk leaves the window at tj = 0)
-                const float left = colv[k - 1];
-                const float diag = __int_as_float(sdp::dpp_i32<sdp::DPP_WAVE_SHR1>(0, __float_as_int(colv[k - 1])));
-                const float upper = __int_as_float(sdp::dpp_i32<sdp::DPP_WAVE_SHR1>(0, __float_as_int(colv[k])));
-                const bool c1 = diag > left;
-                const float bv1 = c1 ? diag : left;
-                const bool c2 = upper > bv1;
-                const bool halt = RULE ? (left == floor_v || diag == floor_v || upper == floor_v)
-                                       : (left == floor_v && diag == floor_v && upper == floor_v);
-                code |= (halt ? 3u : (c2 ? 2u : (c1 ? 1u : 0u))) << (2 * (k - 1));
-            }
-            // The steps themselves run in segments of at most 32 that end where a group of 64 records is complete: inside a segment
-            // the states collect in a scalar (two bits per step) and nothing but the look-up, the move and the loop test is in the
-            // chain; the lanes take their records -- and a complete group leaves -- between segments.
-            while (true) {
-                const int cnt0 = cnt;
-                const int room = 64 - (cnt0 & 63), lim = room < 32 ? room : 32;
-                unsigned long long acc = 0;
-                int k = 0;
-                bool halted = false;
-                while (ti >= 1 && tj >= 1 && k < lim) {
-                    const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)code, tj + 32 * (ti >> 4));
-                    const int st = (int)((w >> (2 * (ti & 15))) & 3u);
-                    if (st == 3) {
-                        halted = true;
-                        break;
-                    }
-                    ti -= st == 2 ? 0 : 1;
-                    tj -= st == 0 ? 0 : 1;
-                    acc = (acc << 2) | (unsigned long long)st;
-                    ++k;
-                }
-                // step t of the segment (0 = first) sits in bits 2 (k - 1 - t) of acc; its record belongs to lane (cnt0 + t) mod 64
-                const int t = (lane - cnt0) & 63;
-                if (t < k) my_s = (int)((acc >> (2 * (k - 1 - t))) & 3ull);
-                cnt = cnt0 + k;
-                if (k > 0 && (cnt & 63) == 0) flush(cnt - 64, 64, r0 + ti, c0 + tj);
-                if (halted) {
-                    stop = true;
-                    break;
-                }
-                if (!(ti >= 1 && tj >= 1)) break;
-            }
-        } else if (r0 >= 0 && c0 >= 0) {
-            // ---- the same for the other window size: three LDS broadcasts and the comparisons per step ----
-            while (ti >= 1 && tj >= 1) {
-                const float *p = tile + ti * TW + tj;
-                const float left = p[-TW], diag = p[-TW - 1], upper = p[-1];
-                const bool c1 = all(diag > left);
-                const float bv1 = c1 ? diag : left;
-                const bool c2 = all(upper > bv1);
-                const float bv = c2 ? upper : bv1;
-                if constexpr (RULE) {
-                    if (all(left == floor_v || diag == floor_v || upper == floor_v)) {   // a stored value equal to the sentinel stops the walk too
-                        stop = true;
-                        break;
-                    }
-                } else if (all(bv == floor_v)) {   // only then can all three be the floor value
-                    if (all(left == floor_v && diag == floor_v && upper == floor_v)) {
-                        stop = true;
-                        break;
-                    }
-                }
-                ti -= c2 ? 0 : 1;
-                tj -= (c1 || c2) ? 1 : 0;
-                record(c2 ? 2 : (c1 ? 1 : 0), r0 + ti, c0 + tj);
-            }
-        } else {
-            while (ti >= 1 && tj >= 1) {
-                const int vi = r0 + ti, vj = c0 + tj;
-                const bool fl = vi <= 0, fu = vj <= 0;
-                if (RULE ? (fl || fu) : (fl && fu)) {
-                    stop = true;
-                    break;
-                }
-                if (vi - 1 < -n || vj - 1 < -m) {   // the diagonal read would wrap twice: IndexError in the reference
-                    bad = true;
-                    break;
-                }
-                const float *p = tile + ti * TW + tj;
-                const float t0 = p[-TW], t1 = p[-TW - 1], t2 = p[-1];
-                const float left = fl ? floor_v : uni(t0), diag = uni(t1), upper = fu ? floor_v : uni(t2);
-                if (RULE ? (left == floor_v || diag == floor_v || upper == floor_v) : (left == floor_v && diag == floor_v && upper == floor_v)) {
-                    stop = true;
-                    break;
-                }
-                int best = 0;
-                float bv = left;
-                if (diag > bv) best = 1, bv = diag;
-                if (upper > bv) best = 2, bv = upper;
-                ti -= best == 2 ? 0 : 1;
-                tj -= best == 0 ? 0 : 1;
-                record(best, r0 + ti, c0 + tj);
-            }
-        }
-        i = r0 + ti, j = c0 + tj;
-        if (stop || bad) break;
-    }
-    while (!bad && i > 0) {
-        i -= 1;
-        record(0, i, j);
-    }
-    while (!bad && j > 0) {
-        j -= 1;
-        record(2, i, j);
-    }
-    if (bad) {
-        if (lane == 0) counts[b] = -1;
-        return;
-    }
-    flush(cnt & ~63, cnt & 63, i, j);
-    // the wave reads back what its own lanes stored: workgroup scope is enough (an agent-scope fence writes back and
-    // invalidates the L2 on this chip -- tens of microseconds each)
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    // steps sit reversed at out[cap-cnt .. cap): move them to the front (ascending groups of 64 never write where a
-    // later group still has to read: the source is always at or above the destination)
-    const int shift = cap - cnt;
-    if (shift > 0) {
-        for (int k0 = 0; k0 < cnt; k0 += 64) {
-            const int k = k0 + lane;
-            int v0 = 0, v1 = 0, v2 = 0;
-            if (k < cnt) {
-                const int *src = out + 3 * (size_t)(shift + k);
-                v0 = __builtin_nontemporal_load(src), v1 = __builtin_nontemporal_load(src + 1), v2 = __builtin_nontemporal_load(src + 2);
-            }
-            __syncthreads();
-            if (k < cnt) {
-                int *dst = out + 3 * (size_t)k;
-                dst[0] = v0, dst[1] = v1, dst[2] = v2;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        }
-    }
-    if (lane == 0) counts[b] = cnt;
-}
-
-extern "C" __global__ void __launch_bounds__(64) sdp_traceback_kernel(const float *grad, int *states, int *counts,
-                                                                      const int *lens, int B, int N, int M, int cap)
-{
-    traceback_walk<0>(grad, states, counts, lens, B, N, M, cap);
-}
-extern "C" __global__ void __launch_bounds__(64) sdp_traceback_cuda_kernel(const float *grad, int *states, int *counts,
-                                                                           const int *lens, int B, int N, int M, int cap)
-{
-    traceback_walk<1>(grad, states, counts, lens, B, N, M, cap);
-}
-
-// ----------------------------------------------------------------------------------
-// masked alignment losses: the reference evaluates its losses with a Python loop over the
-// batch -- slice [:x_len, :y_len], masked_select by G, reduce (deepblast/losses.py:9-48, 51-79, 82-118).
-// Here one launch reduces every pair (one workgroup per pair, float64 accumulation, deterministic
-// order), and one launch writes the gradient w.r.t. the predicted matrix.
-//   kind 0 MatrixCrossEntropy : acc = sum_G [ Yt log p + (1-Yt) log(1-p) ],  p = clamp(Yp, 3e-8, 1-3e-8)
-//   kind 1 SoftPathLoss       : acc = sum_G (P * Yp)^2
-//   kind 2 SoftAlignmentLoss  : acc = sum_G (Yt - Yp)^2
-// HBM-bound elementwise work: 12 B read per cell in the forward, 12 B read + 4 B written in the backward.
-// ----------------------------------------------------------------------------------
-// One workgroup per pair; a thread takes four consecutive columns of a row per iteration (one 16-byte load per
-// tensor when every row of every tensor is 16-byte aligned: M a multiple of 4 and 16-byte aligned base pointers, which
-// the host decides and passes as `vec4`), so the three tensors stream at full width and there is one index division per
-// four cells.  Per-thread float64 partial sums, fixed reduction order: deterministic.
-extern "C" __global__ void __launch_bounds__(1024) sdp_loss_fwd_kernel(const float *ref, const float *pred, const float *G,
-                                                                       const int *lens, double *acc, int *cnt, int N, int M,
-                                                                       int kind, int vec4)
-{
-    __shared__ double s_acc[16];
-    __shared__ int s_cnt[16];
-    const int b = blockIdx.x;
-    int n = N, m = M;
-    if (lens) {
-        n = min(max(lens[2 * b], 0), N);
-        m = min(max(lens[2 * b + 1], 0), M);
-    }
-    const size_t base = (size_t)b * N * M;
-    double a = 0.0;
-    int c = 0;
-    const int q4 = (m + 3) >> 2;            // groups of four columns per row
-    const int total = n * q4;
-    const bool vec = vec4 != 0;   // (the host checked M % 4 == 0 and the pointers' alignment)
-    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
-        const int i = idx / q4, j = (idx - i * q4) << 2;
-        const size_t o = base + (size_t)i * M + j;
-        float g[4], r[4], y[4];
-        if (vec && j + 4 <= m) {
-            const float4 g4 = *reinterpret_cast<const float4 *>(G + o), r4 = *reinterpret_cast<const float4 *>(ref + o),
-                         y4 = *reinterpret_cast<const float4 *>(pred + o);
-            g[0] = g4.x, g[1] = g4.y, g[2] = g4.z, g[3] = g4.w;
-            r[0] = r4.x, r[1] = r4.y, r[2] = r4.z, r[3] = r4.w;
-            y[0] = y4.x, y[1] = y4.y, y[2] = y4.z, y[3] = y4.w;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const bool in = j + e < m;
-                g[e] = in ? G[o + e] : 0.f;
-                r[e] = in ? ref[o + e] : 0.f;
-                y[e] = in ? pred[o + e] : 0.5f;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (g[e] != 0.f) {
-                a += sdp::loss_term(r[e], y[e], kind);
-                ++c;
-            }
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_down(a, off);
-        c += __shfl_down(c, off);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) s_acc[w] = a, s_cnt[w] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double ta = 0.0;
-        int tc = 0;
-        for (int k = 0; k < (int)(blockDim.x >> 6); ++k) ta += s_acc[k], tc += s_cnt[k];
-        acc[b] = ta;
-        cnt[b] = tc;
-    }
-}
-
-// grid (x, B): the workgroups of a pair stride over groups of four columns of the FULL padded matrix (grad is written
-// in full: zero outside the pair's block and where G is 0); `vec4` as in the forward, with grad's alignment too
-extern "C" __global__ void __launch_bounds__(256) sdp_loss_bwd_kernel(const float *ref, const float *pred, const float *G,
-                                                                      const int *lens, const float *scale, float *grad, int N,
-                                                                      int M, int kind, int vec4)
-{
-    const int b = blockIdx.y;
-    int n = N, m = M;
-    if (lens) {
-        n = min(max(lens[2 * b], 0), N);
-        m = min(max(lens[2 * b + 1], 0), M);
-    }
-    const float sc = scale[b];
-    const size_t base = (size_t)b * N * M;
-    const int q4 = (M + 3) >> 2;
-    const int total = N * q4;
-    const bool vec = vec4 != 0;   // (the host checked M % 4 == 0 and the pointers' alignment)
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-        const int i = idx / q4, j = (idx - i * q4) << 2;
-        const size_t o = base + (size_t)i * M + j;
-        float out[4] = {0.f, 0.f, 0.f, 0.f};
-        if (i < n && j < m) {
-            float g[4], r[4], y[4];
-            if (vec) {   // j + 4 <= M: the group lies inside the row (cells at or beyond m are masked below)
-                const float4 g4 = *reinterpret_cast<const float4 *>(G + o), r4 = *reinterpret_cast<const float4 *>(ref + o),
-                             y4 = *reinterpret_cast<const float4 *>(pred + o);
-                g[0] = g4.x, g[1] = g4.y, g[2] = g4.z, g[3] = g4.w;
-                r[0] = r4.x, r[1] = r4.y, r[2] = r4.z, r[3] = r4.w;
-                y[0] = y4.x, y[1] = y4.y, y[2] = y4.z, y[3] = y4.w;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const bool in = j + e < m;
-                    g[e] = in ? G[o + e] : 0.f;
-                    r[e] = in ? ref[o + e] : 0.f;
-                    y[e] = in ? pred[o + e] : 0.5f;
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (j + e < m && g[e] != 0.f) out[e] = sdp::loss_dterm(r[e], y[e], sc, kind);
-        }
-        if (vec) {
-            *reinterpret_cast<float4 *>(grad + o) = make_float4(out[0], out[1], out[2], out[3]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (j + e < M) grad[o + e] = out[e];
-        }
-    }
-}
-
-// ----------------------------------------------------------------------------------
-// device self-test of the cross-lane semantics the sweep relies on
-// ----------------------------------------------------------------------------------
-extern "C" __global__ void sdp_selftest_kernel(int *out)
-{
-    const int lane = threadIdx.x;
-    const double v = 100.0 + lane;
-    const double shr = sdp::dpp_f64<sdp::DPP_WAVE_SHR1>(-1.0, v);
-    const double shl = sdp::dpp_f64<sdp::DPP_WAVE_SHL1>(-2.0, v);
-    const double rol = sdp::dpp_f64<sdp::DPP_WAVE_ROL1>(-3.0, v);
-    const double ror = sdp::dpp_f64<sdp::DPP_WAVE_ROR1>(-4.0, v);
-    int bad = 0;
-    bad |= (shr != (lane == 0 ? -1.0 : 100.0 + lane - 1)) ? 1 : 0;
-    bad |= (shl != (lane == 63 ? -2.0 : 100.0 + lane + 1)) ? 2 : 0;
-    bad |= (rol != 100.0 + ((lane + 1) & 63)) ? 4 : 0;
-    bad |= (ror != 100.0 + ((lane + 63) & 63)) ? 8 : 0;
-    // buffer addressing: out-of-range load returns 0, out-of-range store is dropped
-    __amdgpu_buffer_rsrc_t r = sdp::make_rsrc(out + 64, 64 * 4);
-    const unsigned oob = __builtin_amdgcn_raw_buffer_load_b32(r, sdp::OOB, 0, 0);
-    const unsigned neg = __builtin_amdgcn_raw_buffer_load_b32(r, (unsigned)(-4 * (lane + 1)), 0, 0);
-    const unsigned past = __builtin_amdgcn_raw_buffer_load_b32(r, 64 * 4 + lane * 4, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b32(0xdeadu, r, sdp::OOB, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b32(0xdeadu, r, 64 * 4 + lane * 4, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b32(1000u + lane, r, lane * 4, 0, 0);
-    bad |= (oob != 0u) ? 16 : 0;
-    bad |= (neg != 0u) ? 32 : 0;
-    bad |= (past != 0u) ? 64 : 0;
-    out[lane] = bad;
-    // informational (sdp_probe): is the scalar offset part of the range check?  Read the word right
-    // after the buffer through soffset; 0 = checked (out of range), 7777 = not checked.
-    const unsigned via_s = __builtin_amdgcn_raw_buffer_load_b32(r, lane * 4, 64 * 4, 0);
-    out[192 + lane] = (int)via_s;
-}
-#endif  // SDP_IN_GROUP(0)

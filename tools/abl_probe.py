@@ -1,5 +1,5 @@
 """Time decomposition of the sweeps: every library under build_variants/ (built with -DSDP_EXPERIMENTS and some
--DSDP_ABL=mask, see sdp_kernels.hip) at B=256 512x512, with real traffic and with all pairs aliased to pair 0
+-DSDP_ABL=mask, see sdp_device.h) at B=256 512x512, with real traffic and with all pairs aliased to pair 0
 (cache-served).  usage: python tools/abl_probe.py [BxNxM]"""
 import glob, os, sys
 import numpy as np

@@ -8,8 +8,10 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = ["deepblast_amd/csrc/sdp_kernels.hip", "deepblast_amd/csrc/sdp_kernels.h", "deepblast_amd/csrc/sdp_builds.def", "deepblast_amd/csrc/sdp_api.hip", "deepblast_amd/csrc/sdp_comm.hip",
-         "deepblast_amd/csrc/sdp_ref.hip", "include/sdp.h"]
+sys.path.insert(0, ROOT)
+from deepblast_amd import build  # noqa: E402  (paths only: importing it compiles nothing)
+
+FILES = [os.path.relpath(f, ROOT).replace(os.sep, "/") for f in build.SRC + build.HDR]   # every source and header of the library, in build.py's order
 
 
 def source_sha():
@@ -17,15 +19,10 @@ def source_sha():
     for f in FILES:
         with open(os.path.join(ROOT, f), "rb") as fh:
             h.update(f.encode() + b"\0" + fh.read())
-    extra = os.path.join(ROOT, "deepblast_amd/csrc/sdp_scores.hip")
-    if os.path.exists(extra):
-        with open(extra, "rb") as fh:
-            h.update(b"deepblast_amd/csrc/sdp_scores.hip\0" + fh.read())
     return h.hexdigest()
 
 
 def plan_ids(B=256, N=512, M=512, cus=256):
-    sys.path.insert(0, ROOT)
     from deepblast_amd import _lib
     lib = _lib.load()
     out = {}
