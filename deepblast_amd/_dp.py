@@ -247,6 +247,67 @@ def make_hard_functions(variant, prefix):
     return HardFunction, HardFunctionBackward
 
 
+def make_hard_local_functions(variant, prefix):
+    """The Function pair of a LOCAL 'hardmax' decoder (Decoder(..., local=True); include/sdp.h: sdp_hard_local_*): the shape of
+    make_hard_functions' pair with the zero floor in the recurrence,
+
+        V[i,j] = max(0, theta[i,j] + max(A[i,j] + V[i-1,j], V[i-1,j-1], A[i,j] + V[i,j-1])),   Vt = max over cells of V[i,j]
+
+    E is Et on the best segment pair's path -- from the cell after the last floored one to the first cell that holds Vt -- and
+    +0 elsewhere; a pair without a positive cell has Vt = 0 and an all-zero E.  The conventions for A, the second order and
+    gap_gradient are the global pair's; ymx likewise."""
+
+    class HardLocalFunctionBackward(torch.autograd.Function):
+
+        @staticmethod
+        def forward(ctx, theta, A, Et, P, ends, operator, lens=None, ymx=False, gap_gradient=False):
+            eng = _engine.get_engine()
+            if Et.device != theta.device:
+                raise ValueError(f"Et is on {Et.device}, expected {theta.device}")
+            E, states, counts = eng.hard_local_walk(P, ends, tuple(theta.shape), variant, lens, Et=Et.detach(), ymx=ymx)
+            if gap_gradient:
+                A = _path_gaps(states, counts, Et, tuple(theta.shape))
+            ctx.gap_gradient = gap_gradient
+            ctx.save_for_backward(states, counts)
+            ctx.set_materialize_grads(False)
+            return E, A
+
+        @staticmethod
+        def backward(ctx, Ztheta, ZA):
+            states, counts = ctx.saved_tensors
+            if Ztheta is None and ZA is None:
+                return (None,) * 9
+            ref = Ztheta if Ztheta is not None else ZA
+            Vtd = torch.zeros(states.shape[0], dtype=ref.dtype, device=ref.device)
+            if Ztheta is not None:
+                Vtd = Vtd + _path_sum(states, counts, Ztheta)
+            if ZA is not None:
+                Vtd = Vtd + _path_sum(states, counts, ZA, only_gaps=True)
+            return torch.zeros_like(ref), torch.zeros_like(ref) if ctx.gap_gradient else None, Vtd, None, None, None, None, None, None
+
+    class HardLocalFunction(torch.autograd.Function):
+
+        @staticmethod
+        def forward(ctx, theta, A, operator, lens=None, ymx=False, gap_gradient=False):
+            _validate(theta, A, operator, False)
+            eng = _engine.get_engine()
+            Vt, P, ends = eng.hard_local_forward(theta.detach(), A.detach(), variant, lens, ymx=ymx)
+            ctx.save_for_backward(theta, A, P, ends)
+            ctx.others = (operator, lens, ymx, gap_gradient)
+            return Vt
+
+        @staticmethod
+        def backward(ctx, Et):
+            theta, A, P, ends = ctx.saved_tensors
+            operator, lens, ymx, gap_gradient = ctx.others
+            E, A = HardLocalFunctionBackward.apply(theta, A, Et, P, ends, operator, lens, ymx, *((True,) if gap_gradient else ()))
+            return E, A, None, None, None, None
+
+    HardLocalFunction.__name__ = HardLocalFunction.__qualname__ = prefix + "HardLocalFunction"
+    HardLocalFunctionBackward.__name__ = HardLocalFunctionBackward.__qualname__ = prefix + "HardLocalFunctionBackward"
+    return HardLocalFunction, HardLocalFunctionBackward
+
+
 def traceback(grad, rule="cpu"):
     """Greedy arg-max walk over one (N, M) expected-alignment matrix -> [(i, j, state)].
 
@@ -302,10 +363,11 @@ class _Decoder(nn.Module):
 
     _function = None
     _hard_function = None          # the pair's Function for operator='hardmax' (make_hard_functions)
+    _hard_local_function = None    # ... and for a local 'hardmax' decoder (make_hard_local_functions)
     _variant = None                # SDP_NW / SDP_SW, for the calls that go to the engine without an autograd Function (score)
     _allow_none_operator = False
 
-    def __init__(self, operator, traceback_rule="cpu", arithmetic="fast", gap_gradient=False):
+    def __init__(self, operator, traceback_rule="cpu", arithmetic="fast", gap_gradient=False, local=False):
         """traceback_rule (extension): "cpu" = the walk of the reference's CPU decoders (nw.py:401-444, the parity
         oracle), "cuda" = the walk of its GPU decoders (nw_cuda.py:273-317), for callers that switch over from those.
         arithmetic (extension): "fast" = the tuned sweeps (fp32 exp-domain forward, float64 products in the second-order
@@ -328,8 +390,17 @@ class _Decoder(nn.Module):
         its forward skips), so Ed differs between the two on that border and wherever the border's tangent reaches.  Both are one
         elementwise pass over the state the sweeps left (include/sdp.h: sdp_gap_gradient*); the sweeps and their results are the
         same bits either way.  Gd carries no graph (no third order).  operator='hardmax': G is Et on the x and y cells of the one
-        optimal path and +0 elsewhere, and the second-order gradients are zeros."""
+        optimal path and +0 elsewhere, and the second-order gradients are zeros.
+        local (extension; operator='hardmax' only): True = LOCAL alignment, the classical Smith-Waterman optimum -- the recurrence
+        with a zero floor, V[i,j] = max(0, theta[i,j] + max(...)), Vt the best cell of the table instead of its corner (include/sdp.h:
+        sdp_hard_local_*).  forward / decode / score then give the best-scoring segment pair: E is Et on its path and +0 elsewhere
+        (all zero when no cell is positive), score(..., return_ends=True) adds the end cells, optimal_paths the path without padding
+        and its start cell.  theta must be able to go negative for anything to floor: with theta >= 0 (what
+        scores.alignment_scores produces) the result is the free-end-gaps optimum.  A soft (differentiable) local operator is
+        not built: any other operator raises NotImplementedError."""
         super().__init__()
+        if local and operator != 'hardmax':
+            raise NotImplementedError(f"local=True needs operator='hardmax': a soft local operator is not built (got operator={operator!r})")
         if traceback_rule not in ("cpu", "cuda"):
             raise ValueError(f"traceback_rule must be 'cpu' or 'cuda', got {traceback_rule!r}")
         if arithmetic not in ("fast", "reference"):
@@ -338,6 +409,7 @@ class _Decoder(nn.Module):
         self.traceback_rule = traceback_rule
         self.arithmetic = arithmetic
         self.gap_gradient = bool(gap_gradient)
+        self.local = bool(local)
 
     def forward(self, theta, A, lengths=None, fill=True):
         """theta, A: (B, N, M) fp32 on a ROCm device -> Vt (B,) on the same device.
@@ -359,6 +431,8 @@ class _Decoder(nn.Module):
         theta, A, lengths, transposed = self._oriented(theta, A, lengths)
         if self.operator == 'hardmax':
             # the transposed route carries the tie-order flag, so that the path does not depend on the way a problem is swept
+            if self.local:
+                return self._hard_local_function.apply(theta, A, self.operator, lengths, transposed, *((True,) if self.gap_gradient else ()))
             return self._hard_function.apply(theta, A, self.operator, lengths, transposed, *((True,) if self.gap_gradient else ()))
         reference = self.arithmetic == "reference"
         exact_state = _engine.REF if reference else for_decode
@@ -372,19 +446,28 @@ class _Decoder(nn.Module):
             args = () if lengths is None else (lengths,)
         return self._function.apply(theta, A, self.operator, *args)
 
-    def score(self, theta, A, lengths=None):
+    def score(self, theta, A, lengths=None, return_ends=False):
         """theta, A: (B, N, M) on a ROCm device -> Vt (B,), the alignment scores alone -- what the reference's
         NeuralAligner.score keeps of `self.ddp(theta, A)` under torch.no_grad() (alignment.py:127-137).  The result carries
         NO autograd graph, whatever the inputs require: use forward() to differentiate.  Same values as forward(); the sweep
         behind it (include/sdp.h: sdp_forward_value_f32) neither forms nor stores the state, so nothing but Vt (and, with
         `lengths`, a workspace of a few KB) is allocated -- forward() allocates and writes 5 bytes per cell.  `lengths` as in
         forward(); problems wider than the column limit are swept transposed.  arithmetic="reference" decoders run the
-        reference-rounding forward and drop its state (that mode has no fast path)."""
+        reference-rounding forward and drop its state (that mode has no fast path).
+        return_ends (local decoders only; ValueError on any other): -> (Vt, ends (B, 2) int32), the 0-based cell (i, j) each pair's
+        best local alignment ends in, (-1, -1) where no cell is positive."""
+        if return_ends and not self.local:
+            raise ValueError("return_ends=True needs a local decoder (Decoder('hardmax', local=True)): a global alignment ends in the corner")
         _validate(theta, A, self.operator, type(self)._allow_none_operator)
         theta, A, lengths, transposed = self._oriented(theta, A, lengths)
         eng = _engine.get_engine()
         with torch.no_grad():
             theta, A = theta.detach(), A.detach()
+            if self.local:
+                Vt, ends = eng.hard_local_forward_value(theta, A, self._variant, lengths, ymx=transposed, want_ends=bool(return_ends))
+                if not return_ends:
+                    return Vt
+                return Vt, (ends[:, [1, 0]].contiguous() if transposed else ends)
             if self.operator == 'hardmax':
                 return eng.hard_forward_value(theta, A, self._variant, lengths, ymx=transposed)
             if self.arithmetic == "reference":
@@ -410,26 +493,37 @@ class _Decoder(nn.Module):
             lengths = torch.stack([lengths[:, 1], lengths[:, 0]], dim=1)
         return theta.transpose(1, 2), A.transpose(1, 2), lengths, True
 
-    def optimal_paths(self, theta, A, lengths=None):
+    def optimal_paths(self, theta, A, lengths=None, local=None):
         """The optimal (hard-max) alignment of every pair under the scores given -> (Vt (B,), states (B, cap, 3) int32, counts
         (B,) int32), device tensors without an autograd graph: pair b's list is states[b, :counts[b]], rows (i, j, state) from
         (0, 0) on, in traceback()'s format (the path preceded by its padding).  Available on every decoder whatever its
         `operator`: it is the max-plus recurrence over theta and A.  No E is allocated: one sweep that stores 2 bits per cell,
-        one walk per pair."""
+        one walk per pair.
+        local (None: the decoder's own `local`): True = the best LOCAL alignment of every pair (see __init__), on every decoder
+        likewise.  The list is then the path alone, start first, without padding -- the flanks are unaligned, not gaps -- and
+        empty (counts[b] = 0, Vt[b] = 0) for a pair without a positive cell; states[b, cap - 1] is (number of path cells, i, j of
+        the first one): the alignment's (query_start, hit_start), (0, -1, -1) for an empty one; its last row is the end cell."""
         _validate(theta, A, 'hardmax', False)
         theta, A, lengths, transposed = self._oriented(theta, A, lengths)
         eng = _engine.get_engine()
         with torch.no_grad():
             theta, A = theta.detach(), A.detach()
-            Vt, P = eng.hard_forward(theta, A, self._variant, lengths, ymx=transposed)
-            _, states, counts = eng.hard_walk(P, tuple(theta.shape), self._variant, lengths, ymx=transposed, want_E=False)
+            if self.local if local is None else local:
+                Vt, P, ends = eng.hard_local_forward(theta, A, self._variant, lengths, ymx=transposed)
+                _, states, counts = eng.hard_local_walk(P, ends, tuple(theta.shape), self._variant, lengths, ymx=transposed, want_E=False)
+            else:
+                Vt, P = eng.hard_forward(theta, A, self._variant, lengths, ymx=transposed)
+                _, states, counts = eng.hard_walk(P, tuple(theta.shape), self._variant, lengths, ymx=transposed, want_E=False)
             if transposed:
+                scratch = states[:, -1]
                 states = states[..., [1, 0, 2]].contiguous()
+                if self.local if local is None else local:
+                    states[:, -1] = scratch[:, [0, 2, 1]]     # (number of path cells, first i, first j): the count stays in front
         return Vt, states, counts
 
-    def optimal_alignments(self, theta, A, lengths=None):
+    def optimal_alignments(self, theta, A, lengths=None, local=None):
         """optimal_paths() as traceback_batch() returns its walks: (Vt, list of B lists of (i, j, state))."""
-        Vt, states, counts = self.optimal_paths(theta, A, lengths)
+        Vt, states, counts = self.optimal_paths(theta, A, lengths, local)
         states, counts = states.cpu().numpy(), counts.cpu().numpy()
         return Vt, [[tuple(int(v) for v in row) for row in states[b, :counts[b]]] for b in range(len(counts))]
 

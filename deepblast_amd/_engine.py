@@ -436,6 +436,64 @@ class HipEngine:
                   self._hard_variant(variant, ymx, waves=False))
         return E, states, counts
 
+    # ---- local alignment on the hard-max family (include/sdp.h: sdp_hard_local_*) ----------
+    def hard_local_forward(self, theta, A, variant, lens=None, ymx=False):
+        """-> (Vt (B,), state, ends (B, 2) int32): the max-plus sweep with the zero floor -- Vt the best cell, ends its 0-based
+        (i, j), (-1, -1) where no cell is positive -- and its 2-bit pointers (code 3: an alignment starts after this cell).
+        ymx: theta and A are a TRANSPOSED problem; ends come back in the coordinates handed over."""
+        dev = self.device_of(theta)
+        check_args(theta, torch.float32, theta=theta, A=A)
+        theta, A = theta.contiguous(), A.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        nbytes = self.lib.sdp_hard_state_bytes(B, N, M)
+        state = torch.empty(max(nbytes, 4) // 4, dtype=torch.int32, device=theta.device)
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        ends = torch.empty((B, 2), dtype=torch.int32, device=theta.device)
+        self.call("sdp_hard_local_forward_f32", HARD_LOCAL_KERNELS[111 if ymx else 110], dev, theta, A, state, Vt, ends, B, N, M, lens,
+                  self._hard_variant(variant, ymx))
+        return Vt, state, ends
+
+    def hard_local_forward_value(self, theta, A, variant, lens=None, ymx=False, want_ends=True):
+        """-> (Vt (B,), ends (B, 2) int32 or None): the same sweep with the pointers compiled out (the same bits)."""
+        dev = self.device_of(theta)
+        check_args(theta, torch.float32, theta=theta, A=A)
+        theta, A = theta.contiguous(), A.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        ends = torch.empty((B, 2), dtype=torch.int32, device=theta.device) if want_ends else None
+        self.call("sdp_hard_local_forward_value_f32", HARD_LOCAL_KERNELS[113 if ymx else 112], dev, theta, A, Vt, ends, B, N, M, lens,
+                  self._hard_variant(variant, ymx))
+        return Vt, ends
+
+    def hard_local_walk(self, state, ends, shape, variant, lens=None, Et=None, ymx=False, want_E=True, want_states=True, E_out=None,
+                        states_out=None):
+        """The walk along the pointers of hard_local_forward, from `ends` -> (E (B,N,M) or None, states (B,cap,3) int32 or None,
+        counts (B,) or None).  E: Et[b] on pair b's path, +0 on every other cell of its plane; states / counts: the path alone
+        (no padding), start first; row cap - 1 of states: (number of path cells, i and j of its first cell) -- the alignment's
+        start offsets.  E_out / states_out: buffers to write into instead of fresh ones."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        lens = self._lens(lens, B, state.device)
+        check_args(state, torch.int32, (B, 2), True, ValueError, ends=ends)
+        E = states = counts = None
+        if want_E:
+            if Et is None:
+                raise ValueError("hard_local_walk: E needs Et")
+            check_args(state, Et=Et)
+            Et = Et.detach().to(torch.float32).expand(B).contiguous()
+            check_args(state, torch.float32, (B, N, M), True, ValueError, E_out=E_out)
+            E = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if E_out is None else E_out
+        if want_states:
+            cap = self.lib.sdp_traceback_capacity(N, M)
+            check_args(state, torch.int32, (B, cap, 3), True, ValueError, states_out=states_out)
+            states = torch.empty((B, cap, 3), dtype=torch.int32, device=state.device) if states_out is None else states_out
+            counts = torch.empty(B, dtype=torch.int32, device=state.device)
+        self.call("sdp_hard_local_walk_f32", HARD_LOCAL_KERNELS[114], dev, state, ends, Et if want_E else None, E, states, counts,
+                  B, N, M, lens, self._hard_variant(variant, ymx, waves=False))
+        return E, states, counts
+
     def alignment_targets(self, codes, code_lens, lens, shape, dm, P, G, flags, status):
         """Enqueue sdp_alignment_targets on the current stream (include/sdp.h): codes (B, L) uint8, code_lens (B,) int32,
         lens (B, 2) int32 or None; dm / P fp32, G bool or fp32 (flags), each (B, N, M) or None; status (B,) int32."""
@@ -478,6 +536,10 @@ class HipEngine:
     def selftest(self, device=0):
         _lib.check(self.lib.sdp_selftest(device), "sdp_selftest")
 
+
+# kernel id (csrc/sdp_hard.h; what sdp_kernel_name answers for) -> symbol of the local-alignment kernels: the launch labels
+HARD_LOCAL_KERNELS = {110: "sdp_hard_local_fwd_kernel", 111: "sdp_hard_local_fwd_t_kernel", 112: "sdp_hard_local_val_kernel",
+                      113: "sdp_hard_local_val_t_kernel", 114: "sdp_hard_local_walk_kernel"}
 
 _SWEEPS = ("sdp_forward", "sdp_backward", "sdp_adjoint_forward", "sdp_adjoint_backward")
 # dtype -> (suffix of the four sweeps' entries, their launch labels (float32: where the library's plan is not asked),

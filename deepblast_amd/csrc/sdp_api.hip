@@ -651,6 +651,12 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_gap::ID_GAP2_ROWS: return "sdp_gap2_rows_kernel";
     case sdp_gap::ID_GAP_ROWS_F64: return "sdp_gap_rows_f64_kernel";
     case sdp_gap::ID_GAP2_ROWS_F64: return "sdp_gap2_rows_f64_kernel";
+    // the local-alignment kernels of the hard-max family (csrc/sdp_hard.hip)
+    case sdp_hard::ID_LOCAL_FWD: return "sdp_hard_local_fwd_kernel";
+    case sdp_hard::ID_LOCAL_FWD_T: return "sdp_hard_local_fwd_t_kernel";
+    case sdp_hard::ID_LOCAL_VAL: return "sdp_hard_local_val_kernel";
+    case sdp_hard::ID_LOCAL_VAL_T: return "sdp_hard_local_val_t_kernel";
+    case sdp_hard::ID_LOCAL_WALK: return "sdp_hard_local_walk_kernel";
     }
     return nullptr;
 }
@@ -1332,6 +1338,57 @@ int sdp_hard_walk_f32(const void *state, const float *Et, float *E, int32_t *sta
                        ymx ? 1 : 0);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "sdp_hard_walk_kernel");
+    return 0;
+}
+
+// ---- local alignment on the hard-max family: the zero floor, Vt = the best cell, ends = the first cell that holds it ----
+static int hard_local_forward(const float *theta, const float *A, void *state, float *Vt, int32_t *ends, int B, int N, int M,
+                              const int32_t *lens, int variant, int device, void *stream, bool pointers)
+{
+    bool ymx;
+    int waves, lo;
+    if (int rc = hard_variant(variant, B, N, M, ymx, waves, lo)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    const int W = hard_waves(waves, N, M);
+    auto kernel = pointers ? (ymx ? sdp_hard_local_fwd_t_kernel : sdp_hard_local_fwd_kernel)
+                           : (ymx ? sdp_hard_local_val_t_kernel : sdp_hard_local_val_kernel);
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(64 * W), sdp_hard::forward_lds_bytes(W, M), (hipStream_t)stream, theta, A,
+                       static_cast<uint32_t *>(state), Vt, ends, lens, N, M, lo, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, pointers ? "sdp_hard_local_fwd_kernel" : "sdp_hard_local_val_kernel");
+    return 0;
+}
+
+int sdp_hard_local_forward_f32(const float *theta, const float *A, void *state, float *Vt, int32_t *ends, int B, int N, int M,
+                               const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!theta || !A || !state || !Vt || !ends) return fail(SDP_E_NULLPTR, "sdp_hard_local_forward_f32: null pointer");
+    return hard_local_forward(theta, A, state, Vt, ends, B, N, M, lens, variant, device, stream, true);
+}
+
+int sdp_hard_local_forward_value_f32(const float *theta, const float *A, float *Vt, int32_t *ends, int B, int N, int M,
+                                     const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!theta || !A || !Vt) return fail(SDP_E_NULLPTR, "sdp_hard_local_forward_value_f32: null pointer");
+    return hard_local_forward(theta, A, nullptr, Vt, ends, B, N, M, lens, variant, device, stream, false);
+}
+
+int sdp_hard_local_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, int32_t *states, int32_t *counts,
+                            int B, int N, int M, const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!state || !ends || (!E && !states) || (E && !Et) || (states && !counts))
+        return fail(SDP_E_NULLPTR, "sdp_hard_local_walk_f32: null pointer (state, ends; E with Et, or states with counts, or both)");
+    bool ymx;
+    int waves, lo;
+    if (int rc = hard_variant(variant, B, N, M, ymx, waves, lo)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    hipLaunchKernelGGL(sdp_hard_local_walk_kernel, dim3(B), dim3(64), sdp_hard::walk_lds_bytes(M), (hipStream_t)stream,
+                       static_cast<const uint32_t *>(state), ends, Et, E, states, counts, lens, N, M, lo, sdp_traceback_capacity(N, M),
+                       ymx ? 1 : 0);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "sdp_hard_local_walk_kernel");
     return 0;
 }
 

@@ -24,6 +24,10 @@ __host__ __device__ inline int row_pitch(int M) { return M + STRIP; }   // float
 __host__ __device__ inline size_t forward_lds_bytes(int waves, int M) { return (size_t)waves * row_pitch(M) * 4 + 2 * MAX_WAVES * 4; }
 __host__ __device__ inline size_t walk_lds_bytes(int M) { return (size_t)words(M) * STRIP * 4; }
 
+// kernel ids sdp_kernel_name answers for the local-alignment kernels (the sweeps' builds keep the numbers below 80, the
+// gap-gradient kernels 100-105)
+enum { ID_LOCAL_FWD = 110, ID_LOCAL_FWD_T = 111, ID_LOCAL_VAL = 112, ID_LOCAL_VAL_T = 113, ID_LOCAL_WALK = 114 };
+
 }  // namespace sdp_hard
 
 extern "C" {
@@ -37,6 +41,17 @@ __global__ void sdp_hard_val_t_kernel(const float *theta, const float *A, uint32
                                       int lo, int waves);
 __global__ void sdp_hard_walk_kernel(const uint32_t *state, const float *Et, float *E, int *states, int *counts, const int *lens,
                                      int N, int M, int lo, int cap, int ymx);
+// local alignment: the zero floor, pointer code 3, Vt = the best cell, ends = the first cell that holds it
+__global__ void sdp_hard_local_fwd_kernel(const float *theta, const float *A, uint32_t *state, float *Vt, int *ends, const int *lens,
+                                          int N, int M, int lo, int waves);
+__global__ void sdp_hard_local_fwd_t_kernel(const float *theta, const float *A, uint32_t *state, float *Vt, int *ends, const int *lens,
+                                            int N, int M, int lo, int waves);
+__global__ void sdp_hard_local_val_kernel(const float *theta, const float *A, uint32_t *state, float *Vt, int *ends, const int *lens,
+                                          int N, int M, int lo, int waves);
+__global__ void sdp_hard_local_val_t_kernel(const float *theta, const float *A, uint32_t *state, float *Vt, int *ends, const int *lens,
+                                            int N, int M, int lo, int waves);
+__global__ void sdp_hard_local_walk_kernel(const uint32_t *state, const int *ends, const float *Et, float *E, int *states, int *counts,
+                                           const int *lens, int N, int M, int lo, int cap, int ymx);
 }
 
 #endif  // SDP_HARD_H_

@@ -9,9 +9,11 @@ from ._engine import NW
 
 NeedlemanWunschFunction, NeedlemanWunschFunctionBackward = _dp.make_functions(NW, "NeedlemanWunsch")
 NeedlemanWunschHardFunction, NeedlemanWunschHardFunctionBackward = _dp.make_hard_functions(NW, "NeedlemanWunsch")
+NeedlemanWunschHardLocalFunction, NeedlemanWunschHardLocalFunctionBackward = _dp.make_hard_local_functions(NW, "NeedlemanWunsch")
 
 
 class NeedlemanWunschDecoder(_dp._Decoder):
     _function = NeedlemanWunschFunction
     _hard_function = NeedlemanWunschHardFunction
+    _hard_local_function = NeedlemanWunschHardLocalFunction
     _variant = NW

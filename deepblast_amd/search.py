@@ -21,7 +21,11 @@ indices / values (k,): the top-k targets by `normalized`, best first (None witho
 def search_scores(decoder, zq, gq, zdb, gdb, db_lengths, query_length=None, chunk=256, topk=None):
     """One query against a padded database -> SearchResult.
 
-    decoder       a NeedlemanWunschDecoder / SmithWatermanDecoder (its `score` is the value-only sweep).
+    decoder       a NeedlemanWunschDecoder / SmithWatermanDecoder (its `score` is the value-only sweep).  A LOCAL decoder
+                  (Decoder('hardmax', local=True)) gives local scores: the best cell of the max-plus table with a zero floor.
+                  alignment_scores produces theta = softplus(.) >= 0, and with theta >= 0 nothing ever floors -- the result is
+                  then the free-end-gaps optimum; for true locality shift theta by a threshold of your choosing (a decoder
+                  wrapper whose score() subtracts it).
     zq, gq        (N, D) match / gap embeddings of the query.
     zdb, gdb      (T, Mmax, D) match / gap embeddings of the T targets, zero padded behind each target's length.
     db_lengths    (T,) int: residues per target (1 .. Mmax).

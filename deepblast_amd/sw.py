@@ -12,10 +12,12 @@ from ._engine import SW
 SmithWatermanFunction, SmithWatermanFunctionBackward = _dp.make_functions(SW, "SmithWaterman",
                                                                           allow_none_operator=True)
 SmithWatermanHardFunction, SmithWatermanHardFunctionBackward = _dp.make_hard_functions(SW, "SmithWaterman")
+SmithWatermanHardLocalFunction, SmithWatermanHardLocalFunctionBackward = _dp.make_hard_local_functions(SW, "SmithWaterman")
 
 
 class SmithWatermanDecoder(_dp._Decoder):
     _function = SmithWatermanFunction
     _hard_function = SmithWatermanHardFunction
+    _hard_local_function = SmithWatermanHardLocalFunction
     _variant = SW
     _allow_none_operator = True

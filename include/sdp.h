@@ -394,6 +394,43 @@ int sdp_hard_forward_value_f32(const float *theta, const float *A, float *Vt, in
 int sdp_hard_walk_f32(const void *state, const float *Et, float *E, int32_t *states, int32_t *counts, int B, int N, int M,
                       const int32_t *lens, int variant, int device, void *stream);
 
+/* LOCAL alignment on the hard-max family: the best-scoring SEGMENT pair instead of the corner-to-corner optimum --
+ * the recurrence above with a zero floor.  (Added after SDP_VERSION 106 without a version change: look the symbols up.  The soft
+ * sweeps have no local form.)  With (n, m) = lens[b] or (N, M), lo = 1 (SDP_NW) or 2 (SDP_SW), V (n+1) x (m+1) all zero, 1-based,
+ * every '+' one rounded fp32 addition:
+ *     for i in lo..n, j in lo..m (row-major):
+ *         a = A[i-1,j-1]
+ *         c = (a + V[i-1,j],  V[i-1,j-1],  a + V[i,j-1])                 states x, m, y
+ *         k = the FIRST maximum of c in the order x, m, y (strict '>')
+ *         v = theta[i-1,j-1] + c[k]
+ *         if v > 0:  V[i,j] = v,  P[i,j] = k
+ *         else:      V[i,j] = +0, P[i,j] = 3                             (no alignment passes through this cell)
+ *     Vt  = the maximum over all cells of V[i,j]                         (+0 when no cell is positive or none exists)
+ *     end = the FIRST cell in row-major order that holds Vt, if Vt > 0; else none
+ *     path: from end, while i >= lo and j >= lo and P[i,j] != 3: record (i-1, j-1, P[i,j]), step to the predecessor
+ * -inf in A is legal, NaN unspecified.  The results are the bits of that loop.
+ *   ends     (B, 2) int32 DEVICE: the 0-based end cell (i, j) of each pair, (-1, -1) where there is none.  Written by the two
+ *            forward entries (sdp_hard_local_forward_value_f32: may be NULL), read by the walk.
+ *   state    sdp_hard_state_bytes(B, N, M) bytes, the format of sdp_hard_forward_f32 with the pointer code 3 in use.
+ *   variant  as for sdp_hard_*: SDP_NW / SDP_SW | SDP_HARD_TIES_YMX | SDP_WAVES(w); anything else: SDP_E_VARIANT.
+ *            SDP_HARD_TIES_YMX (a problem handed over TRANSPOSED): c is scanned y, m, x, and the first maximum over cells is taken
+ *            in the order the ORIGINAL problem's row-major scan visits them -- column-major in the coordinates handed over -- so
+ *            that Vt, the end and the path do not depend on which way a problem was swept; `ends` and the (i, j) of the rows are in
+ *            the coordinates handed over (the caller swaps them back), the states are the original's.
+ * sdp_hard_local_walk_f32: one wavefront per pair, from ends[b].
+ *   E        (B, N, M) or NULL: the whole plane is written -- Et[b] on the path, +0 everywhere else.  Needs Et (B,).
+ *   states   (B, sdp_traceback_capacity(N, M), 3) int32 or NULL, counts (B,) int32: the path ALONE, start first, no padding (the
+ *            flanks of a local alignment are unaligned, not gaps): counts[b] rows.  The last row (no list reaches it) receives
+ *            (number of path cells, i and j of the path's first cell) -- the alignment's (query_start, hit_start) --, (0, -1, -1)
+ *            for a pair without a positive cell, which has counts[b] = 0 and an all-zero E.
+ * All arguments are checked before any device call; errors as for sdp_hard_*. */
+int sdp_hard_local_forward_f32(const float *theta, const float *A, void *state, float *Vt, int32_t *ends, int B, int N, int M,
+                               const int32_t *lens, int variant, int device, void *stream);
+int sdp_hard_local_forward_value_f32(const float *theta, const float *A, float *Vt, int32_t *ends, int B, int N, int M,
+                                     const int32_t *lens, int variant, int device, void *stream);
+int sdp_hard_local_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, int32_t *states, int32_t *counts,
+                            int B, int N, int M, const int32_t *lens, int variant, int device, void *stream);
+
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept
  * for callers who are short of memory, not of time; deepblast_amd.losses uses the unfused kernels by default.
@@ -489,7 +526,7 @@ int sdp_plan(int pass, int B, int N, int M, int has_lens, int exact_state, int c
 int sdp_plan_parts(int pass, int B, int N, int M, int has_lens, int exact_state, int cus);
 
 /* The symbol of the kernel build with that id (what rocprofv3 shows for its launches), or NULL if no build has the id.  (100-105:
- * the gap-gradient kernels, which are no builds of the sweep.) */
+ * the gap-gradient kernels, 110-114 the local-alignment kernels of the hard-max family, which are no builds of the sweep.) */
 const char *sdp_kernel_name(int kernel_id);
 
 #ifdef SDP_EXPERIMENTS
