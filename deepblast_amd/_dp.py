@@ -527,6 +527,57 @@ class _Decoder(nn.Module):
         states, counts = states.cpu().numpy(), counts.cpu().numpy()
         return Vt, [[tuple(int(v) for v in row) for row in states[b, :counts[b]]] for b in range(len(counts))]
 
+    def sample_paths(self, theta, A, num_samples, lengths=None, seed=0, sample0=0, return_visits=False):
+        """Alignments drawn from the POSTERIOR the soft-max operator defines -- the Gibbs distribution whose marginals are the
+        expected alignment matrix decode() returns and whose mode optimal_paths() finds -- by a stochastic traceback on the
+        state of one forward sweep (include/sdp.h: sdp_sample_paths_*; no backward sweep, no E).  -> (Vt (B,), states (B, K, cap,
+        3) int32, counts (B, K) int32[, visits (B, N, M) int32]), K = num_samples, device tensors without an autograd graph:
+        sample k of pair b is states[b, k, :counts[b, k]], rows (i, j, state) from (0, 0) on, in optimal_paths()' format (the
+        path preceded by its padding; rows between the list and the last one are unspecified); states[b, k, cap - 1] is (number
+        of path cells, i, j of the first one).  visits (return_visits=True): how many of the K paths pass through each cell --
+        visits / K estimates decode()'s matrix.  The draws are reproducible: sample k is sample number sample0 + k of pair b
+        under `seed` (a counter-based generator; 64 samples at sample0 = 0 are 32 at 0 followed by 32 at 32), and the same
+        whichever way the problem is swept (wider than the column limit: transposed).
+        The state is the decoder's own: packed for the default fp32 decoder, the reference's for arithmetic="reference", float64
+        for float64 tensors.  The samples are walks: states.reshape(B * K, cap, 3) and counts.reshape(B * K) feed
+        deepblast_amd.score.alignment_stats as predictions unchanged (against the true alignments repeated K times), which turns
+        validation_stats' point values into distributions.
+        operator != 'softmax' raises ValueError: the hard-max posterior is a point -- use optimal_paths()."""
+        if self.operator != 'softmax':
+            raise ValueError(f"sample_paths needs operator='softmax' (got {self.operator!r}): the hard-max posterior is a point, use optimal_paths()")
+        _validate(theta, A, self.operator, False)
+        K = int(num_samples)
+        if K < 1:
+            raise ValueError(f"num_samples must be positive, got {num_samples}")
+        theta, A, lengths, transposed = self._oriented(theta, A, lengths)
+        eng = _engine.get_engine()
+        with torch.no_grad():
+            theta, A = theta.detach(), A.detach()
+            exact_state = _engine.REF if (self.arithmetic == "reference" and theta.dtype == torch.float32) else False
+            Vt, Q = eng.forward(theta, A, self._variant, lengths, exact_state=exact_state)
+            states, counts, visits = eng.sample_paths(Q, tuple(theta.shape), self._variant, K, lengths, seed=seed, sample0=sample0,
+                                                      exact_state=exact_state, transposed=transposed, want_visits=bool(return_visits))
+            # the lists come right-aligned (every sample wrote from the end): one gather moves them to the front, the last row stays
+            cap = states.shape[2]
+            row = torch.arange(cap, device=states.device)[None, None, :]
+            cnt = counts.long()[..., None]
+            src = torch.where(row < cnt, row + (cap - 1 - cnt), torch.full_like(row, cap - 1))
+            states = torch.gather(states, 2, src[..., None].expand(-1, -1, -1, 3))
+            if transposed:
+                scratch = states[:, :, -1]
+                states = states[..., [1, 0, 2]].contiguous()
+                states[:, :, -1] = scratch[..., [0, 2, 1]]     # (number of path cells, first i, first j): the count stays in front
+                if visits is not None:
+                    visits = visits.transpose(1, 2).contiguous()
+        return (Vt, states, counts, visits) if return_visits else (Vt, states, counts)
+
+    def sample_alignments(self, theta, A, num_samples, lengths=None, seed=0, sample0=0):
+        """sample_paths() as optimal_alignments() returns its walks: (Vt, list of B lists of K lists of (i, j, state))."""
+        Vt, states, counts = self.sample_paths(theta, A, num_samples, lengths, seed, sample0)
+        states, counts = states.cpu().numpy(), counts.cpu().numpy()
+        return Vt, [[[tuple(int(v) for v in row) for row in states[b, k, :counts[b, k]]] for k in range(counts.shape[1])]
+                    for b in range(counts.shape[0])]
+
     def traceback(self, grad):
         return traceback(grad, self.traceback_rule)
 

@@ -494,6 +494,39 @@ class HipEngine:
                   B, N, M, lens, self._hard_variant(variant, ymx, waves=False))
         return E, states, counts
 
+    # ---- alignments sampled from the posterior (include/sdp.h: sdp_sample_paths_*) -------------------
+    def sample_paths(self, state, shape, variant, K, lens=None, seed=0, sample0=0, exact_state=False, transposed=False,
+                     want_states=True, want_visits=False):
+        """K stochastic tracebacks per pair on the `state` of forward() -> (states (B,K,cap,3) int32 or None, counts (B,K) int32 or
+        None, visits (B,N,M) int32 or None).  exact_state, lens: what forward() was given (a float64 state is known by its dtype).
+        Sample (b, k) is sample number sample0 + k of pair b under `seed` whatever K is; its list is RIGHT-aligned in
+        states[b, k] -- rows cap-1-counts[b,k] .. cap-2, start first -- and row cap-1 holds (number of path cells, i, j of the
+        first one).  visits: how many of the K paths pass through each cell.  transposed: the state is that of a transposed
+        problem (_Decoder._oriented); (i, j) stay in the state's coordinates."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        if not want_states and not want_visits:
+            raise ValueError("sample_paths: nothing asked for (want_states, want_visits)")
+        lens = self._lens(lens, B, state.device)
+        states = counts = visits = None
+        if want_states:
+            cap = self.lib.sdp_traceback_capacity(N, M)
+            states = torch.empty((B, int(K), cap, 3), dtype=torch.int32, device=state.device)
+            counts = torch.empty((B, int(K)), dtype=torch.int32, device=state.device)
+        if want_visits:
+            visits = torch.zeros((B, N, M), dtype=torch.int32, device=state.device)
+        flags = _lib.SDP_SAMPLE_TRANSPOSED if transposed else 0
+        seed = int(seed) & 0xffffffffffffffff
+        if _sweep_dtype(state) == torch.float64:
+            check_args(state, torch.float64, (B, N, M, 3), True, state=state)
+            self.call("sdp_sample_paths_f64", "sdp_sample_rows_f64_kernel", dev, state, states, counts, visits, B, N, M, int(K),
+                      int(sample0), seed, lens, variant | flags)
+        else:
+            flags |= self._state_flags(exact_state)
+            self.call("sdp_sample_paths_f32", "sdp_sample_rows_kernel" if exact_state == REF else "sdp_sample_kernel", dev,
+                      state, states, counts, visits, B, N, M, int(K), int(sample0), seed, lens, variant | flags)
+        return states, counts, visits
+
     def alignment_targets(self, codes, code_lens, lens, shape, dm, P, G, flags, status):
         """Enqueue sdp_alignment_targets on the current stream (include/sdp.h): codes (B, L) uint8, code_lens (B,) int32,
         lens (B, 2) int32 or None; dm / P fp32, G bool or fp32 (flags), each (B, N, M) or None; status (B,) int32."""

@@ -15,6 +15,7 @@ SDP_NO_ZERO_SKIP, SDP_NO_FILL = 0x800, 0x10000   # include/sdp.h: flags of the b
 SDP_TARGETS_GAP_MASK, SDP_TARGETS_G_F32 = 0x1, 0x2  # include/sdp.h: flags of sdp_alignment_targets
 SDP_SCORE_NO_GAPS, SDP_SCORE_PRED_WALK = 0x1, 0x2    # include/sdp.h: flags of sdp_alignment_stats
 SDP_HARD_TIES_YMX = 0x20000                          # include/sdp.h: flag of the sdp_hard_* entries (a transposed problem)
+SDP_SAMPLE_TRANSPOSED = 0x40000                      # include/sdp.h: flag of the sdp_sample_paths_* entries (likewise)
 
 _c_f32p = ctypes.c_void_p
 _c_i32p = ctypes.c_void_p
@@ -101,6 +102,11 @@ SIGNATURES = {
     "sdp_gap_gradient2_f32": (ctypes.c_int, [_c_f32p] * 5 + [ctypes.c_int] * 3 + [_c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "sdp_gap_gradient_f64": (ctypes.c_int, [_c_f32p] * 3 + [ctypes.c_int] * 3 + [_c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "sdp_gap_gradient2_f64": (ctypes.c_int, [_c_f32p] * 5 + [ctypes.c_int] * 3 + [_c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_sample_paths_f32": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, _c_i32p] + [ctypes.c_int] * 5 +
+                             [ctypes.c_uint64, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_sample_paths_f64": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, _c_i32p] + [ctypes.c_int] * 5 +
+                             [ctypes.c_uint64, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_sample_uniform": (ctypes.c_float, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "sdp_selftest": (ctypes.c_int, [ctypes.c_int]),
     "sdp_device_status": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
 }

@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "sdp_gap.h"
+#include "sdp_sample.h"
 #include "sdp_hard.h"
 #include "sdp_kernels.h"
 
@@ -657,6 +658,10 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_hard::ID_LOCAL_VAL: return "sdp_hard_local_val_kernel";
     case sdp_hard::ID_LOCAL_VAL_T: return "sdp_hard_local_val_t_kernel";
     case sdp_hard::ID_LOCAL_WALK: return "sdp_hard_local_walk_kernel";
+    // the sampling kernels (csrc/sdp_sample.hip)
+    case sdp_sample::ID_SAMPLE: return "sdp_sample_kernel";
+    case sdp_sample::ID_SAMPLE_ROWS: return "sdp_sample_rows_kernel";
+    case sdp_sample::ID_SAMPLE_ROWS_F64: return "sdp_sample_rows_f64_kernel";
     }
     return nullptr;
 }
@@ -1510,5 +1515,75 @@ int sdp_gap_gradient2_f64(const double *E, const double *Ed, const double *state
                        v == SDP_SW);
     return gap_launched("sdp_gap2_rows_f64_kernel");
 }
+
+// ---- alignments sampled from the posterior (csrc/sdp_sample.hip): a stochastic traceback on the forward sweep's state ----
+// Where a pair's records live, and in which form, is decided by the code the sweeps decide it with, as for the gap gradient.
+enum SampleState { SAMPLE_SKEWED, SAMPLE_ROWS, SAMPLE_ROWS_F64 };
+
+static int sample_paths(const char *who, SampleState kind, const void *state, int32_t *states, int32_t *counts, int32_t *visits, int B,
+                        int N, int M, int K, int sample0, uint64_t seed, const int32_t *lens, int variant, bool exact_flag, int device,
+                        void *stream)
+{
+    char msg[160];
+    if (!state || (!states && !visits) || (states && !counts)) {
+        snprintf(msg, sizeof(msg), "%s: null pointer (state; states with counts, or visits, or both)", who);
+        return fail(SDP_E_NULLPTR, msg);
+    }
+    const int transposed = (variant & SDP_SAMPLE_TRANSPOSED) ? 1 : 0;
+    const int v = variant & ~SDP_SAMPLE_TRANSPOSED;
+    if (int rc = check_shape(B, N, M, v)) return rc;
+    if (K < 1 || sample0 < 0 || (long long)sample0 + K > 0x7fffffffLL) {
+        snprintf(msg, sizeof(msg), "%s: K must be positive, sample0 non-negative and sample0 + K below 2^31", who);
+        return fail(SDP_E_SHAPE, msg);
+    }
+    const int cap = sdp_traceback_capacity(N, M);
+    const size_t lim = 0x7fffffffu, waves = (size_t)B * ((K + sdp_sample::LANES - 1) / sdp_sample::LANES);
+    if ((states && (size_t)B * K * cap * 3 > lim) || (size_t)B * K > lim || (visits && (size_t)B * N * M > lim) || waves > lim) {
+        snprintf(msg, sizeof(msg), "%s: an output exceeds 2^31 elements", who);
+        return fail(SDP_E_TOOBIG, msg);
+    }
+    if (int rc = gap_prepare(device)) return rc;
+    sdp_sample::Params g = {};
+    g.state = state, g.states = states, g.counts = counts, g.visits = visits, g.lens = lens, g.seed = seed;
+    g.B = B, g.N = N, g.M = M, g.K = K, g.sample0 = sample0;
+    g.lo = v == SDP_SW ? 2 : 1, g.cap = cap, g.transposed = transposed;
+    void (*kernel)(const sdp_sample::Params) = kind == SAMPLE_ROWS ? sdp_sample_rows_kernel : sdp_sample_rows_f64_kernel;
+    const char *name = kind == SAMPLE_ROWS ? "sdp_sample_rows_kernel" : "sdp_sample_rows_f64_kernel";
+    if (kind == SAMPLE_SKEWED) {
+        const bool exact = exact_for(exact_flag, N, M);
+        sdp::Params p = {};
+        p.N = N, p.M = M;
+        p.tpad = sdp::state_tpad(M);
+        state_layout(p);
+        g.nstrips_max = sdp::state_nstrips(N);
+        g.ps = exact ? p.st2_ps : p.st_ps;
+        g.us_q = p.st_us, g.us_x = p.st2_us;
+        g.whole_exact = exact ? 1 : 0, g.route = routes_thin(exact, N, M, lens) ? 1 : 0;
+        kernel = sdp_sample_kernel, name = "sdp_sample_kernel";
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)waves), dim3(sdp_sample::LANES), 0, (hipStream_t)stream, g);
+    return gap_launched(name);
+}
+
+int sdp_sample_paths_f32(const void *state, int32_t *states, int32_t *counts, int32_t *visits, int B, int N, int M, int K, int sample0,
+                         uint64_t seed, const int32_t *lens, int variant, int device, void *stream)
+{
+    if (variant & ~(SDP_SW | SDP_EXACT_STATE | SDP_REF_ROUNDING | SDP_SAMPLE_TRANSPOSED))
+        return fail(SDP_E_VARIANT, "sdp_sample_paths_f32: variant is SDP_NW / SDP_SW | SDP_EXACT_STATE | SDP_REF_ROUNDING | SDP_SAMPLE_TRANSPOSED");
+    const bool ref = (variant & SDP_REF_ROUNDING) != 0, exact = (variant & SDP_EXACT_STATE) != 0;
+    return sample_paths("sdp_sample_paths_f32", ref ? SAMPLE_ROWS : SAMPLE_SKEWED, state, states, counts, visits, B, N, M, K, sample0, seed,
+                        lens, variant & ~(SDP_EXACT_STATE | SDP_REF_ROUNDING), exact, device, stream);
+}
+
+int sdp_sample_paths_f64(const void *state, int32_t *states, int32_t *counts, int32_t *visits, int B, int N, int M, int K, int sample0,
+                         uint64_t seed, const int32_t *lens, int variant, int device, void *stream)
+{
+    if (variant & ~(SDP_SW | SDP_SAMPLE_TRANSPOSED))
+        return fail(SDP_E_VARIANT, "sdp_sample_paths_f64: variant is SDP_NW / SDP_SW | SDP_SAMPLE_TRANSPOSED (float64 states take no state / rounding flags)");
+    return sample_paths("sdp_sample_paths_f64", SAMPLE_ROWS_F64, state, states, counts, visits, B, N, M, K, sample0, seed, lens, variant, false,
+                        device, stream);
+}
+
+float sdp_sample_uniform(uint64_t seed, int pair, int sample, int t) { return sdp_sample::uniform(seed, pair, sample, t); }
 
 }  // extern "C"

@@ -470,6 +470,53 @@ int sdp_gap_gradient_f64(const double *E, const double *state, double *G, int B,
 int sdp_gap_gradient2_f64(const double *E, const double *Ed, const double *state, const double *state_d, double *Gd, int B, int N,
                           int M, const int32_t *lens, int variant, int device, void *stream);
 
+/* Alignments SAMPLED from the posterior: a stochastic traceback on the state of the forward sweep (csrc/sdp_sample.hip;
+ * DESIGN.md 3.15).  The weights Q[i,j,(x,m,y)] the forward sweep leaves are the transition probabilities of the Gibbs
+ * distribution over alignments that the operator defines; E (sdp_backward_*) is its marginals, the hard-max walk its mode, and
+ * these entries draw whole alignments from it.
+ * (n, m) = lens[b], clamped to [1, N] x [1, M] as the soft sweeps clamp them, or (N, M); lo = 1 (SDP_NW) or 2 (SDP_SW); Q[i,j,.]
+ * the weights the forward sweep left for the 1-based cell (i, j).  Sample k of pair b:
+ *     i = n, j = m, t = 0
+ *     while i >= lo and j >= lo:
+ *         u  = U(seed, b, sample0 + k, t)
+ *         qx = Q[i,j,x];  qy = Q[i,j,y]
+ *         s  = x (0) if u < qx  else  y (2) if u < qx + qy  else  m (1)
+ *         record (i-1, j-1, s);  i -= (s != y);  j -= (s != x);  t += 1
+ * and then the list is padded exactly as sdp_hard_walk_f32 pads: (i-1, j, x) while i > 0, then (i, j-1, y) while j > 0.  The
+ * list is stored start first.
+ * Arithmetic of the comparisons.  fp32 states: qx, qy are the fp32 weights exactly as the backward sweep decodes them (the packed
+ * state: the 20-bit field times 1 + 2^-19), qx + qy is one rounded fp32 add, the compares are fp32.  float64 states: the same in
+ * double.  A = -inf gives qx = qy = 0: the walk takes the diagonal.  NaN weights: unspecified.
+ * U is a counter-based generator without state, Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9,
+ * 0xBB67AE85): key = (seed & 0xffffffff, seed >> 32), counter = (t >> 2, sample, pair, 0), u = (word[t & 3] >> 8) * 2^-24 --
+ * exactly representable, in [0, 1).  A sample depends on (seed, pair, sample number) alone: K samples at sample0 = 0 are the
+ * K/2 at 0 followed by the K/2 at K/2.  sdp_sample_uniform is the host's twin of U (the same inline function), so a caller -- or
+ * a test without a GPU -- can reproduce any draw.
+ *   state    what sdp_forward_f32 / sdp_forward_f64 wrote for the same B, N, M, lens.
+ *   variant  SDP_NW / SDP_SW, or-ed with the flags the state was WRITTEN under (sdp_sample_paths_f32: SDP_EXACT_STATE,
+ *            SDP_REF_ROUNDING; sdp_sample_paths_f64: none) and SDP_SAMPLE_TRANSPOSED; any other bit: SDP_E_VARIANT.
+ *            SDP_SAMPLE_TRANSPOSED: the state is that of a problem handed over TRANSPOSED (M exceeded the column limit).  The
+ *            intervals are then taken in the ORIGINAL's order -- u < q(column step) gives the original's x (named 0), u < that +
+ *            q(row step) the original's y (named 2), else the diagonal -- and the padding runs down the columns first, as
+ *            SDP_HARD_TIES_YMX does for the hard walk; (i, j) stay in the coordinates handed over.
+ *   states   (B, K, cap, 3) int32 or NULL, cap = sdp_traceback_capacity(N, M).  The list of sample (b, k) is RIGHT-aligned: rows
+ *            cap-1-counts[b,k] .. cap-2, start first (every lane writes from the end and never moves a record); row cap-1 holds
+ *            (number of path cells, i, j of the first path cell), as for sdp_hard_walk_f32.
+ *   counts   (B, K) int32; required with states.
+ *   visits   (B, N, M) int32 or NULL: + 1 per PATH cell of every sample (padding cells are not counted), by no-return integer
+ *            atomic adds -- the caller zeroes it; the result is deterministic.  visits / K estimates E (Et = 1).
+ *   states and visits must not both be NULL.  K >= 1 and sample0 >= 0 (and sample0 + K < 2^31), else SDP_E_SHAPE; an output of
+ *   more than 2^31 - 1 elements: SDP_E_TOOBIG; M <= sdp_max_cols().  Every argument is checked before any device call.
+ * One launch, any batch: one wavefront per 64 samples of a pair, every lane on its own walk of at most n + m - 1 steps.
+ * (Added after SDP_VERSION 106 without a version change, like the gap-gradient entries: look the symbols up.  sdp_kernel_name
+ * answers 120-122 for their kernels.) */
+#define SDP_SAMPLE_TRANSPOSED 0x40000
+int sdp_sample_paths_f32(const void *state, int32_t *states, int32_t *counts, int32_t *visits, int B, int N, int M, int K, int sample0,
+                         uint64_t seed, const int32_t *lens, int variant, int device, void *stream);
+int sdp_sample_paths_f64(const void *state, int32_t *states, int32_t *counts, int32_t *visits, int B, int N, int M, int K, int sample0,
+                         uint64_t seed, const int32_t *lens, int variant, int device, void *stream);
+float sdp_sample_uniform(uint64_t seed, int pair, int sample, int t);
+
 /* Collecting results across the GPUs of a node for callers without torch.distributed.  The sweeps need no
  * collective; these four wrap the one RCCL all-gather (over xGMI) that gathers Vt -- or E -- from all ranks, one
  * process per GPU.  Rank 0 calls sdp_comm_unique_id and distributes the 128 bytes to the other ranks by its own means;
@@ -526,7 +573,8 @@ int sdp_plan(int pass, int B, int N, int M, int has_lens, int exact_state, int c
 int sdp_plan_parts(int pass, int B, int N, int M, int has_lens, int exact_state, int cus);
 
 /* The symbol of the kernel build with that id (what rocprofv3 shows for its launches), or NULL if no build has the id.  (100-105:
- * the gap-gradient kernels, 110-114 the local-alignment kernels of the hard-max family, which are no builds of the sweep.) */
+ * the gap-gradient kernels, 110-114 the local-alignment kernels of the hard-max family, 120-122 the sampling kernels, which are no
+ * builds of the sweep.) */
 const char *sdp_kernel_name(int kernel_id);
 
 #ifdef SDP_EXPERIMENTS
