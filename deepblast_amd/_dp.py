@@ -397,7 +397,8 @@ class _Decoder(nn.Module):
         (all zero when no cell is positive), score(..., return_ends=True) adds the end cells, optimal_paths the path without padding
         and its start cell.  theta must be able to go negative for anything to floor: with theta >= 0 (what
         scores.alignment_scores produces) the result is the free-end-gaps optimum.  A soft (differentiable) local operator is
-        not built: any other operator raises NotImplementedError."""
+        not built: any other operator raises NotImplementedError.  (The differentiable local alignment is a module of its own,
+        deepblast_amd.local.SoftLocalDecoder: its recurrence is not this family's with another operator.)"""
         super().__init__()
         if local and operator != 'hardmax':
             raise NotImplementedError(f"local=True needs operator='hardmax': a soft local operator is not built (got operator={operator!r})")

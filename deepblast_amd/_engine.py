@@ -494,6 +494,47 @@ class HipEngine:
                   B, N, M, lens, self._hard_variant(variant, ymx, waves=False))
         return E, states, counts
 
+    # ---- the soft local operator (include/sdp.h: sdp_soft_local_*) ---------------------------
+    def soft_local_forward(self, theta, A, lens=None, state_out=None):
+        """-> (Vt (B,), state): the soft local sweep and its 16-byte records (opaque float32 tensor of
+        sdp_soft_local_state_bytes).  state_out: a buffer of that size to write into instead of a fresh one."""
+        dev = self.device_of(theta)
+        check_args(theta, torch.float32, theta=theta, A=A)
+        theta, A = theta.contiguous(), A.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        nfloats = max(self.lib.sdp_soft_local_state_bytes(B, N, M), 4) // 4
+        check_args(theta, torch.float32, (nfloats,), True, ValueError, state_out=state_out)
+        state = torch.empty(nfloats, dtype=torch.float32, device=theta.device) if state_out is None else state_out
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        self.call("sdp_soft_local_forward_f32", SOFT_LOCAL_KERNELS[130], dev, theta, A, state, Vt, B, N, M, lens, 0)
+        return Vt, state
+
+    def soft_local_forward_value(self, theta, A, lens=None):
+        """-> Vt (B,) alone: the same sweep with the records compiled out (the same bits); nothing else is allocated."""
+        dev = self.device_of(theta)
+        check_args(theta, torch.float32, theta=theta, A=A)
+        theta, A = theta.contiguous(), A.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        self.call("sdp_soft_local_forward_value_f32", SOFT_LOCAL_KERNELS[131], dev, theta, A, Vt, B, N, M, lens, 0)
+        return Vt
+
+    def soft_local_backward(self, state, Vt, Et, shape, lens=None, want_G=True):
+        """The mirror sweep over the records of soft_local_forward -> (E (B,N,M), G (B,N,M) or None): Et . dVt/dtheta and
+        Et . dVt/dA, +0 outside each pair's block.  Vt: what soft_local_forward returned with `state`."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        check_args(state, torch.float32, (B,), True, Vt=Vt)
+        check_args(state, Et=Et)
+        Et = Et.detach().to(torch.float32).expand(B).contiguous()
+        lens = self._lens(lens, B, state.device)
+        E = torch.empty((B, N, M), dtype=torch.float32, device=state.device)
+        G = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if want_G else None
+        self.call("sdp_soft_local_backward_f32", SOFT_LOCAL_KERNELS[132], dev, state, Vt, Et, E, G, B, N, M, lens, 0)
+        return E, G
+
     # ---- alignments sampled from the posterior (include/sdp.h: sdp_sample_paths_*) -------------------
     def sample_paths(self, state, shape, variant, K, lens=None, seed=0, sample0=0, exact_state=False, transposed=False,
                      want_states=True, want_visits=False):
@@ -573,6 +614,8 @@ class HipEngine:
 # kernel id (csrc/sdp_hard.h; what sdp_kernel_name answers for) -> symbol of the local-alignment kernels: the launch labels
 HARD_LOCAL_KERNELS = {110: "sdp_hard_local_fwd_kernel", 111: "sdp_hard_local_fwd_t_kernel", 112: "sdp_hard_local_val_kernel",
                       113: "sdp_hard_local_val_t_kernel", 114: "sdp_hard_local_walk_kernel"}
+# kernel id (csrc/sdp_soft_local.h) -> symbol of the soft local operator's kernels
+SOFT_LOCAL_KERNELS = {130: "sdp_soft_local_fwd_kernel", 131: "sdp_soft_local_val_kernel", 132: "sdp_soft_local_bwd_kernel"}
 
 _SWEEPS = ("sdp_forward", "sdp_backward", "sdp_adjoint_forward", "sdp_adjoint_backward")
 # dtype -> (suffix of the four sweeps' entries, their launch labels (float32: where the library's plan is not asked),

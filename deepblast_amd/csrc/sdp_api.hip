@@ -13,6 +13,7 @@
 #include "sdp_gap.h"
 #include "sdp_sample.h"
 #include "sdp_hard.h"
+#include "sdp_soft_local.h"
 #include "sdp_kernels.h"
 
 namespace {
@@ -662,6 +663,10 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_sample::ID_SAMPLE: return "sdp_sample_kernel";
     case sdp_sample::ID_SAMPLE_ROWS: return "sdp_sample_rows_kernel";
     case sdp_sample::ID_SAMPLE_ROWS_F64: return "sdp_sample_rows_f64_kernel";
+    // the soft local operator (csrc/sdp_soft_local.hip)
+    case sdp_soft_local::ID_FWD: return "sdp_soft_local_fwd_kernel";
+    case sdp_soft_local::ID_VAL: return "sdp_soft_local_val_kernel";
+    case sdp_soft_local::ID_BWD: return "sdp_soft_local_bwd_kernel";
     }
     return nullptr;
 }
@@ -1394,6 +1399,73 @@ int sdp_hard_local_walk_f32(const void *state, const int32_t *ends, const float 
                        ymx ? 1 : 0);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "sdp_hard_local_walk_kernel");
+    return 0;
+}
+
+// ---- the soft local operator (csrc/sdp_soft_local.hip): a differentiable Smith-Waterman, first order ----
+// `flags` of the three entries: none is defined, any bit is refused
+static int soft_local_args(int B, int N, int M, int flags)
+{
+    if (int rc = check_shape(B, N, M, SDP_NW)) return rc;
+    if (flags != 0) return fail(SDP_E_VARIANT, "sdp_soft_local_*: this family defines no flags");
+    if ((size_t)B * (size_t)N * (size_t)M > ((size_t)1 << 31)) return fail(SDP_E_TOOBIG, "B*N*M exceeds 2^31 elements");
+    return 0;
+}
+
+// waves of a workgroup: one per strip in flight, as many as the boundary rows fit LDS for
+static int soft_local_waves(int N, int M)
+{
+    int w = sdp_soft_local::strips(N) < sdp_soft_local::MAX_WAVES ? sdp_soft_local::strips(N) : sdp_soft_local::MAX_WAVES;
+    while (w > 1 && sdp_soft_local::sweep_lds_bytes(w, M) > (size_t)sdp_soft_local::LDS_BUDGET) --w;
+    return w;
+}
+
+size_t sdp_soft_local_state_bytes(int B, int N, int M)
+{
+    if (B <= 0 || N <= 0 || M <= 0 || M > sdp::MAX_COLS) return 0;
+    return (size_t)B * sdp_soft_local::pair_records(N, M) * sdp_soft_local::CELL_BYTES;
+}
+
+static int soft_local_forward(const float *theta, const float *A, void *state, float *Vt, int B, int N, int M, const int32_t *lens,
+                              int flags, int device, void *stream, bool records)
+{
+    if (int rc = soft_local_args(B, N, M, flags)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    const int W = soft_local_waves(N, M);
+    hipLaunchKernelGGL(records ? sdp_soft_local_fwd_kernel : sdp_soft_local_val_kernel, dim3(B), dim3(64 * W),
+                       sdp_soft_local::sweep_lds_bytes(W, M), (hipStream_t)stream, theta, A, static_cast<float4 *>(state), Vt, lens, N, M, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, records ? "sdp_soft_local_fwd_kernel" : "sdp_soft_local_val_kernel");
+    return 0;
+}
+
+int sdp_soft_local_forward_f32(const float *theta, const float *A, void *state, float *Vt, int B, int N, int M, const int32_t *lens,
+                               int flags, int device, void *stream)
+{
+    if (!theta || !A || !state || !Vt) return fail(SDP_E_NULLPTR, "sdp_soft_local_forward_f32: null pointer");
+    return soft_local_forward(theta, A, state, Vt, B, N, M, lens, flags, device, stream, true);
+}
+
+int sdp_soft_local_forward_value_f32(const float *theta, const float *A, float *Vt, int B, int N, int M, const int32_t *lens, int flags,
+                                     int device, void *stream)
+{
+    if (!theta || !A || !Vt) return fail(SDP_E_NULLPTR, "sdp_soft_local_forward_value_f32: null pointer");
+    return soft_local_forward(theta, A, nullptr, Vt, B, N, M, lens, flags, device, stream, false);
+}
+
+int sdp_soft_local_backward_f32(const void *state, const float *Vt, const float *Et, float *E, float *G, int B, int N, int M,
+                                const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!state || !Vt || !Et || !E) return fail(SDP_E_NULLPTR, "sdp_soft_local_backward_f32: null pointer (state, Vt, Et, E; G may be NULL)");
+    if (int rc = soft_local_args(B, N, M, flags)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    const int W = soft_local_waves(N, M);
+    hipLaunchKernelGGL(sdp_soft_local_bwd_kernel, dim3(B), dim3(64 * W), sdp_soft_local::sweep_lds_bytes(W, M), (hipStream_t)stream,
+                       static_cast<const float4 *>(state), Vt, Et, E, G, lens, N, M, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_bwd_kernel");
     return 0;
 }
 

@@ -431,6 +431,41 @@ int sdp_hard_local_forward_value_f32(const float *theta, const float *A, float *
 int sdp_hard_local_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, int32_t *states, int32_t *counts,
                             int B, int N, int M, const int32_t *lens, int variant, int device, void *stream);
 
+/* The SOFT LOCAL operator (csrc/sdp_soft_local.hip): a differentiable Smith-Waterman -- the log-sum-exp over every
+ * local alignment, of which the hard local operator above is the zero-temperature limit.  (Added after SDP_VERSION 106 without a
+ * version change: look the symbols up.  "The soft sweeps have no local form" above still holds: this is a kernel family of its own.)
+ * With (n, m) = lens[b] or (N, M), cells 1-based, theta and A 0-based, states x, m, y = 0, 1, 2; a V outside the table does not
+ * exist and is -inf, NOT 0:
+ *     V[i,j]  = theta[i,j] + log(1 + exp(A[i,j] + V[i-1,j]) + exp(V[i-1,j-1]) + exp(A[i,j] + V[i,j-1]))
+ *     q_x, q_m, q_y [i,j] = the three exp terms divided by the sum in the log         (restart weight: 1 - q_x - q_m - q_y)
+ *     Vt      = log(1 + sum over all cells of exp V[i,j])
+ * exp(Vt) = 1 + the sum over every non-empty local path of exp(score): a path starts at any cell, takes steps x / m / y and ends at
+ * any cell; its score is theta on its cells plus A on every cell it ENTERS through x or y (the start cell pays no A); the 1 is the
+ * empty alignment (the hard local operator's Vt = 0).  For A <= 0: hard_local_Vt <= Vt <= hard_local_Vt + log(1 + #paths).
+ * The backward pass gives the TRUE gradients (there is no reference convention to reproduce here):
+ *     w[i,j]  = exp(V[i,j] - Vt)                                            the probability that the alignment ends in (i, j)
+ *     E[i,j]  = Et w[i,j] + q_x[i+1,j] E[i+1,j] + q_m[i+1,j+1] E[i+1,j+1] + q_y[i,j+1] E[i,j+1]      = Et dVt/dtheta[i,j]
+ *     G[i,j]  = E[i,j] (q_x[i,j] + q_y[i,j])                                                          = Et dVt/dA[i,j]
+ * E / Et is the posterior probability that the cell lies on the alignment.  E and G are +0 outside the pair's [:n, :m] block (the
+ * backward kernel writes them; there is no SDP_NO_FILL here); a pair with n < 1 or m < 1 has Vt = 0 and E = G = 0.  fp32 only,
+ * finite inputs, first order only (no adjoint pair).  No floating-point atomics: two calls on the same inputs give the same bits,
+ * and sdp_soft_local_forward_value_f32 gives the bits of sdp_soft_local_forward_f32's Vt.
+ *   state    sdp_soft_local_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: four floats per cell {q_x, q_m, q_y,
+ *            V}, private layout; written by sdp_soft_local_forward_f32, read by sdp_soft_local_backward_f32 with the same B, N, M,
+ *            lens.  Only records of cells inside a pair's block are written, and the backward pass reads no others.
+ *   Vt       (B,): written by the forward entries, READ by the backward entry (w needs it).
+ *   G        (B, N, M) or NULL.
+ *   flags    this family defines none: any bit is refused (SDP_E_VARIANT).
+ * One workgroup per pair, rows unbounded, M <= sdp_max_cols().  All arguments are checked before any device call: SDP_E_NULLPTR,
+ * SDP_E_SHAPE, SDP_E_MAXCOLS, SDP_E_VARIANT, SDP_E_TOOBIG (N*M > 2^28, or B*N*M > 2^31 elements). */
+size_t sdp_soft_local_state_bytes(int B, int N, int M);
+int sdp_soft_local_forward_f32(const float *theta, const float *A, void *state, float *Vt, int B, int N, int M, const int32_t *lens,
+                               int flags, int device, void *stream);
+int sdp_soft_local_forward_value_f32(const float *theta, const float *A, float *Vt, int B, int N, int M, const int32_t *lens, int flags,
+                                     int device, void *stream);
+int sdp_soft_local_backward_f32(const void *state, const float *Vt, const float *Et, float *E, float *G, int B, int N, int M,
+                                const int32_t *lens, int flags, int device, void *stream);
+
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept
  * for callers who are short of memory, not of time; deepblast_amd.losses uses the unfused kernels by default.
