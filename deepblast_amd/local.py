@@ -67,6 +67,7 @@ class SoftLocalDecoder(torch.nn.Module):
     decode(theta, A, lengths=None)  -> E (B, N, M) for Et = 1: E[b, i, j] is the posterior probability that cell (i, j) lies on the
     alignment of pair b.  No autograd graph.
     score(theta, A, lengths=None)   -> Vt (B,) through the value-only sweep: no state is allocated, no graph.
+    theta finite; A finite or -inf (a forbidden gap: G is exactly 0 there).
     lengths (B, 2): pair b is theta[b, :n_b, :m_b]; E and G are +0 outside it, and an empty pair has Vt = 0.  Problems wider than
     the column limit (2048) are swept transposed -- the operator is symmetric under transposition with x <-> y -- and the results
     come back in the caller's coordinates; both sides above the limit raise ValueError."""

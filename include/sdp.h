@@ -447,9 +447,10 @@ int sdp_hard_local_walk_f32(const void *state, const int32_t *ends, const float 
  *     E[i,j]  = Et w[i,j] + q_x[i+1,j] E[i+1,j] + q_m[i+1,j+1] E[i+1,j+1] + q_y[i,j+1] E[i,j+1]      = Et dVt/dtheta[i,j]
  *     G[i,j]  = E[i,j] (q_x[i,j] + q_y[i,j])                                                          = Et dVt/dA[i,j]
  * E / Et is the posterior probability that the cell lies on the alignment.  E and G are +0 outside the pair's [:n, :m] block (the
- * backward kernel writes them; there is no SDP_NO_FILL here); a pair with n < 1 or m < 1 has Vt = 0 and E = G = 0.  fp32 only,
- * finite inputs, first order only (no adjoint pair).  No floating-point atomics: two calls on the same inputs give the same bits,
- * and sdp_soft_local_forward_value_f32 gives the bits of sdp_soft_local_forward_f32's Vt.
+ * backward kernel writes them; there is no SDP_NO_FILL here); a pair with n < 1 or m < 1 has Vt = 0 and E = G = 0.  fp32 only;
+ * theta finite; A finite or -inf (a forbidden gap: G is exactly 0 there); first order only (no adjoint pair).  No floating-point
+ * atomics: two calls on the same inputs give the same bits, and sdp_soft_local_forward_value_f32 gives the bits of
+ * sdp_soft_local_forward_f32's Vt.
  *   state    sdp_soft_local_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: four floats per cell {q_x, q_m, q_y,
  *            V}, private layout; written by sdp_soft_local_forward_f32, read by sdp_soft_local_backward_f32 with the same B, N, M,
  *            lens.  Only records of cells inside a pair's block are written, and the backward pass reads no others.

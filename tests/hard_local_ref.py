@@ -127,8 +127,52 @@ def forward_batch(theta, A, variant):
     return Vt, ends, P
 
 
-def batch(theta, A, variant, lens=None, Et=None):
-    """(B, N, M) -> dict(Vt (B,) fp32, ends (B, 2) int32, E (B, N, M) fp32, cells): every pair over its own [:n, :m] block"""
+def forward_fast(theta, A, variant, ymx=False):
+    """forward_batch() swept along the anti-diagonals: one numpy operation per diagonal over all of its cells and all B pairs --
+    the same fp32 operations per cell in the same nesting, the same strict '>', the zero floor and code START, the first best
+    cell in row-major order (tests/test_hard_local.py holds it to forward() bit for bit).  For the shapes the loops are too slow
+    for.  ymx: the tie rule of SDP_HARD_TIES_YMX as pair_transposed() states it -- c scanned y, m, x, the first best cell in
+    COLUMN-major order -- on the tensors as they are handed over."""
+    B, n, m = theta.shape
+    lo = 2 if variant else 1
+    th, a = np.asarray(theta, F), np.asarray(A, F)
+    V = np.zeros((B, n + 1, m + 1), F)
+    P = np.full((B, n + 1, m + 1), -1, np.int8)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for d in range(2 * lo, n + m + 1):                     # the cells with i + j = d
+            i = np.arange(max(lo, d - m), min(n, d - lo) + 1)
+            j = d - i
+            aa = a[:, i - 1, j - 1]
+            c = (aa + V[:, i - 1, j], V[:, i - 1, j - 1], aa + V[:, i, j - 1])
+            first, rest = (2, (1, 0)) if ymx else (0, (1, 2))
+            best, k = c[first], np.full((B, len(i)), first, np.int8)
+            for q in rest:
+                t = c[q] > best
+                best, k = np.where(t, c[q], best), np.where(t, np.int8(q), k)
+            v = th[:, i - 1, j - 1] + best
+            assert v.dtype == F
+            alive = v > 0
+            V[:, i, j], P[:, i, j] = np.where(alive, v, F(0)), np.where(alive, k, np.int8(START))
+    Vt, ends = np.zeros(B, F), np.zeros((B, 2), np.int64)
+    if n >= lo and m >= lo:
+        inner = V[:, lo:, lo:]
+        w = m + 1 - lo
+        if ymx:
+            h = n + 1 - lo
+            first = np.ascontiguousarray(inner.transpose(0, 2, 1)).reshape(B, -1).argmax(axis=1)
+            ends = np.stack([first % h + lo, first // h + lo], axis=1)
+        else:
+            first = inner.reshape(B, -1).argmax(axis=1)        # the first maximum in row-major order
+            ends = np.stack([first // w + lo, first % w + lo], axis=1)
+        Vt = V[np.arange(B), ends[:, 0], ends[:, 1]]
+        ends[~(Vt > 0)] = 0
+        Vt = np.where(Vt > 0, Vt, F(0))
+    return Vt, ends, P
+
+
+def batch(theta, A, variant, lens=None, Et=None, fwd=forward_batch):
+    """(B, N, M) -> dict(Vt (B,) fp32, ends (B, 2) int32, E (B, N, M) fp32, cells): every pair over its own [:n, :m] block;
+    fwd: forward_batch or forward_fast"""
     B, N, M = theta.shape
     Et = np.ones(B, F) if Et is None else np.broadcast_to(np.asarray(Et, F).reshape(-1), (B,))
     Vt = np.zeros(B, F)
@@ -139,7 +183,7 @@ def batch(theta, A, variant, lens=None, Et=None):
     for sl, n, m in groups:
         if n < 1 or m < 1:
             continue
-        v, e, P = forward_batch(np.ascontiguousarray(theta[sl, :n, :m], F), np.ascontiguousarray(A[sl, :n, :m], F), variant)
+        v, e, P = fwd(np.ascontiguousarray(theta[sl, :n, :m], F), np.ascontiguousarray(A[sl, :n, :m], F), variant)
         Vt[sl] = v
         for q, b in enumerate(range(B)[sl]):
             if e[q, 0] > 0:

@@ -26,6 +26,30 @@ def forward(theta, A, variant):
     return V[n, m], P
 
 
+def forward_fast(theta, A, variant):
+    """forward() swept along the anti-diagonals: one numpy operation per diagonal over all of its cells -- the same fp32
+    operations per cell in the same nesting, the same strict '>' (tests/test_hard.py holds it to forward() bit for bit).  For
+    the shapes the loop is too slow for."""
+    n, m = theta.shape
+    lo = 2 if variant else 1
+    th, a = np.asarray(theta, F), np.asarray(A, F)
+    V = np.zeros((n + 1, m + 1), F)
+    P = np.full((n + 1, m + 1), -1, np.int8)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for d in range(2 * lo, n + m + 1):                     # the cells with i + j = d
+            i = np.arange(max(lo, d - m), min(n, d - lo) + 1)
+            j = d - i
+            aa = a[i - 1, j - 1]
+            best, k = aa + V[i - 1, j], np.zeros(len(i), np.int8)
+            for q, c in ((1, V[i - 1, j - 1]), (2, aa + V[i, j - 1])):
+                t = c > best
+                best, k = np.where(t, c, best), np.where(t, np.int8(q), k)
+            v = th[i - 1, j - 1] + best
+            assert v.dtype == F
+            P[i, j], V[i, j] = k, v
+    return V[n, m], P
+
+
 def path(P, variant):
     """-> [(i, j, state)] 0-based, in increasing order"""
     n, m = P.shape[0] - 1, P.shape[1] - 1
@@ -52,17 +76,17 @@ def padded(cells, n, m):
     return pad[::-1] + list(cells)
 
 
-def pair(theta, A, variant):
-    """one pair -> (Vt, path cells, padded list)"""
+def pair(theta, A, variant, fwd=forward):
+    """one pair -> (Vt, path cells, padded list); fwd: forward or forward_fast"""
     n, m = theta.shape
     if n < 1 or m < 1:
         return F(0), [], []
-    Vt, P = forward(theta, A, variant)
+    Vt, P = fwd(theta, A, variant)
     cells = path(P, variant)
     return Vt, cells, padded(cells, n, m)
 
 
-def batch(theta, A, variant, lens=None, Et=None):
+def batch(theta, A, variant, lens=None, Et=None, fwd=forward):
     """(B, N, M) -> dict(Vt (B,) fp32, E (B, N, M) fp32, cells, lists): every pair over its own [:n, :m] block"""
     B, N, M = theta.shape
     Et = np.ones(B, F) if Et is None else np.broadcast_to(np.asarray(Et, F).reshape(-1), (B,))
@@ -71,7 +95,7 @@ def batch(theta, A, variant, lens=None, Et=None):
     cells, lists = [], []
     for b in range(B):
         n, m = (N, M) if lens is None else (int(lens[b][0]), int(lens[b][1]))
-        v, c, p = pair(np.ascontiguousarray(theta[b, :n, :m]), np.ascontiguousarray(A[b, :n, :m]), variant)
+        v, c, p = pair(np.ascontiguousarray(theta[b, :n, :m]), np.ascontiguousarray(A[b, :n, :m]), variant, fwd)
         Vt[b] = v
         for (i, j, _) in c:
             E[b, i, j] = Et[b]

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import hard_ref
+import strip_schedule
 from hard_engine import HardOracleEngine
 
 
@@ -201,6 +202,37 @@ def test_hard_ref_against_brute_force(variant):
             Vt, cells, lst = hard_ref.pair(th[0], a[0], variant)
             assert Vt == hard_ref.brute_force_best(th[0], a[0], variant), (n, m, seed)
             assert (lst[0][:2] == (0, 0)) if lst else (n == 1 and m == 1 and variant == 1)
+
+
+# the small shapes of tests/test_hard_gpu.py: SHAPES (the loop reference takes about a second per 50k cells)
+SMALL = [(1, 1), (1, 7), (7, 1), (2, 2), (5, 9), (31, 33), (64, 64), (65, 130), (63, 16), (64, 17), (65, 1), (65, 2), (66, 33), (66, 34)]
+
+
+@pytest.mark.parametrize("variant", [0, 1], ids=["nw", "sw"])
+def test_fast_form_is_the_loop_bit_for_bit(variant):
+    """hard_ref.forward_fast (one numpy operation per anti-diagonal) against hard_ref.forward: Vt, every pointer, path and list"""
+    def cont(seed, B, N, M):
+        rng = np.random.RandomState(seed)
+        return np.logaddexp(0, rng.randn(B, N, M)).astype(np.float32), (-np.logaddexp(0, -rng.randn(B, N, M))).astype(np.float32)
+    for family in (hard_ref.quarter_scores, cont):
+        for (n, m) in SMALL:
+            th, a = family(11, 1, n, m)
+            Vt, P = hard_ref.forward(th[0], a[0], variant)
+            Vf, Pf = hard_ref.forward_fast(th[0], a[0], variant)
+            assert np.float32(Vt).view(np.uint32) == np.float32(Vf).view(np.uint32) and np.array_equal(P, Pf), (n, m)
+    th, a = hard_ref.quarter_scores(13, 5, 40, 40)
+    a[3, 5:, 7] = -np.inf
+    lens = [(1, 1), (40, 40), (2, 39), (33, 17), (0, 4)]
+    for ln in (None, lens):
+        r, f = (hard_ref.batch(th, a, variant, ln, Et=[1.0, -2.5, 0.0, 1.0, 1.0], fwd=fw) for fw in (hard_ref.forward, hard_ref.forward_fast))
+        assert np.array_equal(r["Vt"].view(np.uint32), f["Vt"].view(np.uint32)) and np.array_equal(r["E"].view(np.uint32), f["E"].view(np.uint32))
+        assert r["cells"] == f["cells"] and r["lists"] == f["lists"]
+
+
+def test_the_wide_shapes_are_on_the_routes_they_are_named_for():
+    """seven waves from M = 1983 on, nine strips at 513 rows (csrc/sdp_hard.h, csrc/sdp_api.hip: hard_waves)"""
+    c = strip_schedule.check_wide_shapes("sdp_hard.h")
+    assert c["PTR_STEPS"] == 16
 
 
 # ---- the C ABI's argument checks need no GPU ----

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import hard_ref
+import strip_schedule
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -104,6 +105,47 @@ def test_fewer_waves_than_strips(variant, waves):
     finally:
         eng.force_waves.pop("hard", None)
     _check(got, hard_ref.batch(th, a, variant), waves)
+
+
+# Full width and seven waves (tests/strip_schedule.py: WIDE has what each shape covers); 449 x 1982 runs in the soft local suite
+WIDE = [(449, 1983), (513, 2048)]
+
+
+@functools.lru_cache(maxsize=None)
+def _want_wide(family, N, M, variant):
+    """hard_ref.forward_fast's results for a wide case (tests/test_hard.py holds it to the loop bit for bit), computed once"""
+    th, a = _case(family, 23, 2, N, M)
+    return hard_ref.batch(th, a, variant, Et=[1.0, -2.5], fwd=hard_ref.forward_fast)
+
+
+@pytest.mark.parametrize("variant", [0, 1], ids=["nw", "sw"])
+@pytest.mark.parametrize("family", sorted(FAMILIES))
+@pytest.mark.parametrize("shape", WIDE, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_full_width_on_seven_waves(variant, family, shape):
+    """the wave count LDS forces (seven: neither a power of two nor a divisor of the strip count) and the column limit"""
+    c = strip_schedule.check_wide_shapes("sdp_hard.h")
+    assert strip_schedule.waves(c, *shape) == 7 and shape in strip_schedule.WIDE
+    th, a = _case(family, 23, 2, *shape)
+    want = _want_wide(family, *shape, variant)
+    got = _run(th, a, variant, Et=[1.0, -2.5])
+    _check(got, want, shape)
+    Vv = _engine().hard_forward_value(_dev(th), _dev(a), variant)
+    assert np.array_equal(_bits(Vv.cpu().numpy()), _bits(want["Vt"]))
+
+
+@pytest.mark.parametrize("variant", [0, 1], ids=["nw", "sw"])
+def test_full_width_with_the_tie_flag(variant):
+    """513 x 2048 handed over as the transpose of a 2048 x 513 problem: the `_t` kernels at the column limit give the original's
+    Vt, path and padded list"""
+    th, a = _case("ties", 24, 2, 513, 2048)
+    want = hard_ref.batch(np.ascontiguousarray(th.transpose(0, 2, 1)), np.ascontiguousarray(a.transpose(0, 2, 1)), variant,
+                          fwd=hard_ref.forward_fast)
+    Vt, E, states, counts = _run(th, a, variant, ymx=True)
+    st = states[..., [1, 0, 2]]
+    st[:, -1] = states[:, -1]                          # (the last row is scratch: the number of path cells in front)
+    _check((Vt, E.transpose(0, 2, 1), st, counts), want, "ymx")
+    Vv = _engine().hard_forward_value(_dev(th), _dev(a), variant, ymx=True)
+    assert np.array_equal(_bits(Vv.cpu().numpy()), _bits(want["Vt"]))
 
 
 @pytest.mark.parametrize("variant", [0, 1], ids=["nw", "sw"])

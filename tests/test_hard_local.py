@@ -112,6 +112,47 @@ def test_tie_flag_is_needed(variant):
     assert ref.pair_transposed(th[0], a[0], variant, flag=False) != ref.pair(th[0], a[0], variant)
 
 
+# the small shapes of tests/test_hard_local_gpu.py: SHAPES
+SMALL = [(1, 1), (1, 70), (70, 1), (64, 32), (63, 33), (65, 97)]
+
+
+def _tie_scores(seed, B, N, M):
+    return ref.quarter_scores(seed, B, N, M, lo=-1.0, hi=0.5)
+
+
+@pytest.mark.parametrize("variant", [0, 1], ids=["nw", "sw"])
+def test_fast_form_is_the_loop_bit_for_bit(variant):
+    """ref.forward_fast (one numpy operation per anti-diagonal) against the loops: V's best, the end, every pointer, the path"""
+    for family in (_tie_scores, ref.floor_scores):
+        for (n, m) in SMALL:
+            th, a = family(11, 2, n, m)
+            Vf, ef, Pf = ref.forward_fast(th, a, variant)
+            for b in range(2):
+                Vt, end, P, _ = ref.forward(th[b], a[b], variant)
+                assert _bits(np.float32(Vt)) == _bits(Vf[b:b + 1])[0] and tuple(ef[b]) == (end or (0, 0)) and np.array_equal(P, Pf[b]), (n, m, b)
+    th, a = _tie_scores(13, 6, 40, 40)
+    th[5] = -np.abs(th[5]) - np.float32(0.25)
+    a[3, 5:, 7] = -np.inf
+    lens = [(0, 5), (40, 40), (2, 39), (33, 17), (31, 40), (40, 30)]
+    for ln in (None, lens):
+        r, f = (ref.batch(th, a, variant, ln, Et=[1.0, -2.5, 0.5, 1.0, 2.0, 1.0], fwd=fw) for fw in (ref.forward_batch, ref.forward_fast))
+        assert np.array_equal(_bits(r["Vt"]), _bits(f["Vt"])) and np.array_equal(r["ends"], f["ends"]) and r["cells"] == f["cells"]
+        assert np.array_equal(_bits(r["E"]), _bits(f["E"])) and any(r["cells"])
+
+
+@pytest.mark.parametrize("variant", [0, 1], ids=["nw", "sw"])
+def test_fast_form_with_the_tie_flag_is_pair_transposed(variant):
+    """ymx: on the transposed tensors the fast form gives what pair_transposed(flag=True) -- and so the direct sweep -- gives"""
+    for seed in list(range(6)) + [TIE_SEEDS[variant]]:
+        for (n, m) in ((6, 11), (1, 5), (5, 1), (4, 4), (20, 33)):
+            th, a = ref.quarter_scores(seed, 1, n, m, lo=-0.5, hi=0.25)
+            Vt, e, P = ref.forward_fast(np.ascontiguousarray(th.transpose(0, 2, 1)), np.ascontiguousarray(a.transpose(0, 2, 1)), variant, ymx=True)
+            end = (int(e[0, 0]), int(e[0, 1])) if e[0, 0] > 0 else None
+            cells = [(j, i, 2 - k) for (i, j, k) in ref.path(P[0], end, variant)]
+            got = (Vt[0], (end[1] - 1, end[0] - 1) if end else (-1, -1), cells)
+            assert got == ref.pair_transposed(th[0], a[0], variant, flag=True) == ref.pair(th[0], a[0], variant), (seed, n, m)
+
+
 # ---- the Python wiring over the stand-in engine ----
 def test_the_two_refusals(eng):
     NW, SW = _decoders()

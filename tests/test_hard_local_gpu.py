@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import hard_local_ref as ref
+import strip_schedule
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -122,6 +123,48 @@ def test_fewer_waves_than_strips(variant, waves):
     finally:
         eng.force_waves.pop("hard", None)
     _check(got, _want("ties", 11, 3, 130, 200, variant), waves)
+
+
+# Full width and seven waves (tests/strip_schedule.py: WIDE has what each shape covers); 449 x 1982 runs in the soft local suite
+WIDE = [(449, 1983), (513, 2048)]
+
+
+@functools.lru_cache(maxsize=None)
+def _want_wide(family, N, M, variant):
+    """ref.forward_fast's results for a wide case (tests/test_hard_local.py holds it to the loops bit for bit), computed once"""
+    th, a = _case(family, 23, 2, N, M)
+    return ref.batch(th, a, variant, Et=np.asarray(ET[:2], np.float32), fwd=ref.forward_fast)
+
+
+@pytest.mark.parametrize("variant", [0, 1], ids=["nw", "sw"])
+@pytest.mark.parametrize("family", sorted(FAMILIES))
+@pytest.mark.parametrize("shape", WIDE, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_full_width_on_seven_waves(variant, family, shape):
+    """the wave count LDS forces (seven: neither a power of two nor a divisor of the strip count) and the column limit: Vt, the
+    end, the pointers along the path, the walk"""
+    c = strip_schedule.check_wide_shapes("sdp_hard.h")
+    assert strip_schedule.waves(c, *shape) == 7 and shape in strip_schedule.WIDE
+    th, a = _case(family, 23, 2, *shape)
+    want = _want_wide(family, *shape, variant)
+    _check(_run(th, a, variant), want, shape)
+    assert all(want["cells"]) and (want["Vt"] > 0).all()
+    Vv, ev = _engine().hard_local_forward_value(_dev(th), _dev(a), variant)
+    assert np.array_equal(_bits(Vv.cpu().numpy()), _bits(want["Vt"])) and np.array_equal(ev.cpu().numpy(), want["ends"])
+
+
+@pytest.mark.parametrize("variant", [0, 1], ids=["nw", "sw"])
+def test_full_width_with_the_tie_flag(variant):
+    """513 x 2048 handed over as the transpose of a 2048 x 513 problem: the `_t` kernels at the column limit give the original's
+    Vt, end and path, in swapped coordinates"""
+    th, a = _case("ties", 24, 2, 513, 2048)
+    want = ref.batch(np.ascontiguousarray(th.transpose(0, 2, 1)), np.ascontiguousarray(a.transpose(0, 2, 1)), variant,
+                     Et=np.asarray(ET[:2], np.float32), fwd=ref.forward_fast)
+    Vt, ends, E, states, counts = _run(th, a, variant, ymx=True)
+    st = states[..., [1, 0, 2]]
+    st[:, -1] = states[:, -1][:, [0, 2, 1]]            # the scratch row is (count, i, j)
+    _check((Vt, ends[:, ::-1], E.transpose(0, 2, 1), st, counts), want, "ymx")
+    Vv, ev = _engine().hard_local_forward_value(_dev(th), _dev(a), variant, ymx=True)
+    assert np.array_equal(_bits(Vv.cpu().numpy()), _bits(want["Vt"])) and np.array_equal(ev.cpu().numpy()[:, ::-1], want["ends"])
 
 
 @pytest.mark.parametrize("variant", [0, 1], ids=["nw", "sw"])

@@ -10,6 +10,7 @@ import torch
 
 import hard_local_ref
 import soft_local_ref as ref
+import strip_schedule
 from soft_local_engine import SoftLocalOracleEngine
 
 
@@ -101,6 +102,73 @@ def test_the_hard_local_operator_is_the_zero_temperature_limit():
         soft = ref.pair(beta * th[b].astype(np.float64), beta * a[b].astype(np.float64))[0] / beta
         assert hard <= soft <= hard + (np.log(n * m) + (n + m) * np.log(3.0)) / beta, (b, hard, soft)
     assert max(ref.hard_local_f64(th[b], a[b]) for b in range(6)) > 0
+
+
+# ---- the wavefront form of the reference, and the input family of the wide cases ----
+TOL = 1e-4            # tests/parity.py's bound, which the GPU tests hold the kernels to
+WIDE = ((449, 1982), (449, 1983), (513, 2048))       # the shapes of tests/test_soft_local_gpu.py's wide cases
+
+
+def _close(r, w, what):
+    for k in ("Vt", "E", "G"):
+        assert r[k].shape == w[k].shape and w[k].dtype == np.float64 and np.abs(r[k] - w[k]).max() <= 1e-12, (what, k)
+
+
+@pytest.mark.parametrize("family", ["floor", "drift", "model", "steep", "islands"])
+def test_wavefront_form_is_the_definition(family):
+    """one numpy operation per anti-diagonal gives what the loops over cells give"""
+    for (n, m) in ((24, 26),) if family == "islands" else ((1, 1), (1, 7), (6, 1), (2, 2), (9, 13), (13, 9)):
+        th, a = ref.family(family, 40 + n, 2, n, m)
+        _close(ref.batch(th, a), ref.batch_wavefront(th, a), (family, n, m))
+
+
+def test_wavefront_form_with_lengths_weights_and_forbidden_gaps():
+    th, a = ref.family("model", 41, 6, 9, 13)
+    lens = [(9, 13), (0, 5), (5, 0), (1, 13), (9, 1), (12, 20)]          # (the last one is clamped to the tensor)
+    et = np.array([1.0, 2.0, -0.5, 3.0, 0.0, 0.25])
+    _close(ref.batch(th, a, lens, Et=et), ref.batch_wavefront(th, a, lens, Et=et), "lens")
+    a = a.copy()
+    a[np.random.RandomState(42).rand(*a.shape) < 0.3] = -np.inf
+    a[1, 4, :] = -np.inf
+    r, w = ref.batch(th, a), ref.batch_wavefront(th, a)
+    _close(r, w, "-inf")
+    assert all(np.isfinite(v).all() for v in w.values()) and not w["G"][np.isinf(a)].any() and w["G"].any()
+    # the same code in float32: an estimate of plain fp32 arithmetic, not a second yardstick
+    w32 = ref.batch_wavefront(th, a, dtype=np.float32)
+    assert all(v.dtype == np.float32 for v in w32.values()) and np.abs(w32["E"] - w["E"]).max() <= 1e-5
+
+
+@pytest.fixture(scope="module", params=WIDE, ids=lambda s: f"{s[0]}x{s[1]}")
+def wide(request):
+    n, m = request.param
+    th, a = ref.family("islands", 1000 + 7 * n + m, 1, n, m)     # the seed of tests/test_soft_local_gpu.py: _case
+    return n, m, th, a, ref.batch_wavefront(th, a)
+
+
+def test_the_wide_shapes_are_on_the_routes_they_are_named_for():
+    """8 waves and exactly 64 KB of LDS at M = 1982, seven waves from 1983 on (csrc/sdp_soft_local.h, csrc/sdp_api.hip)"""
+    c = strip_schedule.check_wide_shapes("sdp_soft_local.h")
+    assert WIDE == tuple(sorted(strip_schedule.WIDE)) and c["HALF"] == 16 and c["CELL_BYTES"] == 16
+
+
+def test_islands_stay_inside_plain_fp32(wide):
+    """condition 1 of the wide cases: fp32 arithmetic alone uses at most a quarter of the bound the kernels are held to"""
+    n, m, th, a, w = wide
+    w32 = ref.batch_wavefront(th, a, dtype=np.float32)
+    errs = {k: float(np.abs(w32[k] - w[k]).max()) for k in ("E", "G")}
+    print(n, m, "fp32 numpy against float64:", errs, "Vt", w["Vt"], float(abs(w32["Vt"][0] - w["Vt"][0]) / w["Vt"][0]))
+    assert errs["E"] <= TOL / 4 and errs["G"] <= TOL / 4
+
+
+def test_islands_put_weight_on_every_strip_edge(wide):
+    """condition 2: every strip edge (rows 64 k - 1 and 64 k) has a cell with E >= 0.02 on each of its two rows and a cell with
+    G >= 0.001 within six rows of it -- a hand-off between strips that went wrong would show, in E and in G"""
+    n, m, th, a, w = wide
+    E, G = w["E"][0], w["G"][0]
+    for edge in range(64, n, 64):
+        assert E[edge - 1].max() >= 0.02 and E[edge].max() >= 0.02, (edge, E[edge - 1].max(), E[edge].max())
+        assert G[max(edge - 6, 0):edge + 6].max() >= 0.001, (edge, G[max(edge - 6, 0):edge + 6].max())
+    assert E.max() < 0.5          # truly local: no cell is on most alignments
 
 
 # ---- the Python wiring over the stand-in engine ----
