@@ -535,6 +535,43 @@ class HipEngine:
         self.call("sdp_soft_local_backward_f32", SOFT_LOCAL_KERNELS[132], dev, state, Vt, Et, E, G, B, N, M, lens, 0)
         return E, G
 
+    def soft_local_adjoint_forward(self, state, Vt, ZE, ZG, shape, lens=None, state_d_out=None):
+        """The adjoint forward sweep over the records of soft_local_forward -> (Vtd (B,), state_d): ZE, ZG (B,N,M) the cotangents
+        of E and G, one of them may be None (zeros); state_d the dot records (opaque float32 tensor of
+        sdp_soft_local_adjoint_state_bytes; state_d_out: a buffer of that size to write into instead of a fresh one)."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        if ZE is None and ZG is None:
+            raise ValueError("soft_local_adjoint_forward: ZE and ZG are both None")
+        check_args(state, torch.float32, (B,), True, Vt=Vt)
+        check_args(state, torch.float32, (B, N, M), ZE=ZE, ZG=ZG)
+        ZE, ZG = (None if z is None else z.detach().contiguous() for z in (ZE, ZG))
+        lens = self._lens(lens, B, state.device)
+        nfloats = max(self.lib.sdp_soft_local_adjoint_state_bytes(B, N, M), 4) // 4
+        check_args(state, torch.float32, (nfloats,), True, ValueError, state_d_out=state_d_out)
+        state_d = torch.empty(nfloats, dtype=torch.float32, device=state.device) if state_d_out is None else state_d_out
+        Vtd = torch.empty(B, dtype=torch.float32, device=state.device)
+        self.call("sdp_soft_local_adjoint_forward_f32", SOFT_LOCAL_ADJOINT_KERNELS[140], dev, state, Vt, ZE, ZG, state_d, Vtd, B, N, M,
+                  lens, 0)
+        return Vtd, state_d
+
+    def soft_local_adjoint_backward(self, state, state_d, Vt, Vtd, Et, shape, lens=None, want_G=True):
+        """The adjoint mirror sweep -> (Ed (B,N,M), Gd (B,N,M) or None): the gradients of <ZE,E> + <ZG,G> with respect to theta and
+        A, +0 outside each pair's block.  state, Vt: of soft_local_forward; state_d, Vtd: of soft_local_adjoint_forward; Et: what
+        soft_local_backward was given."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        check_args(state, torch.float32, (B,), True, Vt=Vt, Vtd=Vtd)
+        check_args(state, torch.float32, None, True, state_d=state_d)
+        check_args(state, Et=Et)
+        Et = Et.detach().to(torch.float32).expand(B).contiguous()
+        lens = self._lens(lens, B, state.device)
+        Ed = torch.empty((B, N, M), dtype=torch.float32, device=state.device)
+        Gd = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if want_G else None
+        self.call("sdp_soft_local_adjoint_backward_f32", SOFT_LOCAL_ADJOINT_KERNELS[141], dev, state, state_d, Vt, Vtd, Et, Ed, Gd,
+                  B, N, M, lens, 0)
+        return Ed, Gd
+
     # ---- alignments sampled from the posterior (include/sdp.h: sdp_sample_paths_*) -------------------
     def sample_paths(self, state, shape, variant, K, lens=None, seed=0, sample0=0, exact_state=False, transposed=False,
                      want_states=True, want_visits=False):
@@ -616,6 +653,8 @@ HARD_LOCAL_KERNELS = {110: "sdp_hard_local_fwd_kernel", 111: "sdp_hard_local_fwd
                       113: "sdp_hard_local_val_t_kernel", 114: "sdp_hard_local_walk_kernel"}
 # kernel id (csrc/sdp_soft_local.h) -> symbol of the soft local operator's kernels
 SOFT_LOCAL_KERNELS = {130: "sdp_soft_local_fwd_kernel", 131: "sdp_soft_local_val_kernel", 132: "sdp_soft_local_bwd_kernel"}
+# the same of its adjoint pair (csrc/sdp_soft_local_adj.hip)
+SOFT_LOCAL_ADJOINT_KERNELS = {140: "sdp_soft_local_adj_fwd_kernel", 141: "sdp_soft_local_adj_bwd_kernel"}
 
 _SWEEPS = ("sdp_forward", "sdp_backward", "sdp_adjoint_forward", "sdp_adjoint_backward")
 # dtype -> (suffix of the four sweeps' entries, their launch labels (float32: where the library's plan is not asked),

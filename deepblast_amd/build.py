@@ -16,9 +16,11 @@ KERNEL_GROUPS = range(1, 11)   # SDP_GROUP = 1 .. 10: the sections of sdp_builds
 SRC = [KERNELS, os.path.join(HERE, "csrc", "sdp_aux.hip"), os.path.join(HERE, "csrc", "sdp_scores.hip"), os.path.join(HERE, "csrc", "sdp_ref.hip"),
        os.path.join(HERE, "csrc", "sdp_comm.hip"), os.path.join(HERE, "csrc", "sdp_targets.hip"),
        os.path.join(HERE, "csrc", "sdp_score.hip"), os.path.join(HERE, "csrc", "sdp_hard.hip"), os.path.join(HERE, "csrc", "sdp_gap.hip"),
-       os.path.join(HERE, "csrc", "sdp_sample.hip"), os.path.join(HERE, "csrc", "sdp_soft_local.hip"), os.path.join(HERE, "csrc", "sdp_api.hip")]
+       os.path.join(HERE, "csrc", "sdp_sample.hip"), os.path.join(HERE, "csrc", "sdp_soft_local.hip"),
+       os.path.join(HERE, "csrc", "sdp_soft_local_adj.hip"), os.path.join(HERE, "csrc", "sdp_api.hip")]
 HDR = [os.path.join(HERE, "csrc", "sdp_kernels.h"), os.path.join(HERE, "csrc", "sdp_device.h"), os.path.join(HERE, "csrc", "sdp_builds.def"), os.path.join(HERE, "csrc", "sdp_hard.h"),
        os.path.join(HERE, "csrc", "sdp_gap.h"), os.path.join(HERE, "csrc", "sdp_sample.h"), os.path.join(HERE, "csrc", "sdp_soft_local.h"),
+       os.path.join(HERE, "csrc", "sdp_soft_local_device.h"),
        os.path.join(ROOT, "include", "sdp.h")]
 OUT = os.path.join(HERE, "libsdp_hip.so")
 

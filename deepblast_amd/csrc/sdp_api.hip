@@ -568,6 +568,19 @@ int raise_scores_limits(int device)
     return 0;
 }
 
+// the soft local operator's adjoint backward sweep keeps two boundary rows per wave (sdp_soft_local::adjoint_lds_bytes): up to
+// 2 x 64 KB, so its limit is raised like the ones above -- by sdp_init, or lazily by the first call
+int raise_soft_local_adjoint_limit(int device)
+{
+    static thread_local unsigned long long raised = 0;
+    if (device < 64 && (raised >> device & 1ull)) return 0;
+    const hipError_t e = hipFuncSetAttribute((const void *)sdp_soft_local_adj_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             160 * 1024);
+    if (e != hipSuccess) return fail_hip(e, "hipFuncSetAttribute(sdp_soft_local_adj_bwd_kernel)");
+    if (device < 64) raised |= 1ull << device;
+    return 0;
+}
+
 // variant | SDP_REF_ROUNDING (sdp_ref.hip): one workgroup of 256 threads per pair, three rolling anti-diagonals of float64
 size_t ref_lds(int M) { return (size_t)3 * (M + 2) * sizeof(double); }
 size_t ref_state_bytes(int B, int N, int M) { return (size_t)B * N * M * 3 * sizeof(float); }
@@ -667,6 +680,9 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_soft_local::ID_FWD: return "sdp_soft_local_fwd_kernel";
     case sdp_soft_local::ID_VAL: return "sdp_soft_local_val_kernel";
     case sdp_soft_local::ID_BWD: return "sdp_soft_local_bwd_kernel";
+    // its adjoint pair (csrc/sdp_soft_local_adj.hip)
+    case sdp_soft_local::ID_ADJ_FWD: return "sdp_soft_local_adj_fwd_kernel";
+    case sdp_soft_local::ID_ADJ_BWD: return "sdp_soft_local_adj_bwd_kernel";
     }
     return nullptr;
 }
@@ -685,7 +701,8 @@ int sdp_init(int device)
     if (device >= 0 && device < MAX_DEV && !status_words(device)) return fail(SDP_E_SELFTEST, "sdp_init: could not create the host-pinned status words");
     for (const Build &b : BUILDS)
         if (int rc = raise_lds_limit(b, device)) return rc;
-    return raise_scores_limits(device);
+    if (int rc = raise_scores_limits(device)) return rc;
+    return raise_soft_local_adjoint_limit(device);
 }
 
 int sdp_device_status(int device, int32_t info[4])
@@ -1466,6 +1483,42 @@ int sdp_soft_local_backward_f32(const void *state, const float *Vt, const float 
                        static_cast<const float4 *>(state), Vt, Et, E, G, lens, N, M, W);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_bwd_kernel");
+    return 0;
+}
+
+// ---- its second order (csrc/sdp_soft_local_adj.hip): the adjoint pair, on the launch geometry of the first order ----
+size_t sdp_soft_local_adjoint_state_bytes(int B, int N, int M) { return sdp_soft_local_state_bytes(B, N, M); }
+
+int sdp_soft_local_adjoint_forward_f32(const void *state, const float *Vt, const float *ZE, const float *ZG, void *state_d, float *Vtd,
+                                       int B, int N, int M, const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!state || !Vt || !state_d || !Vtd || (!ZE && !ZG))
+        return fail(SDP_E_NULLPTR, "sdp_soft_local_adjoint_forward_f32: null pointer (state, Vt, state_d, Vtd; one of ZE, ZG may be NULL)");
+    if (int rc = soft_local_args(B, N, M, flags)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    const int W = soft_local_waves(N, M);
+    hipLaunchKernelGGL(sdp_soft_local_adj_fwd_kernel, dim3(B), dim3(64 * W), sdp_soft_local::sweep_lds_bytes(W, M), (hipStream_t)stream,
+                       static_cast<const float4 *>(state), Vt, ZE, ZG, static_cast<float4 *>(state_d), Vtd, lens, N, M, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_adj_fwd_kernel");
+    return 0;
+}
+
+int sdp_soft_local_adjoint_backward_f32(const void *state, const void *state_d, const float *Vt, const float *Vtd, const float *Et,
+                                        float *Ed, float *Gd, int B, int N, int M, const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!state || !state_d || !Vt || !Vtd || !Et || !Ed)
+        return fail(SDP_E_NULLPTR, "sdp_soft_local_adjoint_backward_f32: null pointer (state, state_d, Vt, Vtd, Et, Ed; Gd may be NULL)");
+    if (int rc = soft_local_args(B, N, M, flags)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = raise_soft_local_adjoint_limit(device)) return rc;
+    const int W = soft_local_waves(N, M);
+    hipLaunchKernelGGL(sdp_soft_local_adj_bwd_kernel, dim3(B), dim3(64 * W), sdp_soft_local::adjoint_lds_bytes(W, M), (hipStream_t)stream,
+                       static_cast<const float4 *>(state), static_cast<const float4 *>(state_d), Vt, Vtd, Et, Ed, Gd, lens, N, M, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_adj_bwd_kernel");
     return 0;
 }
 

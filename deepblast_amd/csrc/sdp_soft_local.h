@@ -1,4 +1,4 @@
-// sdp_soft_local.h -- the soft local operator's kernel family (csrc/sdp_soft_local.hip): launch geometry shared with the host side.
+// sdp_soft_local.h -- the soft local operator's kernel family (csrc/sdp_soft_local.hip, csrc/sdp_soft_local_adj.hip): launch geometry shared with the host side.
 #ifndef SDP_SOFT_LOCAL_H_
 #define SDP_SOFT_LOCAL_H_
 
@@ -11,6 +11,7 @@ namespace sdp_soft_local {
 constexpr int STRIP = 64;        // rows of a strip: one per lane of the wave that sweeps it
 constexpr int CHUNK = 32;        // anti-diagonal steps between two barriers; a lane's scores of a chunk are 32 consecutive floats
 constexpr int HALF = 16;         // steps of the backward sweep's record prefetch and of its E / G stores
+constexpr int ADJ_GROUP = 8;     // the same of the adjoint sweeps (csrc/sdp_soft_local_adj.hip): two record streams, half the depth
 constexpr int MAX_WAVES = 8;     // waves (strips in flight) of a workgroup
 constexpr int KEY = 256;         // progress word of a wave: strip * KEY + chunks done (chunks of a strip <= 66 < KEY)
 constexpr int LDS_BUDGET = 64 * 1024;
@@ -21,11 +22,19 @@ __host__ __device__ inline int strips(int N) { return (N + STRIP - 1) / STRIP; }
 __host__ __device__ inline int chunks(int m) { return (m + STRIP - 1 + CHUNK - 1) / CHUNK; }
 __host__ __device__ inline int row_pitch(int M) { return M + STRIP; }   // floats of one boundary row in LDS
 __host__ __device__ inline size_t sweep_lds_bytes(int waves, int M) { return (size_t)waves * row_pitch(M) * 4 + 2 * MAX_WAVES * 4; }
+// the adjoint backward sweep's ring carries two floats per column, the pushes of E and of Ed: 2 * waves * row_pitch(M) * 4 bytes
+// plus the progress words -- 131008 bytes at eight waves and M = 1982, above the 64 KB a kernel gets unasked (the host raises
+// the kernel's dynamic-LDS attribute; the wave count stays that of sweep_lds_bytes and LDS_BUDGET)
+__host__ __device__ inline size_t adjoint_lds_bytes(int waves, int M) { return 2 * (size_t)waves * row_pitch(M) * 4 + 2 * MAX_WAVES * 4; }
+// (the adjoint pair keeps one value per pair in the dot record of lane 1 at step 0 of chunk 0 of strip 0, which no cell owns:
+// csrc/sdp_soft_local_adj.hip, NORM_SLOT -- a change of this layout must leave it such a record)
 // records of one pair: every step of every chunk of every strip holds a line of 64 (one per lane)
 __host__ __device__ inline size_t pair_records(int N, int M) { return (size_t)strips(N) * chunks(M) * CHUNK * STRIP; }
 
 // kernel ids sdp_kernel_name answers for (the hard family's local kernels keep 110-114, the sampling kernels 120-122)
 enum { ID_FWD = 130, ID_VAL = 131, ID_BWD = 132 };
+// the adjoint pair (csrc/sdp_soft_local_adj.hip); 133 .. 139 answer NULL
+enum { ID_ADJ_FWD = 140, ID_ADJ_BWD = 141 };
 
 }  // namespace sdp_soft_local
 
@@ -36,6 +45,10 @@ __global__ void sdp_soft_local_val_kernel(const float *theta, const float *A, fl
                                           int waves);
 __global__ void sdp_soft_local_bwd_kernel(const float4 *state, const float *Vt, const float *Et, float *E, float *G, const int *lens,
                                           int N, int M, int waves);
+__global__ void sdp_soft_local_adj_fwd_kernel(const float4 *state, const float *Vt, const float *ZE, const float *ZG, float4 *stated,
+                                              float *Vtd, const int *lens, int N, int M, int waves);
+__global__ void sdp_soft_local_adj_bwd_kernel(const float4 *state, const float4 *stated, const float *Vt, const float *Vtd,
+                                              const float *Et, float *Ed, float *Gd, const int *lens, int N, int M, int waves);
 }
 
 #endif  // SDP_SOFT_LOCAL_H_

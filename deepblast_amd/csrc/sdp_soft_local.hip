@@ -28,32 +28,11 @@
 #include <stdint.h>
 
 #include "sdp_soft_local.h"
+#include "sdp_soft_local_device.h"
 
 namespace {
 
 using namespace sdp_soft_local;
-
-constexpr int DPP_WAVE_SHL1 = 0x130;   // lane i <- lane i + 1; lane 63 keeps `old`
-constexpr int DPP_WAVE_SHR1 = 0x138;   // lane i <- lane i - 1; lane 0 keeps `old`
-
-__device__ __forceinline__ float from_upper_lane(float lane0, float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0), __float_as_int(v), DPP_WAVE_SHR1, 0xf, 0xf, false));
-}
-
-__device__ __forceinline__ float from_lower_lane(float lane63, float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane63), __float_as_int(v), DPP_WAVE_SHL1, 0xf, 0xf, false));
-}
-
-__device__ __forceinline__ float of_lane(float v, int lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-struct __attribute__((packed, aligned(4))) F4 {   // four floats at any 4-byte boundary
-    float v[4];
-};
 
 // the scores lane `lane` of strip `s` needs in chunk `c`: columns 32 c - lane .. 32 c - lane + 31 of row 64 s + lane; 0 where
 // the cell does not exist (the value is then never used)

@@ -41,46 +41,110 @@ class SoftLocalFunctionBackward(torch.autograd.Function):
                                   "sdp_soft_local_*) is not built")
 
 
-class SoftLocalFunction(torch.autograd.Function):
-    """Vt = soft_local(theta, A); backward: theta.grad = E = Et . dVt/dtheta, A.grad = G = Et . dVt/dA, one mirror sweep.
-    Once differentiable: differentiating E or G raises NotImplementedError (SoftLocalFunctionBackward)."""
+class SoftLocalAdjoint(torch.autograd.Function):
+    """(Ed, Gd, Vtd) of the adjoint pair (include/sdp.h: sdp_soft_local_adjoint_*): the gradients of <ZE, E> + <ZG, G> with respect
+    to theta, A and Et.  Differentiable in nothing: the third order is not built, and this is the node that says so."""
 
     @staticmethod
-    def forward(ctx, theta, A, lens=None):
+    def forward(ctx, theta, A, Et, ZE, ZG, state, Vt, lens, want_G):
+        # (theta, A, Et, ZE and ZG are here for the graph: a third differentiation must arrive below)
+        eng = _engine.get_engine()
+        shape = tuple(theta.shape)
+        Vtd, state_d = eng.soft_local_adjoint_forward(state, Vt, ZE, ZG, shape, lens)
+        Ed, Gd = eng.soft_local_adjoint_backward(state, state_d, Vt, Vtd, Et, shape, lens, want_G=want_G)
+        return Ed, Gd, Vtd
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError("the soft local operator is second order only: its third order (the derivative of the adjoint "
+                                  "pair sdp_soft_local_adjoint_*) is not built")
+
+
+class SoftLocalFunctionBackward2(torch.autograd.Function):
+    """SoftLocalFunctionBackward for SoftLocalDecoder(second_order=True): the same (E, G), differentiable once more through the
+    adjoint pair.  backward(ZE, ZG) -> the gradients of <ZE, E> + <ZG, G>: Ed for theta, Gd for A, Vtd for Et."""
+
+    @staticmethod
+    def forward(ctx, theta, A, Et, state, Vt, lens, want_E, want_G):
+        shape = tuple(theta.shape)
+        E, G = _engine.get_engine().soft_local_backward(state, Vt, Et, shape, lens, want_G=want_G)
+        ctx.save_for_backward(theta, A, Et, state, Vt)
+        ctx.lens = lens
+        ctx.set_materialize_grads(False)
+        return (E if want_E else None), G
+
+    @staticmethod
+    def backward(ctx, ZE, ZG):
+        theta, A, Et, state, Vt = ctx.saved_tensors
+        none = (None,) * 5
+        if ZE is None and ZG is None:
+            return (None, None, None) + none
+        Ed, Gd, Vtd = SoftLocalAdjoint.apply(theta, A, Et, ZE, ZG, state, Vt, ctx.lens, ctx.needs_input_grad[1])
+        if Vtd.shape != Et.shape:       # Et was broadcast over the batch
+            Vtd = Vtd.sum_to_size(Et.shape)
+        return (Ed if ctx.needs_input_grad[0] else None, Gd, Vtd if ctx.needs_input_grad[2] else None) + none
+
+
+class SoftLocalFunction(torch.autograd.Function):
+    """Vt = soft_local(theta, A); backward: theta.grad = E = Et . dVt/dtheta, A.grad = G = Et . dVt/dA, one mirror sweep.
+    Once differentiable: differentiating E or G raises NotImplementedError (SoftLocalFunctionBackward) -- unless second_order is
+    set: E and G are then differentiable through the adjoint pair (SoftLocalFunctionBackward2), and the third order raises."""
+
+    @staticmethod
+    def forward(ctx, theta, A, lens=None, second_order=False):
         Vt, state = _engine.get_engine().soft_local_forward(theta.detach(), A.detach(), lens)
         ctx.save_for_backward(theta, A, state, Vt)
         ctx.lens = lens
+        ctx.second_order = second_order
         return Vt
 
     @staticmethod
     def backward(ctx, Et):
         theta, A, state, Vt = ctx.saved_tensors
-        E, G = SoftLocalFunctionBackward.apply(theta, A, Et, state, Vt, ctx.lens, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        return E, G, None
+        if ctx.second_order:
+            # (Vt detached: the adjoint pair carries the whole derivative, and this node is not to be visited again for it)
+            E, G = SoftLocalFunctionBackward2.apply(theta, A, Et, state, Vt.detach(), ctx.lens, ctx.needs_input_grad[0],
+                                                    ctx.needs_input_grad[1])
+        else:
+            E, G = SoftLocalFunctionBackward.apply(theta, A, Et, state, Vt, ctx.lens, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return E, G, None, None
 
 
 class SoftLocalDecoder(torch.nn.Module):
     """Local alignment scores, their gradients and the posterior alignment matrix, on a ROCm device in float32.
 
     forward(theta, A, lengths=None) -> Vt (B,), differentiable ONCE in theta and A: theta.grad = E, A.grad = G, both true gradients
-    (this operator has no pass-through convention for A).  The second order is not built: differentiating a gradient raises.
+    (this operator has no pass-through convention for A).  Differentiating a gradient raises, unless second_order is set.
     decode(theta, A, lengths=None)  -> E (B, N, M) for Et = 1: E[b, i, j] is the posterior probability that cell (i, j) lies on the
-    alignment of pair b.  No autograd graph.
+    alignment of pair b.  No autograd graph, unless second_order is set.
+    second_order=True: forward() is differentiable TWICE and decode() returns E with a graph, so that a loss on the alignment
+    matrix -- loss(first, dec.decode(theta, A, lengths), x_len, y_len, G).backward() -- trains theta and A: the gradients come
+    from the adjoint pair (sdp_soft_local_adjoint_*), true ones for both.  The third order is not built and raises.
     score(theta, A, lengths=None)   -> Vt (B,) through the value-only sweep: no state is allocated, no graph.
     theta finite; A finite or -inf (a forbidden gap: G is exactly 0 there).
     lengths (B, 2): pair b is theta[b, :n_b, :m_b]; E and G are +0 outside it, and an empty pair has Vt = 0.  Problems wider than
     the column limit (2048) are swept transposed -- the operator is symmetric under transposition with x <-> y -- and the results
     come back in the caller's coordinates; both sides above the limit raise ValueError."""
 
+    def __init__(self, second_order=False):
+        super().__init__()
+        self.second_order = bool(second_order)
+
     def forward(self, theta, A, lengths=None):
         _validate(theta, A)
         theta, A, lengths, _ = _Decoder._oriented(theta, A, lengths)
-        return SoftLocalFunction.apply(theta, A, lengths)
+        return SoftLocalFunction.apply(theta, A, lengths, self.second_order)
 
     def decode(self, theta, A, lengths=None):
         _validate(theta, A)
         theta, A, lengths, transposed = _Decoder._oriented(theta, A, lengths)
         eng = _engine.get_engine()
+        if self.second_order and torch.is_grad_enabled() and (theta.requires_grad or A.requires_grad):
+            # E with a graph: the first-order pair outside autograd, then the node the adjoint pair hangs on (Et = 1)
+            Vt, state = eng.soft_local_forward(theta.detach(), A.detach(), lengths)
+            one = torch.ones(theta.shape[0], dtype=torch.float32, device=theta.device)
+            E, _ = SoftLocalFunctionBackward2.apply(theta, A, one, state, Vt, lengths, True, False)
+            return E.transpose(1, 2) if transposed else E
         with torch.no_grad():
             theta, A = theta.detach(), A.detach()
             Vt, state = eng.soft_local_forward(theta, A, lengths)

@@ -448,7 +448,7 @@ int sdp_hard_local_walk_f32(const void *state, const int32_t *ends, const float 
  *     G[i,j]  = E[i,j] (q_x[i,j] + q_y[i,j])                                                          = Et dVt/dA[i,j]
  * E / Et is the posterior probability that the cell lies on the alignment.  E and G are +0 outside the pair's [:n, :m] block (the
  * backward kernel writes them; there is no SDP_NO_FILL here); a pair with n < 1 or m < 1 has Vt = 0 and E = G = 0.  fp32 only;
- * theta finite; A finite or -inf (a forbidden gap: G is exactly 0 there); first order only (no adjoint pair).  No floating-point
+ * theta finite; A finite or -inf (a forbidden gap: G is exactly 0 there); the second order is the adjoint pair below.  No floating-point
  * atomics: two calls on the same inputs give the same bits, and sdp_soft_local_forward_value_f32 gives the bits of
  * sdp_soft_local_forward_f32's Vt.
  *   state    sdp_soft_local_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: four floats per cell {q_x, q_m, q_y,
@@ -466,6 +466,40 @@ int sdp_soft_local_forward_value_f32(const float *theta, const float *A, float *
                                      int device, void *stream);
 int sdp_soft_local_backward_f32(const void *state, const float *Vt, const float *Et, float *E, float *G, int B, int N, int M,
                                 const int32_t *lens, int flags, int device, void *stream);
+
+/* Its SECOND ORDER (csrc/sdp_soft_local_adj.hip): the adjoint pair, for a loss on E or G.  (Added after SDP_VERSION
+ * 106 without a version change: look the symbols up.)  Given cotangents ZE on E and ZG on G, both (B, N, M) and ignored outside a
+ * pair's block, with the records q, V and w = exp(V - Vt) of the forward sweep, quantities outside the table being 0:
+ *   adjoint forward (the direction of the forward sweep):
+ *     u_x = ZG[i,j] + Vd[i-1,j]     u_m = Vd[i-1,j-1]     u_y = ZG[i,j] + Vd[i,j-1]              (the restart term has u = 0)
+ *     ub  = q_x u_x + q_m u_m + q_y u_y;     Vd[i,j] = ZE[i,j] + ub;     qd_k[i,j] = q_k[i,j] (u_k - ub),  k = x, m, y
+ *     Vtd = sum over cells of w[i,j] Vd[i,j]                       (= (<ZE,E> + <ZG,G>) / Et, but defined for Et = 0 too)
+ *   adjoint backward (the mirror sweep; E is re-formed beside Ed by the first-order recurrence, it is not read):
+ *     Ed[i,j] = Et w[i,j] (Vd[i,j] - Vtd) + qd_x[i+1,j] E[i+1,j] + q_x[i+1,j] Ed[i+1,j] + qd_m[i+1,j+1] E[i+1,j+1]
+ *               + q_m[i+1,j+1] Ed[i+1,j+1] + qd_y[i,j+1] E[i,j+1] + q_y[i,j+1] Ed[i,j+1]
+ *     Gd[i,j] = Ed[i,j] (q_x + q_y)[i,j] + E[i,j] (qd_x + qd_y)[i,j]
+ * With L = <ZE,E> + <ZG,G>: dL/dtheta = Ed, dL/dA = Gd, dL/dEt = Vtd.  Ed and Gd are +0 outside the pair's block, an empty pair has
+ * Vtd = 0.  The third order is not built.  No floating-point atomics: two calls give the same bits.
+ * Both sweeps take w from the records alone: exp(-Vt) + sum over cells of exp(V - Vt) is 1 by the definition of Vt, and the adjoint
+ * forward sweep divides by what it finds that sum to be (in fp32 it misses 1 by the rounding of Vt, half an ulp of a Vt of several
+ * hundred being 1e-5 on every w at once), so that the w of both sweeps sum to 1 - exp(-Vt).
+ *   state    what sdp_soft_local_forward_f32 wrote, with the Vt it wrote; same B, N, M, lens throughout.
+ *   state_d  sdp_soft_local_adjoint_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: four floats per cell
+ *            {qd_x, qd_m, qd_y, Vd} in the layout of `state`, private; written by the adjoint forward entry (cells of a pair's
+ *            block, and one record per pair that no cell owns, for the normaliser), read by the adjoint backward entry (no others).
+ *   ZE, ZG   one of them may be NULL: zeros.  Both NULL: SDP_E_NULLPTR.
+ *   Vtd      (B,): written by the adjoint forward entry, READ by the adjoint backward entry.
+ *   Gd       (B, N, M) or NULL.
+ *   flags    none is defined: any bit is refused (SDP_E_VARIANT).
+ * The launch geometry is that of the first order; the adjoint backward kernel keeps two boundary rows per wave in LDS (up to 131008
+ * bytes), for which the entry raises the kernel's dynamic-LDS limit (sdp_init does it too, before a stream capture).  Argument
+ * checks as above, before any device call: SDP_E_NULLPTR, SDP_E_SHAPE, SDP_E_MAXCOLS, SDP_E_VARIANT, SDP_E_TOOBIG. */
+size_t sdp_soft_local_adjoint_state_bytes(int B, int N, int M);
+int sdp_soft_local_adjoint_forward_f32(const void *state, const float *Vt, const float *ZE, const float *ZG, void *state_d, float *Vtd,
+                                       int B, int N, int M, const int32_t *lens, int flags, int device, void *stream);
+int sdp_soft_local_adjoint_backward_f32(const void *state, const void *state_d, const float *Vt, const float *Vtd, const float *Et,
+                                        float *Ed, float *Gd, int B, int N, int M, const int32_t *lens, int flags, int device,
+                                        void *stream);
 
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept
