@@ -572,6 +572,51 @@ class HipEngine:
                   B, N, M, lens, 0)
         return Ed, Gd
 
+    # ---- alignments sampled from its posterior (include/sdp.h: sdp_soft_local_end_tables_f32, sdp_soft_local_sample_paths_f32) ----
+    def soft_local_end_tables(self, state, Vt, shape, lens=None, cdf_out=None, rows_out=None):
+        """The end-cell tables over the records of soft_local_forward -> (cdf (B,N,M), rows (B,N+1)) fp32: the running sums of
+        w = exp(V - Vt) along every row, and of the rows' totals from exp(-Vt) on.  Only entries inside a pair's block are
+        written; fresh tensors are zero outside.  cdf_out / rows_out: buffers to write into instead of fresh ones."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        check_args(state, torch.float32, (B,), True, Vt=Vt)
+        check_args(state, torch.float32, (B, N, M), True, ValueError, cdf_out=cdf_out)
+        check_args(state, torch.float32, (B, N + 1), True, ValueError, rows_out=rows_out)
+        lens = self._lens(lens, B, state.device)
+        new = torch.empty if lens is None else torch.zeros      # (without lengths every entry is written)
+        cdf = new((B, N, M), dtype=torch.float32, device=state.device) if cdf_out is None else cdf_out
+        rows = new((B, N + 1), dtype=torch.float32, device=state.device) if rows_out is None else rows_out
+        self.call("sdp_soft_local_end_tables_f32", SOFT_LOCAL_SAMPLE_KERNELS[134], dev, state, Vt, cdf, rows, B, N, M, lens, 0)
+        return cdf, rows
+
+    def soft_local_sample_paths(self, state, cdf, rows, shape, K, lens=None, seed=0, sample0=0, want_states=True, want_visits=False,
+                                want_ends=False):
+        """K local alignments per pair drawn from the posterior, on the `state` of soft_local_forward and the tables of
+        soft_local_end_tables -> (states (B,K,cap,3) int32 or None, counts (B,K) int32 or None, visits (B,N,M) int32 or None,
+        ends (B,K,2) int32 or None).  Sample (b, k) is sample number sample0 + k of pair b under `seed` whatever K is; its list
+        -- the path alone, start first -- is RIGHT-aligned in states[b, k]: rows cap-1-counts[b,k] .. cap-2, and row cap-1 holds
+        (number of path cells, i, j of the first one), (0, -1, -1) for an empty sample; rows in front of the list are
+        unspecified.  ends: the end cell, (-1, -1) for an empty sample.  visits: how many of the K paths pass through each cell."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        if not (want_states or want_visits or want_ends):
+            raise ValueError("soft_local_sample_paths: nothing asked for (want_states, want_visits, want_ends)")
+        check_args(state, torch.float32, (B, N, M), True, ValueError, cdf=cdf)
+        check_args(state, torch.float32, (B, N + 1), True, ValueError, rows=rows)
+        lens = self._lens(lens, B, state.device)
+        states = counts = visits = ends = None
+        if want_states:
+            cap = self.lib.sdp_traceback_capacity(N, M)
+            states = torch.empty((B, int(K), cap, 3), dtype=torch.int32, device=state.device)
+            counts = torch.empty((B, int(K)), dtype=torch.int32, device=state.device)
+        if want_visits:
+            visits = torch.zeros((B, N, M), dtype=torch.int32, device=state.device)
+        if want_ends:
+            ends = torch.empty((B, int(K), 2), dtype=torch.int32, device=state.device)
+        self.call("sdp_soft_local_sample_paths_f32", SOFT_LOCAL_SAMPLE_KERNELS[135], dev, state, cdf, rows, states, counts, visits, ends,
+                  B, N, M, int(K), int(sample0), int(seed) & 0xffffffffffffffff, lens, 0)
+        return states, counts, visits, ends
+
     # ---- alignments sampled from the posterior (include/sdp.h: sdp_sample_paths_*) -------------------
     def sample_paths(self, state, shape, variant, K, lens=None, seed=0, sample0=0, exact_state=False, transposed=False,
                      want_states=True, want_visits=False):
@@ -655,6 +700,8 @@ HARD_LOCAL_KERNELS = {110: "sdp_hard_local_fwd_kernel", 111: "sdp_hard_local_fwd
 SOFT_LOCAL_KERNELS = {130: "sdp_soft_local_fwd_kernel", 131: "sdp_soft_local_val_kernel", 132: "sdp_soft_local_bwd_kernel"}
 # the same of its adjoint pair (csrc/sdp_soft_local_adj.hip)
 SOFT_LOCAL_ADJOINT_KERNELS = {140: "sdp_soft_local_adj_fwd_kernel", 141: "sdp_soft_local_adj_bwd_kernel"}
+# and of the kernels that sample from its posterior (csrc/sdp_soft_local_sample.h)
+SOFT_LOCAL_SAMPLE_KERNELS = {134: "sdp_soft_local_tables_kernel", 135: "sdp_soft_local_sample_kernel"}
 
 _SWEEPS = ("sdp_forward", "sdp_backward", "sdp_adjoint_forward", "sdp_adjoint_backward")
 # dtype -> (suffix of the four sweeps' entries, their launch labels (float32: where the library's plan is not asked),

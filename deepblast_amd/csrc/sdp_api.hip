@@ -14,6 +14,7 @@
 #include "sdp_sample.h"
 #include "sdp_hard.h"
 #include "sdp_soft_local.h"
+#include "sdp_soft_local_sample.h"
 #include "sdp_kernels.h"
 
 namespace {
@@ -683,6 +684,9 @@ const char *sdp_kernel_name(int kernel_id)
     // its adjoint pair (csrc/sdp_soft_local_adj.hip)
     case sdp_soft_local::ID_ADJ_FWD: return "sdp_soft_local_adj_fwd_kernel";
     case sdp_soft_local::ID_ADJ_BWD: return "sdp_soft_local_adj_bwd_kernel";
+    // sampling from its posterior (csrc/sdp_soft_local_sample.hip)
+    case sdp_soft_local_sample::ID_TABLES: return "sdp_soft_local_tables_kernel";
+    case sdp_soft_local_sample::ID_SAMPLE: return "sdp_soft_local_sample_kernel";
     }
     return nullptr;
 }
@@ -1519,6 +1523,50 @@ int sdp_soft_local_adjoint_backward_f32(const void *state, const void *state_d, 
                        static_cast<const float4 *>(state), static_cast<const float4 *>(state_d), Vt, Vtd, Et, Ed, Gd, lens, N, M, W);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_adj_bwd_kernel");
+    return 0;
+}
+
+// ---- alignments sampled from its posterior (csrc/sdp_soft_local_sample.hip): the end-cell tables, then one walk per sample ----
+int sdp_soft_local_end_tables_f32(const void *state, const float *Vt, float *cdf, float *rows, int B, int N, int M, const int32_t *lens,
+                                  int flags, int device, void *stream)
+{
+    if (!state || !Vt || !cdf || !rows) return fail(SDP_E_NULLPTR, "sdp_soft_local_end_tables_f32: null pointer (state, Vt, cdf, rows)");
+    if (int rc = soft_local_args(B, N, M, flags)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    // cdf by one wave per (pair, strip); then, behind it on the stream, rows by one wave per pair
+    const unsigned waves = (unsigned)B * (unsigned)sdp_soft_local::strips(N);   // <= B N <= 2^31 / M
+    for (int pass = 0; pass < 2; ++pass) {
+        hipLaunchKernelGGL(sdp_soft_local_tables_kernel, dim3(pass ? (unsigned)B : waves), dim3(sdp_soft_local_sample::LANES), 0,
+                           (hipStream_t)stream, static_cast<const float4 *>(state), Vt, cdf, rows, lens, N, M, pass);
+        e = hipGetLastError();
+        if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_tables_kernel");
+    }
+    return 0;
+}
+
+int sdp_soft_local_sample_paths_f32(const void *state, const float *cdf, const float *rows, int32_t *states, int32_t *counts,
+                                    int32_t *visits, int32_t *ends, int B, int N, int M, int K, int sample0, uint64_t seed,
+                                    const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!state || !cdf || !rows || (states && !counts) || (!states && !counts && !visits && !ends))
+        return fail(SDP_E_NULLPTR, "sdp_soft_local_sample_paths_f32: null pointer (state, cdf, rows; states with counts, or visits, or ends)");
+    if (int rc = soft_local_args(B, N, M, flags)) return rc;
+    if (K < 1 || sample0 < 0 || (long long)sample0 + K > 0x7fffffffLL)
+        return fail(SDP_E_SHAPE, "sdp_soft_local_sample_paths_f32: K must be positive, sample0 non-negative and sample0 + K below 2^31");
+    const int cap = sdp_traceback_capacity(N, M);
+    const size_t lim = 0x7fffffffu, waves = (size_t)B * ((K + sdp_soft_local_sample::LANES - 1) / sdp_soft_local_sample::LANES);
+    if ((states && (size_t)B * K * cap * 3 > lim) || (size_t)B * K * 2 > lim || waves > lim)
+        return fail(SDP_E_TOOBIG, "sdp_soft_local_sample_paths_f32: an output exceeds 2^31 elements");
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    sdp_soft_local_sample::Params g = {};
+    g.state = static_cast<const float4 *>(state), g.cdf = cdf, g.rows = rows;
+    g.states = states, g.counts = counts, g.visits = visits, g.ends = ends, g.lens = lens, g.seed = seed;
+    g.B = B, g.N = N, g.M = M, g.K = K, g.sample0 = sample0, g.cap = cap;
+    hipLaunchKernelGGL(sdp_soft_local_sample_kernel, dim3((unsigned)waves), dim3(sdp_soft_local_sample::LANES), 0, (hipStream_t)stream, g);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_sample_kernel");
     return 0;
 }
 

@@ -33,7 +33,8 @@ __host__ __device__ inline size_t pair_records(int N, int M) { return (size_t)st
 
 // kernel ids sdp_kernel_name answers for (the hard family's local kernels keep 110-114, the sampling kernels 120-122)
 enum { ID_FWD = 130, ID_VAL = 131, ID_BWD = 132 };
-// the adjoint pair (csrc/sdp_soft_local_adj.hip); 133 .. 139 answer NULL
+// the adjoint pair (csrc/sdp_soft_local_adj.hip); 134 and 135 are the sampling kernels' (csrc/sdp_soft_local_sample.h), 133 and
+// 136 .. 139 answer NULL
 enum { ID_ADJ_FWD = 140, ID_ADJ_BWD = 141 };
 
 }  // namespace sdp_soft_local

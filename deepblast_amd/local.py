@@ -121,6 +121,8 @@ class SoftLocalDecoder(torch.nn.Module):
     matrix -- loss(first, dec.decode(theta, A, lengths), x_len, y_len, G).backward() -- trains theta and A: the gradients come
     from the adjoint pair (sdp_soft_local_adjoint_*), true ones for both.  The third order is not built and raises.
     score(theta, A, lengths=None)   -> Vt (B,) through the value-only sweep: no state is allocated, no graph.
+    sample_paths(theta, A, num_samples, ...) / sample_alignments(...) -> local alignments drawn from the posterior whose marginals
+    decode() returns: the end cell is a draw, the walk may stop at every cell, a sample may be empty.  No graph.
     theta finite; A finite or -inf (a forbidden gap: G is exactly 0 there).
     lengths (B, 2): pair b is theta[b, :n_b, :m_b]; E and G are +0 outside it, and an empty pair has Vt = 0.  Problems wider than
     the column limit (2048) are swept transposed -- the operator is symmetric under transposition with x <-> y -- and the results
@@ -157,3 +159,50 @@ class SoftLocalDecoder(torch.nn.Module):
         theta, A, lengths, _ = _Decoder._oriented(theta, A, lengths)
         with torch.no_grad():
             return _engine.get_engine().soft_local_forward_value(theta.detach(), A.detach(), lengths)
+
+    def sample_paths(self, theta, A, num_samples, lengths=None, seed=0, sample0=0, return_visits=False, return_ends=False):
+        """Local alignments drawn from the POSTERIOR this operator defines -- the empty alignment with probability exp(-Vt), a
+        path with exp(score - Vt); decode() returns its marginals, Decoder('hardmax', local=True).optimal_paths() its mode -- from
+        one forward sweep, the end-cell tables and one walk per sample (include/sdp.h: sdp_soft_local_end_tables_f32,
+        sdp_soft_local_sample_paths_f32; no backward sweep, no E).  -> (Vt (B,), states (B, K, cap, 3) int32, counts (B, K)
+        int32[, visits (B, N, M) int32][, ends (B, K, 2) int32]), K = num_samples, device tensors without an autograd graph: sample k
+        of pair b is states[b, k, :counts[b, k]], rows (i, j, state), the path alone, start first, in the format of
+        optimal_paths(local=True) (rows between the list and the last one are unspecified); states[b, k, cap - 1] is (number of
+        path cells, i, j of the first one), (0, -1, -1) for an empty sample, which has counts = 0.  The start cell carries state m
+        (1).  visits: how many of the K paths pass through each cell -- visits / K estimates decode()'s matrix.  ends: the end
+        cell of every sample, (-1, -1) for an empty one.
+        The draws are reproducible: sample k is sample number sample0 + k of pair b under `seed` (a counter-based generator: 64
+        samples at sample0 = 0 are 32 at 0 followed by 32 at 32).
+        Problems wider than the column limit are swept transposed by forward() and decode(); sampling them is NOT built (the end
+        tables would need running sums across the lanes of the transposed state, and the draw must not depend on the sweep
+        direction): ValueError."""
+        _validate(theta, A)
+        K = int(num_samples)
+        if K < 1:
+            raise ValueError(f"num_samples must be positive, got {num_samples}")
+        eng = _engine.get_engine()
+        if theta.shape[2] > eng.max_cols():
+            raise ValueError(f"sample_paths is out of scope for problems swept transposed (M = {theta.shape[2]} exceeds the column "
+                             f"limit {eng.max_cols()}): sampling on a transposed state is not built")
+        with torch.no_grad():
+            theta, A = theta.detach(), A.detach()
+            shape = tuple(theta.shape)
+            Vt, state = eng.soft_local_forward(theta, A, lengths)
+            cdf, rows = eng.soft_local_end_tables(state, Vt, shape, lengths)
+            states, counts, visits, ends = eng.soft_local_sample_paths(state, cdf, rows, shape, K, lengths, seed=seed, sample0=sample0,
+                                                                       want_visits=bool(return_visits), want_ends=bool(return_ends))
+            # the lists come right-aligned (every sample wrote from the end): one gather moves them to the front, the last row stays
+            cap = states.shape[2]
+            row = torch.arange(cap, device=states.device)[None, None, :]
+            cnt = counts.long()[..., None]
+            src = torch.where(row < cnt, row + (cap - 1 - cnt), torch.full_like(row, cap - 1))
+            states = torch.gather(states, 2, src[..., None].expand(-1, -1, -1, 3))
+        return (Vt, states, counts) + ((visits,) if return_visits else ()) + ((ends,) if return_ends else ())
+
+    def sample_alignments(self, theta, A, num_samples, lengths=None, seed=0, sample0=0):
+        """sample_paths() as Decoder.sample_alignments() returns its walks: (Vt, list of B lists of K lists of (i, j, state)); an
+        empty sample is an empty list."""
+        Vt, states, counts = self.sample_paths(theta, A, num_samples, lengths, seed, sample0)
+        states, counts = states.cpu().numpy(), counts.cpu().numpy()
+        return Vt, [[[tuple(int(v) for v in row) for row in states[b, k, :counts[b, k]]] for k in range(counts.shape[1])]
+                    for b in range(counts.shape[0])]

@@ -501,6 +501,61 @@ int sdp_soft_local_adjoint_backward_f32(const void *state, const void *state_d, 
                                         float *Ed, float *Gd, int B, int N, int M, const int32_t *lens, int flags, int device,
                                         void *stream);
 
+/* Alignments SAMPLED from its posterior (csrc/sdp_soft_local_sample.hip): what sdp_sample_paths_* is to the soft
+ * global operator.  (Added after SDP_VERSION 106 without a version change: look the symbols up.  sdp_kernel_name answers 134 and
+ * 135 for their kernels.)  The operator defines a distribution over local alignments: the empty one has probability exp(-Vt), a path
+ * exp(score - Vt); E / Et is its marginals.  A sample is drawn backwards: the END cell first, with weights w = exp(V - Vt), then a
+ * walk along the records that stops with the restart weight -- "the alignment starts here".
+ * For pair b, (n, m) = lens[b] clamped to [0, N] x [0, M], or (N, M); cells 0-based; U(seed, pair, sample, t) the generator of
+ * sdp_sample_paths_* (sdp_sample_uniform is its host twin); the sample number of sample k is sample0 + k.
+ * TABLES (sdp_soft_local_end_tables_f32, from the state and the Vt that sdp_soft_local_forward_f32 wrote), row-major float32:
+ *     cdf (B, N, M)    cdf[b,i,j]  = the running sum along row i of expf(V[i,j'] - Vt[b]) for j' = 0 .. j, formed by sequential
+ *                      fp32 adds in increasing j'
+ *     rows (B, N + 1)  rows[b,0]   = expf(-Vt[b]);  rows[b,i+1] = rows[b,i] + cdf[b,i,m-1], by sequential fp32 adds
+ * Both are non-decreasing by construction (an fp32 add of a non-negative number never lowers a sum), which the searches below
+ * rely on.  Only entries inside the pair's block are written -- cdf: i < n and j < m; rows: index <= n -- and the others are
+ * left untouched; a pair with n < 1 or m < 1 has rows[b,0] = 1 and nothing else.  No floating-point atomics: the same bits on
+ * every call.
+ * END CELL, a pure function of the tables and two uniforms:
+ *     t = 0:  g = U(.., 0) * rows[b,n]      (one fp32 multiply).  g < rows[b,0]: the sample is the EMPTY alignment.  Otherwise i is
+ *             the first row with g < rows[b,i+1], or n - 1 if there is none.
+ *     t = 1:  h = U(.., 1) * cdf[b,i,m-1].  j is the first column with h < cdf[b,i,j], or m - 1 if there is none.
+ * A pair with n < 1 or m < 1 gives only empty samples.  The draws divide by the totals the tables hold: in fp32 those miss 1 by the
+ * rounding of Vt (up to about 1e-5), and dividing keeps that off the result, as the adjoint pair above does.
+ * WALK, from (i, j), for t = 2, 3, ..., with the cell's record {q_x, q_m, q_y, V} and u = U(.., t):
+ *     u < q_x                  the cell was entered through x (0): go to (i-1, j)
+ *     else u < q_x + q_y       (one fp32 add) through y (2): go to (i, j-1)
+ *     else u < (q_x + q_y) + q_m   through m (1): go to (i-1, j-1)
+ *     else                     stop: this cell is the alignment's START; it pays no gap score and is recorded with state m (1)
+ * The records have q = 0 towards anything outside the table, and A = -inf gives an exact 0: the walk never leaves the block and
+ * never enters a cell through a forbidden gap; every step lowers i or j, so it ends after at most n + m - 1 cells.  (The kernel
+ * also ends a walk at the block's edge: a buffer that is not a state is not read out of bounds.)  NaN weights: unspecified.
+ * OUTPUTS, in the format of sdp_hard_local_walk_f32 -- the path alone, start first, no padding:
+ *   states   (B, K, cap, 3) int32 or NULL, cap = sdp_traceback_capacity(N, M).  The list of sample (b, k) is RIGHT-aligned: rows
+ *            cap-1-counts[b,k] .. cap-2, rows (i, j, state), start first (every lane writes from the end and never moves a
+ *            record); its last row is the end cell.  Row cap-1 holds (number of path cells, i, j of the first cell), (0, -1, -1)
+ *            for an empty sample.  Rows in front of the list are not written.
+ *   counts   (B, K) int32: the number of path cells, 0 for an empty sample; required with states.
+ *   visits   (B, N, M) int32 or NULL: + 1 per path cell of every sample, by no-return integer atomic adds -- the caller zeroes
+ *            it; the result is deterministic.  visits / K estimates E (Et = 1).
+ *   ends     (B, K, 2) int32 or NULL: the end cell (i, j), (-1, -1) for an empty sample.
+ *   If nothing is asked for (states, counts, visits and ends all NULL): SDP_E_NULLPTR.
+ * A sample depends on (seed, pair, sample number) and the tables alone: the same call twice gives the same tensors, and K = 64 at
+ * sample0 = 0 equals 32 at 0 joined with 32 at 32.
+ *   state, Vt  what sdp_soft_local_forward_f32 wrote; cdf, rows: what sdp_soft_local_end_tables_f32 wrote from them; same B, N, M,
+ *              lens throughout.
+ *   flags    none is defined: any bit is refused (SDP_E_VARIANT).
+ * K >= 1 and sample0 >= 0 (and sample0 + K < 2^31), else SDP_E_SHAPE; an output of more than 2^31 - 1 elements: SDP_E_TOOBIG.  All
+ * arguments are checked before any device call, with the family's codes: SDP_E_NULLPTR, SDP_E_SHAPE, SDP_E_MAXCOLS, SDP_E_VARIANT,
+ * SDP_E_TOOBIG.  Tables: one wave per strip of 64 rows, then one per pair; samples: one wave per 64 samples of a pair.
+ * A problem that was swept TRANSPOSED (M above sdp_max_cols()) is out of scope: the running sums along the caller's rows would be
+ * sums across the lanes of the transposed state, and a draw that depended on the sweep direction would not be the same draw. */
+int sdp_soft_local_end_tables_f32(const void *state, const float *Vt, float *cdf, float *rows, int B, int N, int M, const int32_t *lens,
+                                  int flags, int device, void *stream);
+int sdp_soft_local_sample_paths_f32(const void *state, const float *cdf, const float *rows, int32_t *states, int32_t *counts,
+                                    int32_t *visits, int32_t *ends, int B, int N, int M, int K, int sample0, uint64_t seed,
+                                    const int32_t *lens, int flags, int device, void *stream);
+
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept
  * for callers who are short of memory, not of time; deepblast_amd.losses uses the unfused kernels by default.

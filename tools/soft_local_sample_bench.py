@@ -1,0 +1,92 @@
+#!/usr/bin/env python
+"""What a sample from the soft local operator's posterior costs, beside its forward sweep and beside the global sampler, on one GPU,
+interleaved in one process.
+usage: python tools/soft_local_sample_bench.py [REPS=5] [ITERS=20] [OUT=profiles/soft_local_sample_bench.json]
+On NW 256 x 512^2 (BASELINE.json configs[1]'s scores), us per call (min / median / max over REPS interleaved rounds of ITERS
+back-to-back calls, HIP events, 10 warm calls in front of every timed loop) of
+  SLf            the soft local forward sweep with its records (into a buffer kept between calls),
+  tables         HipEngine.soft_local_end_tables alone: both launches, cdf and rows into buffers kept between calls,
+  sample_K64     HipEngine.soft_local_sample_paths on that state and those tables, K = 64, lists and counts (no visits, no ends),
+  sample_K1024v  ... K = 1024, visits only (the zeroing of visits included),
+  module_K64     SoftLocalDecoder.sample_paths, K = 64: forward sweep, tables, samples and the gather that left-aligns the lists,
+  Gf, G_sample_K64   the global soft forward sweep (packed state) and HipEngine.sample_paths on its state, K = 64, lists and counts,
+and from them walks per second, the time per walk step (steps = path cells, read from the results) and the table kernel's
+algorithmic bytes: 4 B read per cell as the algorithm needs them, 16 B as the 128-byte lines of the state arrive, 4 B written.
+A first measurement: there is no target.  Writes OUT with the source stamp."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import datagen  # noqa: E402
+import source_stamp  # noqa: E402
+from deepblast_amd._engine import NW, get_engine  # noqa: E402
+from deepblast_amd.local import SoftLocalDecoder  # noqa: E402
+from value_bench import interleaved, mmm  # noqa: E402
+
+arg = {a.split("=")[0]: a.split("=")[1] for a in sys.argv[1:] if "=" in a}
+REPS, ITERS = int(arg.get("REPS", 5)), int(arg.get("ITERS", 20))
+OUT = os.path.join(ROOT, arg.get("OUT", "profiles/soft_local_sample_bench.json"))
+
+
+def main():
+    B, N, M = 256, 512, 512
+    shape = (B, N, M)
+    eng = get_engine()
+    dec = SoftLocalDecoder()
+    th, A = datagen.theta_A(1, B, N, M)
+    th, A = torch.from_numpy(th).cuda(), torch.from_numpy(A).cuda()
+    Vt, state = eng.soft_local_forward(th, A)
+    cdf, rows = eng.soft_local_end_tables(state, Vt, shape)
+    _, Q = eng.forward(th, A, NW)
+
+    cands = {"SLf": lambda: eng.soft_local_forward(th, A, state_out=state),
+             "tables": lambda: eng.soft_local_end_tables(state, Vt, shape, cdf_out=cdf, rows_out=rows),
+             "sample_K64": lambda: eng.soft_local_sample_paths(state, cdf, rows, shape, 64, seed=1),
+             "sample_K1024v": lambda: eng.soft_local_sample_paths(state, cdf, rows, shape, 1024, seed=1, want_states=False, want_visits=True),
+             "module_K64": lambda: dec.sample_paths(th, A, 64, seed=1),
+             "Gf": lambda: eng.forward(th, A, NW),
+             "G_sample_K64": lambda: eng.sample_paths(Q, shape, NW, 64, seed=1)}
+    states, counts, _, _ = cands["sample_K64"]()
+    _, _, visits, _ = cands["sample_K1024v"]()
+    torch.cuda.synchronize()
+    steps = {"sample_K64": int(counts.sum()), "sample_K1024v": int(visits.sum())}
+    empty = int((counts == 0).sum())
+    del states, counts, visits
+    r = interleaved(cands, REPS, ITERS)
+    doc = {"_stamp": {"source_sha256": source_stamp.source_sha()},
+           "_note": f"NW {B} x {N} x {M}; us per call, {REPS} interleaved rounds of {ITERS} back-to-back calls each (HIP events); "
+                    "tools/soft_local_sample_bench.py.  A first measurement, no target.",
+           "device": torch.cuda.get_device_name(0), "us": {k: dict(mmm(v), reps=v) for k, v in r.items()}, "walks": {}}
+    slf = np.median(r["SLf"])
+    for name, K in (("sample_K64", 64), ("sample_K1024v", 1024)):
+        us = np.median(r[name])
+        doc["walks"][name] = {"K": K, "walks": B * K, "steps": steps[name], "mean_steps_per_walk": steps[name] / (B * K),
+                              "walks_per_s": B * K / (us * 1e-6), "ns_per_walk_step": us * 1e3 / steps[name],
+                              "call_ns_per_step_of_a_walk": us * 1e3 / (steps[name] / (B * K)),
+                              "soft_local_forward_sweeps_per_call": us / slf}
+    doc["walks"]["sample_K64"]["empty_samples"] = empty
+    cells, us = B * N * M, np.median(r["tables"])
+    doc["tables"] = {"soft_local_forward_sweeps_per_call": us / slf, "cells": cells,
+                     "TBps_algorithmic_8B_per_cell": cells * 8 / (us * 1e-6) / 1e12,
+                     "TBps_with_whole_state_lines_20B_per_cell": cells * 20 / (us * 1e-6) / 1e12}
+    doc["ratios"] = {"sample_K64_over_G_sample_K64": mmm([p / q for p, q in zip(r["sample_K64"], r["G_sample_K64"])]),
+                     "tables_over_SLf": mmm([p / q for p, q in zip(r["tables"], r["SLf"])]),
+                     "module_K64_over_SLf": mmm([p / q for p, q in zip(r["module_K64"], r["SLf"])]),
+                     "SLf_over_Gf": mmm([p / q for p, q in zip(r["SLf"], r["Gf"])])}
+    print(json.dumps({k: v for k, v in doc.items() if k != "_stamp"}), flush=True)
+    os.makedirs(os.path.dirname(OUT), exist_ok=True)
+    with open(OUT, "w") as fh:
+        json.dump(doc, fh, indent=1)
+    print("->", os.path.relpath(OUT, ROOT))
+
+
+if __name__ == "__main__":
+    assert torch.cuda.is_available(), "soft_local_sample_bench.py measures on a GPU; there is nothing to report without one"
+    main()
