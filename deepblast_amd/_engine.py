@@ -617,6 +617,54 @@ class HipEngine:
                   B, N, M, int(K), int(sample0), int(seed) & 0xffffffffffffffff, lens, 0)
         return states, counts, visits, ends
 
+    # ---- the sparsemax operator (include/sdp.h: sdp_sparsemax_*) ------------------------------
+    def _sparsemax_variant(self, variant):
+        w = self.force_waves.get("sparsemax", 0)
+        return variant | (_lib.SDP_WAVES(w) if w else 0)
+
+    def sparsemax_forward(self, theta, A, variant, lens=None, state_out=None):
+        """-> (Vt (B,), state): the sparsemax sweep and its 16-byte records {q_x, q_m, q_y, V} (opaque float32 tensor of
+        sdp_sparsemax_state_bytes).  state_out: a buffer of that size to write into instead of a fresh one."""
+        dev = self.device_of(theta)
+        check_args(theta, torch.float32, theta=theta, A=A)
+        theta, A = theta.contiguous(), A.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        nfloats = max(self.lib.sdp_sparsemax_state_bytes(B, N, M), 4) // 4
+        check_args(theta, torch.float32, (nfloats,), True, ValueError, state_out=state_out)
+        state = torch.empty(nfloats, dtype=torch.float32, device=theta.device) if state_out is None else state_out
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        self.call("sdp_sparsemax_forward_f32", SPARSEMAX_KERNELS[150], dev, theta, A, state, Vt, B, N, M, lens,
+                  self._sparsemax_variant(variant))
+        return Vt, state
+
+    def sparsemax_forward_value(self, theta, A, variant, lens=None):
+        """-> Vt (B,) alone: the same sweep with the records compiled out (the same bits); nothing else is allocated."""
+        dev = self.device_of(theta)
+        check_args(theta, torch.float32, theta=theta, A=A)
+        theta, A = theta.contiguous(), A.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        self.call("sdp_sparsemax_forward_value_f32", SPARSEMAX_KERNELS[151], dev, theta, A, Vt, B, N, M, lens,
+                  self._sparsemax_variant(variant))
+        return Vt
+
+    def sparsemax_backward(self, state, Vt, Et, shape, variant, lens=None, want_G=True):
+        """The mirror sweep over the records of sparsemax_forward -> (E (B,N,M), G (B,N,M) or None): Et . dVt/dtheta and
+        Et . dVt/dA, +0 outside each pair's block (and below lo for SW).  Vt: what sparsemax_forward returned with `state`."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        check_args(state, torch.float32, (B,), True, Vt=Vt)
+        check_args(state, Et=Et)
+        Et = Et.detach().to(torch.float32).expand(B).contiguous()
+        lens = self._lens(lens, B, state.device)
+        E = torch.empty((B, N, M), dtype=torch.float32, device=state.device)
+        G = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if want_G else None
+        self.call("sdp_sparsemax_backward_f32", SPARSEMAX_KERNELS[152], dev, state, Vt, Et, E, G, B, N, M, lens,
+                  self._sparsemax_variant(variant))
+        return E, G
+
     # ---- alignments sampled from the posterior (include/sdp.h: sdp_sample_paths_*) -------------------
     def sample_paths(self, state, shape, variant, K, lens=None, seed=0, sample0=0, exact_state=False, transposed=False,
                      want_states=True, want_visits=False):
@@ -702,6 +750,8 @@ SOFT_LOCAL_KERNELS = {130: "sdp_soft_local_fwd_kernel", 131: "sdp_soft_local_val
 SOFT_LOCAL_ADJOINT_KERNELS = {140: "sdp_soft_local_adj_fwd_kernel", 141: "sdp_soft_local_adj_bwd_kernel"}
 # and of the kernels that sample from its posterior (csrc/sdp_soft_local_sample.h)
 SOFT_LOCAL_SAMPLE_KERNELS = {134: "sdp_soft_local_tables_kernel", 135: "sdp_soft_local_sample_kernel"}
+# kernel id (csrc/sdp_sparsemax.h) -> symbol of the sparsemax operator's kernels
+SPARSEMAX_KERNELS = {150: "sdp_sparsemax_fwd_kernel", 151: "sdp_sparsemax_val_kernel", 152: "sdp_sparsemax_bwd_kernel"}
 
 _SWEEPS = ("sdp_forward", "sdp_backward", "sdp_adjoint_forward", "sdp_adjoint_backward")
 # dtype -> (suffix of the four sweeps' entries, their launch labels (float32: where the library's plan is not asked),

@@ -2,7 +2,7 @@
 
 The sweep kernels (csrc/sdp_kernels.hip) are one template instantiated 36 times (csrc/sdp_builds.def); as ONE translation unit
 they take three to four minutes.  The file therefore knows `-DSDP_GROUP=<g>` (one group of its kernels per translation unit), and
-its ten groups, like the twelve other sources, are compiled to objects in parallel and linked: ~40 s on 8 cores."""
+its ten groups, like the other sources, are compiled to objects in parallel and linked: ~40 s on 8 cores."""
 import os
 import subprocess
 import sys
@@ -18,11 +18,11 @@ SRC = [KERNELS, os.path.join(HERE, "csrc", "sdp_aux.hip"), os.path.join(HERE, "c
        os.path.join(HERE, "csrc", "sdp_score.hip"), os.path.join(HERE, "csrc", "sdp_hard.hip"), os.path.join(HERE, "csrc", "sdp_gap.hip"),
        os.path.join(HERE, "csrc", "sdp_sample.hip"), os.path.join(HERE, "csrc", "sdp_soft_local.hip"),
        os.path.join(HERE, "csrc", "sdp_soft_local_adj.hip"), os.path.join(HERE, "csrc", "sdp_soft_local_sample.hip"),
-       os.path.join(HERE, "csrc", "sdp_api.hip")]
+       os.path.join(HERE, "csrc", "sdp_sparsemax.hip"), os.path.join(HERE, "csrc", "sdp_api.hip")]
 HDR = [os.path.join(HERE, "csrc", "sdp_kernels.h"), os.path.join(HERE, "csrc", "sdp_device.h"), os.path.join(HERE, "csrc", "sdp_builds.def"), os.path.join(HERE, "csrc", "sdp_hard.h"),
        os.path.join(HERE, "csrc", "sdp_gap.h"), os.path.join(HERE, "csrc", "sdp_sample.h"), os.path.join(HERE, "csrc", "sdp_soft_local.h"),
        os.path.join(HERE, "csrc", "sdp_soft_local_device.h"), os.path.join(HERE, "csrc", "sdp_soft_local_sample.h"),
-       os.path.join(ROOT, "include", "sdp.h")]
+       os.path.join(HERE, "csrc", "sdp_sparsemax.h"), os.path.join(ROOT, "include", "sdp.h")]
 OUT = os.path.join(HERE, "libsdp_hip.so")
 
 

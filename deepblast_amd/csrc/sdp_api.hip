@@ -15,6 +15,7 @@
 #include "sdp_hard.h"
 #include "sdp_soft_local.h"
 #include "sdp_soft_local_sample.h"
+#include "sdp_sparsemax.h"
 #include "sdp_kernels.h"
 
 namespace {
@@ -687,6 +688,10 @@ const char *sdp_kernel_name(int kernel_id)
     // sampling from its posterior (csrc/sdp_soft_local_sample.hip)
     case sdp_soft_local_sample::ID_TABLES: return "sdp_soft_local_tables_kernel";
     case sdp_soft_local_sample::ID_SAMPLE: return "sdp_soft_local_sample_kernel";
+    // the sparsemax operator (csrc/sdp_sparsemax.hip)
+    case sdp_sparsemax::ID_FWD: return "sdp_sparsemax_fwd_kernel";
+    case sdp_sparsemax::ID_VAL: return "sdp_sparsemax_val_kernel";
+    case sdp_sparsemax::ID_BWD: return "sdp_sparsemax_bwd_kernel";
     }
     return nullptr;
 }
@@ -1567,6 +1572,79 @@ int sdp_soft_local_sample_paths_f32(const void *state, const float *cdf, const f
     hipLaunchKernelGGL(sdp_soft_local_sample_kernel, dim3((unsigned)waves), dim3(sdp_soft_local_sample::LANES), 0, (hipStream_t)stream, g);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_sample_kernel");
+    return 0;
+}
+
+// ---- the sparsemax operator (csrc/sdp_sparsemax.hip): the global recurrence under the sparse smoothed maximum, first order ----
+// `variant` of the three entries: SDP_NW / SDP_SW | SDP_WAVES(w); anything else is refused
+static int sparsemax_args(int variant, int B, int N, int M, int &waves, int &lo)
+{
+    waves = (variant >> 12) & 0xf;
+    variant &= ~(0xf << 12);
+    if (int rc = check_shape(B, N, M, variant)) return rc;
+    if ((size_t)B * (size_t)N * (size_t)M > ((size_t)1 << 31)) return fail(SDP_E_TOOBIG, "B*N*M exceeds 2^31 elements");
+    lo = variant == SDP_SW ? 2 : 1;
+    return 0;
+}
+
+// waves of a workgroup: one per strip in flight, as many as the boundary rows fit LDS for
+static int sparsemax_waves(int forced, int N, int M)
+{
+    int w = sdp_sparsemax::strips(N) < sdp_sparsemax::MAX_WAVES ? sdp_sparsemax::strips(N) : sdp_sparsemax::MAX_WAVES;
+    if (forced > 0 && forced < w) w = forced;
+    while (w > 1 && sdp_sparsemax::sweep_lds_bytes(w, M) > (size_t)sdp_sparsemax::LDS_BUDGET) --w;
+    return w;
+}
+
+size_t sdp_sparsemax_state_bytes(int B, int N, int M)
+{
+    if (B <= 0 || N <= 0 || M <= 0 || M > sdp::MAX_COLS) return 0;
+    return (size_t)B * sdp_sparsemax::pair_records(N, M) * sdp_sparsemax::CELL_BYTES;
+}
+
+static int sparsemax_forward(const float *theta, const float *A, void *state, float *Vt, int B, int N, int M, const int32_t *lens,
+                             int variant, int device, void *stream, bool records)
+{
+    int waves, lo;
+    if (int rc = sparsemax_args(variant, B, N, M, waves, lo)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    const int W = sparsemax_waves(waves, N, M);
+    hipLaunchKernelGGL(records ? sdp_sparsemax_fwd_kernel : sdp_sparsemax_val_kernel, dim3(B), dim3(64 * W),
+                       sdp_sparsemax::sweep_lds_bytes(W, M), (hipStream_t)stream, theta, A, static_cast<float4 *>(state), Vt, lens, N, M, lo, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, records ? "sdp_sparsemax_fwd_kernel" : "sdp_sparsemax_val_kernel");
+    return 0;
+}
+
+int sdp_sparsemax_forward_f32(const float *theta, const float *A, void *state, float *Vt, int B, int N, int M, const int32_t *lens,
+                              int variant, int device, void *stream)
+{
+    if (!theta || !A || !state || !Vt) return fail(SDP_E_NULLPTR, "sdp_sparsemax_forward_f32: null pointer");
+    return sparsemax_forward(theta, A, state, Vt, B, N, M, lens, variant, device, stream, true);
+}
+
+int sdp_sparsemax_forward_value_f32(const float *theta, const float *A, float *Vt, int B, int N, int M, const int32_t *lens, int variant,
+                                    int device, void *stream)
+{
+    if (!theta || !A || !Vt) return fail(SDP_E_NULLPTR, "sdp_sparsemax_forward_value_f32: null pointer");
+    return sparsemax_forward(theta, A, nullptr, Vt, B, N, M, lens, variant, device, stream, false);
+}
+
+int sdp_sparsemax_backward_f32(const void *state, const float *Vt, const float *Et, float *E, float *G, int B, int N, int M,
+                               const int32_t *lens, int variant, int device, void *stream)
+{
+    // (Vt is part of the trio's call shape and must be what the forward entry wrote; the sweep itself starts from Et alone)
+    if (!state || !Vt || !Et || !E) return fail(SDP_E_NULLPTR, "sdp_sparsemax_backward_f32: null pointer (state, Vt, Et, E; G may be NULL)");
+    int waves, lo;
+    if (int rc = sparsemax_args(variant, B, N, M, waves, lo)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    const int W = sparsemax_waves(waves, N, M);
+    hipLaunchKernelGGL(sdp_sparsemax_bwd_kernel, dim3(B), dim3(64 * W), sdp_sparsemax::sweep_lds_bytes(W, M), (hipStream_t)stream,
+                       static_cast<const float4 *>(state), Et, E, G, lens, N, M, lo, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "sdp_sparsemax_bwd_kernel");
     return 0;
 }
 

@@ -1,0 +1,332 @@
+// sdp_sparsemax.hip -- the sparsemax operator: a differentiable alignment score with a SPARSE gradient (include/sdp.h:
+// sdp_sparsemax_*)
+//
+//     c = (A[i,j] + V[i-1,j],  V[i-1,j-1],  A[i,j] + V[i,j-1])                                    states x = 0, m = 1, y = 2
+//     q = the Euclidean projection of c onto the simplex = max(c - tau, 0),  tau = max over k of (c_(1) + .. + c_(k) - 1) / k
+//     V[i,j] = theta[i,j] + sum over the support of q_s (c_s - q_s / 2);   Vt = V[n,m]
+//     E[i,j] = q_x[i+1,j] E[i+1,j] + q_m[i+1,j+1] E[i+1,j+1] + q_y[i,j+1] E[i,j+1],  E[n,m] = Et;   G = E (q_x + q_y)
+//
+// a V outside the table is 0, and the loops start at lo = 1 (SDP_NW) or 2 (SDP_SW), as for csrc/sdp_hard.hip.  The schedule is that
+// of csrc/sdp_soft_local.hip, repeated here and not shared (those kernels compile to what they compiled to before).  Three kernels:
+//
+//   forward   one workgroup per pair, one wave per strip of 64 rows (lane = row), swept along the anti-diagonals: at step s lane l
+//             is at column s - l, V[i-1,j] arrives from lane l - 1 by DPP, V[i-1,j-1] is what arrived one step before.  The waves
+//             of a workgroup run consecutive strips three chunks of 32 steps apart; a strip's bottom row crosses to the next strip
+//             through LDS, and a barrier per chunk is the only synchronisation.  Scores are loaded one chunk ahead.  Vt is the
+//             corner cell: the lane that owns it keeps it and writes it after the sweep.  No atomics, the same bits on every call.
+//   records   16 bytes per cell, {q_x, q_m, q_y, V}, in the layout of the soft local records: step t of chunk c of strip S holds the
+//             records of all 64 lanes as one 1 KB line, state[(((pair * strips(N) + S) * chunks(M) + c) * 32 + t) * 64 + lane].
+//             Cell (i, j) (0-based) is lane i % 64 of strip i / 64 at step j + i % 64.  Only cells of the pair's block are written,
+//             and only those are used.  All three weights are stored: one formed as 1 - the others would lose the exact zeros.
+//   value     the forward sweep with the records compiled out: the same arithmetic, the same bits of Vt.
+//   backward  the mirror sweep: strips from the bottom, chunks and steps reversed, so every lane stays on its own cell's record.
+//             The corner cell starts with Et; a cell forms E, then pushes q_x E up, q_m E up-left and q_y E left: the push to the
+//             row above goes to lane l - 1 by DPP (q_x E of this step plus q_m E of the step before, one value), the top row of a
+//             strip crosses to the strip above through LDS.  G = q_x E + q_y E is a by-product.  Records are fetched half a chunk
+//             ahead; E and G leave as 16 consecutive floats of a row.  The workgroup writes +0 outside the pair's block before it
+//             sweeps.  There is no zero-chunk skip: every chunk runs.
+//
+// The cell works in differences from the maximum, d = c - max(c) (one of them is 0, none is positive): tau, q and the value come
+// from d and the maximum is added back last -- V reaches several hundred, and q = max(d, tau) - tau then carries the rounding of the
+// two subtractions alone.  No exp, no log, no division; no branch and no select.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sdp_sparsemax.h"
+
+namespace {
+
+using namespace sdp_sparsemax;
+
+constexpr int DPP_WAVE_SHL1 = 0x130;   // lane i <- lane i + 1; lane 63 keeps `old`
+constexpr int DPP_WAVE_SHR1 = 0x138;   // lane i <- lane i - 1; lane 0 keeps `old`
+
+__device__ __forceinline__ float from_upper_lane(float lane0, float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0), __float_as_int(v), DPP_WAVE_SHR1, 0xf, 0xf, false));
+}
+
+__device__ __forceinline__ float from_lower_lane(float lane63, float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane63), __float_as_int(v), DPP_WAVE_SHL1, 0xf, 0xf, false));
+}
+
+__device__ __forceinline__ float of_lane(float v, int lane)
+{
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+
+struct __attribute__((packed, aligned(4))) F4 {   // four floats at any 4-byte boundary
+    float v[4];
+};
+
+// the scores lane `lane` of strip `s` needs in chunk `c`: columns 32 c - lane .. 32 c - lane + 31 of row 64 s + lane; 0 where
+// the cell does not exist (the value is then never used)
+__device__ __forceinline__ void load_chunk(const float *theta, const float *A, size_t plane, int M, int n, int m, int s, int c,
+                                           int lane, float (&th)[CHUNK], float (&a)[CHUNK])
+{
+    const int row = s * STRIP + lane, col0 = c * CHUNK - lane;
+    const bool rowok = row < n;
+    const size_t at = plane + (size_t)(rowok ? row : 0) * M;
+    if (rowok && col0 >= 0 && col0 + CHUNK <= m) {
+        const F4 *pt = reinterpret_cast<const F4 *>(theta + at + col0), *pa = reinterpret_cast<const F4 *>(A + at + col0);
+#pragma unroll
+        for (int g = 0; g < CHUNK / 4; ++g) {
+            const F4 t4 = pt[g], a4 = pa[g];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) th[4 * g + e] = t4.v[e], a[4 * g + e] = a4.v[e];
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < CHUNK; ++t) {
+            const int col = col0 + t;
+            const bool ok = rowok && col >= 0 && col < m;
+            th[t] = ok ? theta[at + col] : 0.f;
+            a[t] = ok ? A[at + col] : 0.f;
+        }
+    }
+}
+
+// sparsemax over three values, cm finite, cx and cy finite or -inf -> the value max_q <q, c> - |q|^2 / 2; q: its maximiser.
+// With d = c - max(c) sorted 0 = d1 >= d2 >= d3, tau - max(c) is the largest of -1, (d2 - 1) / 2 and (d2 + d3 - 1) / 3 (the
+// thresholds of the supports of one, two and three; the largest is the one whose support is consistent).  Every d is raised to tau
+// first: q_s = max(d_s, tau) - tau is then exactly +0 wherever d_s <= tau, -inf included, and the value's term q_s (d_s - q_s / 2) =
+// q_s (d_s + tau) / 2 is a product of finite numbers that is 0 off the support (0 * -inf never forms, and nothing is selected).
+__device__ __forceinline__ float sparsemax3(float cx, float cm, float cy, float &qx, float &qm, float &qy)
+{
+    const float mx = fmaxf(fmaxf(cx, cm), cy);
+    const float dx = cx - mx, dm = cm - mx, dy = cy - mx;
+    const float d2 = __builtin_amdgcn_fmed3f(dx, dm, dy), d3 = fminf(fminf(dx, dm), dy);
+    const float t2 = (d2 - 1.f) * 0.5f, t3 = ((d2 + d3) - 1.f) * (1.f / 3.f);
+    const float tau = fmaxf(fmaxf(t2, t3), -1.f);
+    const float ex = fmaxf(dx, tau), em = fmaxf(dm, tau), ey = fmaxf(dy, tau);
+    qx = ex - tau;
+    qm = em - tau;
+    qy = ey - tau;
+    return mx + 0.5f * ((qx * (ex + tau) + qy * (ey + tau)) + qm * (em + tau));
+}
+
+// STATE: write the records (else: the value-only sweep)
+template <bool STATE>
+__device__ __forceinline__ void sparsemax_forward(const float *theta, const float *A, float4 *state, float *Vt, const int *lens, int N,
+                                                  int M, int lo, int W)
+{
+    extern __shared__ float smem[];
+    const int Mp = row_pitch(M);
+    float *bnd = smem;                                      // [W][Mp]: bottom row of strip s in bnd[s % W]
+    int *keys = reinterpret_cast<int *>(smem + W * Mp);    // [2][MAX_WAVES]: progress words, double-buffered by chunk parity
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int n = N, m = M;
+    if (lens) {
+        n = min(max(lens[2 * b], 0), N);
+        m = min(max(lens[2 * b + 1], 0), M);
+    }
+    if (n < 1 || m < 1) {   // (uniform over the workgroup: nobody reaches a barrier)
+        if (tid == 0) Vt[b] = 0.f;
+        return;
+    }
+    const int S = strips(n), C = chunks(m), NS = strips(N), CH = chunks(M);
+    const size_t plane = (size_t)b * N * M;
+    if (tid < 2 * MAX_WAVES) keys[tid] = (tid & (MAX_WAVES - 1)) * KEY;
+    const int lastw = (S - 1) % W, upw = (w + W - 1) % W;
+    const int first = lo - 1;   // the first 0-based row and column of the loops: the cells before them keep V = 0 and q = 0
+
+    int s = w, c = 0;
+    float th[CHUNK], a[CHUNK], nth[CHUNK], na[CHUNK];
+    load_chunk(theta, A, plane, M, n, m, s, c, lane, th, a);
+    float vcur = 0.f, up_old = 0.f;   // the zero border: column 0 of the table, and its cell of the row above
+    float corner = 0.f;               // V of this lane's cell in column m: Vt, in the lane of row n
+
+    for (int tick = 0;; ++tick) {
+        __syncthreads();
+        const int *kr = keys + (tick & 1) * MAX_WAVES;
+        int *kw = keys + ((tick + 1) & 1) * MAX_WAVES;
+        if (kr[lastw] >= S * KEY) break;   // the last strip is complete (the same word for every wave: a uniform exit)
+        bool run = s < S;
+        if (run && s > 0) run = kr[upw] >= (s - 1) * KEY + min(c + 3, C);   // the row above is three chunks ahead, or complete
+        if (run) {
+            const int ns = c + 1 < C ? s : s + W, nc = c + 1 < C ? c + 1 : 0;
+            load_chunk(theta, A, plane, M, n, m, ns, nc, lane, nth, na);
+            const int jb = c * CHUNK + lane;   // lanes 0 .. 31: the column of the row above that lane 0 needs at step `lane`
+            float brow = 0.f;                  // (strip 0: the zero border)
+            if (s > 0 && lane < CHUNK && jb < m) brow = bnd[((s - 1) % W) * Mp + jb];
+            float bout = 0.f;
+            const int row1 = s * STRIP + lane + 1;
+            const bool rowlive = row1 > first;
+            const int colb = c * CHUNK - lane;
+            // steps t with col >= 0 and t < tlim are cells of the pair: rows >= n and columns >= m compute values nobody reads
+            const int tlim = (row1 <= n ? m : 0) - colb;
+            float4 *rec = nullptr;
+            if (STATE) rec = state + ((((size_t)b * NS + s) * CH + c) * CHUNK) * STRIP + lane;
+#pragma unroll
+            for (int t = 0; t < CHUNK; ++t) {
+                const int col = colb + t;
+                const float up = from_upper_lane(of_lane(brow, t), vcur);
+                float qx, qm, qy;
+                float v = th[t] + sparsemax3(a[t] + up, up_old, a[t] + vcur, qx, qm, qy);
+                // a lane that has not started, and a cell below lo, keep the 0 of the border
+                const bool live = rowlive && col >= first;
+                v = live ? v : vcur;
+                if (STATE) {
+                    if (col >= 0 && t < tlim) rec[(size_t)t * STRIP] = make_float4(live ? qx : 0.f, live ? qm : 0.f, live ? qy : 0.f, v);
+                }
+                corner = (col == m - 1) ? v : corner;
+                const float bv = of_lane(v, STRIP - 1);
+                bout = (lane == t) ? bv : bout;
+                up_old = up;
+                vcur = v;
+            }
+            // lane t holds the bottom row's value of step t: column 32 c + t - 63
+            const int jo = c * CHUNK + lane - (STRIP - 1);
+            if (s + 1 < S && lane < CHUNK && jo >= 0 && jo < m) bnd[(s % W) * Mp + jo] = bout;
+            if (ns != s) vcur = 0.f, up_old = 0.f;
+            s = ns, c = nc;
+#pragma unroll
+            for (int t = 0; t < CHUNK; ++t) th[t] = nth[t], a[t] = na[t];
+        }
+        if (lane == 0) kw[w] = s * KEY + c;
+    }
+    // the last strip is the last one its wave swept: the lane of row n holds V[n,m] (a cell below lo: the 0 it kept)
+    if (w == lastw && lane == (n - 1) % STRIP) Vt[b] = corner;
+}
+
+// the records lane `lane` of strip `s` reads in half `h` of chunk `c`: steps 16 h .. 16 h + 15
+__device__ __forceinline__ void load_half(const float4 *state, size_t pair, int CH, int s, int c, int h, int lane, float4 (&q)[HALF])
+{
+    const float4 *src = state + (((pair + s) * CH + c) * CHUNK + h * HALF) * STRIP + lane;
+#pragma unroll
+    for (int t = 0; t < HALF; ++t) q[t] = src[(size_t)t * STRIP];
+}
+
+// 16 consecutive cells of row `row` from column col0 on; only cells of the pair's block are written
+__device__ __forceinline__ void store_half(float *out, size_t plane, int M, int n, int m, int row, int col0, const float (&e)[HALF])
+{
+    if (row >= n) return;
+    const size_t at = plane + (size_t)row * M;
+    if (col0 >= 0 && col0 + HALF <= m) {
+        F4 *p = reinterpret_cast<F4 *>(out + at + col0);
+#pragma unroll
+        for (int g = 0; g < HALF / 4; ++g) {
+            F4 x;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x.v[k] = e[4 * g + k];
+            p[g] = x;
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < HALF; ++t) {
+            const int col = col0 + t;
+            if (col >= 0 && col < m) out[at + col] = e[t];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(512) sdp_sparsemax_fwd_kernel(const float *theta, const float *A, float4 *state, float *Vt,
+                                                                           const int *lens, int N, int M, int lo, int waves)
+{
+    sparsemax_forward<true>(theta, A, state, Vt, lens, N, M, lo, waves);
+}
+extern "C" __global__ void __launch_bounds__(512) sdp_sparsemax_val_kernel(const float *theta, const float *A, float4 *state, float *Vt,
+                                                                           const int *lens, int N, int M, int lo, int waves)
+{
+    sparsemax_forward<false>(theta, A, state, Vt, lens, N, M, lo, waves);
+}
+
+// G may be NULL.  Strip and chunk counters run in the REVERSED order (rs = S - 1 - strip, rc = C - 1 - chunk), with which the
+// progress words and the boundary ring are those of the forward sweep: strip rs reads what strip rs - 1 -- the one below -- left.
+extern "C" __global__ void __launch_bounds__(512) sdp_sparsemax_bwd_kernel(const float4 *state, const float *Et, float *E, float *G,
+                                                                           const int *lens, int N, int M, int lo, int W)
+{
+    extern __shared__ float smem[];
+    const int Mp = row_pitch(M);
+    float *bnd = smem;                                      // [W][Mp]: what the top row of strip rs pushes up, in bnd[rs % W]
+    int *keys = reinterpret_cast<int *>(smem + W * Mp);    // [2][MAX_WAVES]: progress words, double-buffered by chunk parity
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int n = N, m = M;
+    if (lens) {
+        n = min(max(lens[2 * b], 0), N);
+        m = min(max(lens[2 * b + 1], 0), M);
+    }
+    if (n < 1 || m < 1) n = 0, m = 0;
+    const size_t plane = (size_t)b * N * M;
+    // +0 outside the pair's block (no cell of it is written again)
+    for (int r = w; r < N; r += W) {
+        const size_t at = plane + (size_t)r * M;
+        for (int col = (r < n ? m : 0) + lane; col < M; col += STRIP) {
+            E[at + col] = 0.f;
+            if (G) G[at + col] = 0.f;
+        }
+    }
+    if (n < 1) return;   // (uniform over the workgroup: nobody reaches a barrier)
+    const int S = strips(n), C = chunks(m), NS = strips(N), CH = chunks(M);
+    const size_t pair = (size_t)b * NS;
+    if (tid < 2 * MAX_WAVES) keys[tid] = (tid & (MAX_WAVES - 1)) * KEY;
+    const int lastw = (S - 1) % W, upw = (w + W - 1) % W;
+    const float et = Et[b];
+    const int first = lo - 1;   // the first 0-based row and column of the loops: E and G are +0 on the cells before them
+
+    int rs = w, rc = 0;
+    float4 cur[HALF], nxt[HALF];
+    if (rs < S) load_half(state, pair, CH, S - 1 - rs, C - 1, 1, lane, cur);
+    // what this lane's cell of the step before pushes: `send` to the row above (q_x E, plus q_m E of the step before that, which
+    // is due one column further left), `py` to its own row; pm: q_m E of the step before
+    float send = 0.f, pm = 0.f, py = 0.f;
+
+    for (int tick = 0;; ++tick) {
+        __syncthreads();
+        const int *kr = keys + (tick & 1) * MAX_WAVES;
+        int *kw = keys + ((tick + 1) & 1) * MAX_WAVES;
+        if (kr[lastw] >= S * KEY) break;   // the last strip is complete (the same word for every wave: a uniform exit)
+        bool run = rs < S;
+        if (run && rs > 0) run = kr[upw] >= (rs - 1) * KEY + min(rc + 3, C);   // the strip below is three chunks ahead, or complete
+        if (run) {
+            const int s = S - 1 - rs, c = C - 1 - rc;
+            const int nrs = rc + 1 < C ? rs : rs + W, nrc = rc + 1 < C ? rc + 1 : 0;
+            const int jb = c * CHUNK + lane - (STRIP - 1);   // lanes 0 .. 31: the column lane 63 is at in step `lane`
+            float brow = 0.f;
+            if (rs > 0 && lane < CHUNK && jb >= 0 && jb < m) brow = bnd[((rs - 1) % W) * Mp + jb];
+            float bout = 0.f;
+            const int row = s * STRIP + lane;
+            const bool rowok = row < n && row >= first;
+            const float seed = row == n - 1 ? et : 0.f;   // Et enters at the corner cell alone
+            const int colb = c * CHUNK - lane;
+#pragma unroll
+            for (int h = 1; h >= 0; --h) {
+                if (h == 1)
+                    load_half(state, pair, CH, s, c, 0, lane, nxt);
+                else if (nrs < S)
+                    load_half(state, pair, CH, S - 1 - nrs, C - 1 - nrc, 1, lane, nxt);
+                float e[HALF], g[HALF];
+#pragma unroll
+                for (int tt = HALF - 1; tt >= 0; --tt) {
+                    const int t = h * HALF + tt;
+                    const int col = colb + t;
+                    const bool cell = rowok && col >= first && col < m;
+                    const float4 q = cur[tt];
+                    const float in = from_lower_lane(of_lane(brow, t), send);
+                    const float ev = cell ? (col == m - 1 ? seed : 0.f) + (in + py) : 0.f;
+                    const float px = (cell ? q.x : 0.f) * ev, pmn = (cell ? q.y : 0.f) * ev;
+                    py = (cell ? q.z : 0.f) * ev;
+                    send = px + pm;
+                    pm = pmn;
+                    e[tt] = ev;
+                    g[tt] = 0.f + (px + py);   // (+0 where both weights are +0, whatever the sign of E)
+                    const float tv = of_lane(send, 0);
+                    bout = (lane == t) ? tv : bout;
+                }
+                store_half(E, plane, M, n, m, row, colb + h * HALF, e);
+                if (G) store_half(G, plane, M, n, m, row, colb + h * HALF, g);
+#pragma unroll
+                for (int tt = 0; tt < HALF; ++tt) cur[tt] = nxt[tt];
+            }
+            // lane t holds what the top row pushed up in step t: column 32 c + t of the row above
+            const int jo = c * CHUNK + lane;
+            if (rs + 1 < S && lane < CHUNK && jo < m) bnd[(rs % W) * Mp + jo] = bout;
+            if (nrs != rs) send = 0.f, pm = 0.f, py = 0.f;
+            rs = nrs, rc = nrc;
+        }
+        if (lane == 0) kw[w] = rs * KEY + rc;
+    }
+}

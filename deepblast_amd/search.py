@@ -25,7 +25,8 @@ def search_scores(decoder, zq, gq, zdb, gdb, db_lengths, query_length=None, chun
                   (Decoder('hardmax', local=True)) gives local scores: the best cell of the max-plus table with a zero floor.
                   alignment_scores produces theta = softplus(.) >= 0, and with theta >= 0 nothing ever floors -- the result is
                   then the free-end-gaps optimum; for true locality shift theta by a threshold of your choosing (a decoder
-                  wrapper whose score() subtracts it).
+                  wrapper whose score() subtracts it).  Any object with score(theta, A, lengths) -> (B,) serves:
+                  deepblast_amd.sparse.SparsemaxDecoder and deepblast_amd.local.SoftLocalDecoder rank a database by their scores.
     zq, gq        (N, D) match / gap embeddings of the query.
     zdb, gdb      (T, Mmax, D) match / gap embeddings of the T targets, zero padded behind each target's length.
     db_lengths    (T,) int: residues per target (1 .. Mmax).

@@ -556,6 +556,42 @@ int sdp_soft_local_sample_paths_f32(const void *state, const float *cdf, const f
                                     int32_t *visits, int32_t *ends, int B, int N, int M, int K, int sample0, uint64_t seed,
                                     const int32_t *lens, int flags, int device, void *stream);
 
+/* The SPARSEMAX operator (csrc/sdp_sparsemax.hip): the global recurrence of the sweeps above under the second
+ * smoothed maximum of Mensch & Blondel -- the maximum regularised by the squared norm instead of the entropy -- whose gradient, the
+ * alignment matrix E, is SPARSE: exact zeros off a few paths, exactly 0 / 1 where the scores are decisive, fractional only where
+ * they are ambiguous.  (Added after SDP_VERSION 106 without a version change: look the symbols up.  sdp_kernel_name answers 150,
+ * 151 and 152 for its kernels.)  With (n, m) = lens[b] or (N, M), lo = 1 (SDP_NW) or 2 (SDP_SW), V (n+1) x (m+1) all zero,
+ * 1-based, exactly as for sdp_hard_*: zero borders, loops from lo; states x, m, y = 0, 1, 2:
+ *     for i in lo..n, j in lo..m:
+ *         c = (A[i-1,j-1] + V[i-1,j],  V[i-1,j-1],  A[i-1,j-1] + V[i,j-1])
+ *         q = sparsemax(c): the Euclidean projection of c onto the simplex (Martins & Astudillo) -- with c sorted descending,
+ *             k = max{k : 1 + k c_(k) > c_(1) + .. + c_(k)},  tau = (c_(1) + .. + c_(k) - 1) / k,  q = max(c - tau, 0)
+ *         V[i,j] = theta[i-1,j-1] + sum over the support (q_s > 0) of q_s (c_s - q_s / 2)
+ *     Vt = V[n,m]                                                           (0 when no cell exists)
+ *     E[i,j] = q_x[i+1,j] E[i+1,j] + q_m[i+1,j+1] E[i+1,j+1] + q_y[i,j+1] E[i,j+1],   E[n+1,m+1] = Et, q_m[n+1,m+1] = 1
+ *     G[i,j] = E[i,j] (q_x[i,j] + q_y[i,j])
+ * E = Et dVt/dtheta and G = Et dVt/dA are the TRUE gradients (Danskin); this operator has no pass-through convention for A.  E and
+ * G are +0 outside the pair's [:n, :m] block and, for SDP_SW, on row 1 and column 1 of the table (no cell below lo is computed:
+ * V = 0 and q = 0 there); a pair with n < 1 or m < 1 has Vt = 0 and E = G = 0.  fp32 only; theta finite; A finite or -inf: that
+ * branch lies outside the support, its weight and G are exactly +0 and nothing is NaN.  q is exactly +0 off the support.  No
+ * atomics: two calls on the same inputs give the same bits, and sdp_sparsemax_forward_value_f32 gives the bits of
+ * sdp_sparsemax_forward_f32's Vt.  Not built: the second order (an adjoint pair), sampling, float64, a local form.
+ *   state    sdp_sparsemax_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: four floats per cell {q_x, q_m, q_y,
+ *            V}, private layout; written by sdp_sparsemax_forward_f32, read by sdp_sparsemax_backward_f32 with the same B, N, M,
+ *            lens, variant.  Only records of cells inside a pair's block are written, and the backward pass reads no others.
+ *   Vt       (B,): written by the forward entries; the backward entry takes what they wrote (the call shape of sdp_soft_local_*).
+ *   G        (B, N, M) or NULL.
+ *   variant  SDP_NW / SDP_SW | SDP_WAVES(w); any other bit is refused (SDP_E_VARIANT).
+ * One workgroup per pair, rows unbounded, M <= sdp_max_cols().  All arguments are checked before any device call: SDP_E_NULLPTR,
+ * SDP_E_SHAPE, SDP_E_MAXCOLS, SDP_E_VARIANT, SDP_E_TOOBIG (N*M > 2^28, or B*N*M > 2^31 elements). */
+size_t sdp_sparsemax_state_bytes(int B, int N, int M);
+int sdp_sparsemax_forward_f32(const float *theta, const float *A, void *state, float *Vt, int B, int N, int M, const int32_t *lens,
+                              int variant, int device, void *stream);
+int sdp_sparsemax_forward_value_f32(const float *theta, const float *A, float *Vt, int B, int N, int M, const int32_t *lens, int variant,
+                                    int device, void *stream);
+int sdp_sparsemax_backward_f32(const void *state, const float *Vt, const float *Et, float *E, float *G, int B, int N, int M,
+                               const int32_t *lens, int variant, int device, void *stream);
+
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept
  * for callers who are short of memory, not of time; deepblast_amd.losses uses the unfused kernels by default.
