@@ -665,6 +665,41 @@ class HipEngine:
                   self._sparsemax_variant(variant))
         return E, G
 
+    def sparsemax_adjoint_forward(self, state, ZE, ZG, shape, variant, lens=None, state_d_out=None):
+        """The adjoint forward sweep over the records of sparsemax_forward -> (Vtd (B,), state_d): ZE, ZG (B,N,M) the cotangents
+        of E and G, one of them may be None (zeros); state_d the dot records (opaque float32 tensor of
+        sdp_sparsemax_adjoint_state_bytes; state_d_out: a buffer of that size to write into instead of a fresh one)."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        if ZE is None and ZG is None:
+            raise ValueError("sparsemax_adjoint_forward: ZE and ZG are both None")
+        check_args(state, torch.float32, (B, N, M), ZE=ZE, ZG=ZG)
+        ZE, ZG = (None if z is None else z.detach().contiguous() for z in (ZE, ZG))
+        lens = self._lens(lens, B, state.device)
+        nfloats = max(self.lib.sdp_sparsemax_adjoint_state_bytes(B, N, M), 4) // 4
+        check_args(state, torch.float32, (nfloats,), True, ValueError, state_d_out=state_d_out)
+        state_d = torch.empty(nfloats, dtype=torch.float32, device=state.device) if state_d_out is None else state_d_out
+        Vtd = torch.empty(B, dtype=torch.float32, device=state.device)
+        self.call("sdp_sparsemax_adjoint_forward_f32", SPARSEMAX_ADJOINT_KERNELS[154], dev, state, ZE, ZG, state_d, Vtd, B, N, M, lens,
+                  self._sparsemax_variant(variant))
+        return Vtd, state_d
+
+    def sparsemax_adjoint_backward(self, state, state_d, Et, shape, variant, lens=None, want_G=True):
+        """The adjoint mirror sweep -> (Ed (B,N,M), Gd (B,N,M) or None): the gradients of <ZE,E> + <ZG,G> with respect to theta and
+        A, +0 outside each pair's block (and below lo for SW).  state: of sparsemax_forward; state_d: of sparsemax_adjoint_forward;
+        Et: what sparsemax_backward was given."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        check_args(state, torch.float32, None, True, state_d=state_d)
+        check_args(state, Et=Et)
+        Et = Et.detach().to(torch.float32).expand(B).contiguous()
+        lens = self._lens(lens, B, state.device)
+        Ed = torch.empty((B, N, M), dtype=torch.float32, device=state.device)
+        Gd = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if want_G else None
+        self.call("sdp_sparsemax_adjoint_backward_f32", SPARSEMAX_ADJOINT_KERNELS[155], dev, state, state_d, Et, Ed, Gd, B, N, M, lens,
+                  self._sparsemax_variant(variant))
+        return Ed, Gd
+
     # ---- alignments sampled from the posterior (include/sdp.h: sdp_sample_paths_*) -------------------
     def sample_paths(self, state, shape, variant, K, lens=None, seed=0, sample0=0, exact_state=False, transposed=False,
                      want_states=True, want_visits=False):
@@ -752,6 +787,8 @@ SOFT_LOCAL_ADJOINT_KERNELS = {140: "sdp_soft_local_adj_fwd_kernel", 141: "sdp_so
 SOFT_LOCAL_SAMPLE_KERNELS = {134: "sdp_soft_local_tables_kernel", 135: "sdp_soft_local_sample_kernel"}
 # kernel id (csrc/sdp_sparsemax.h) -> symbol of the sparsemax operator's kernels
 SPARSEMAX_KERNELS = {150: "sdp_sparsemax_fwd_kernel", 151: "sdp_sparsemax_val_kernel", 152: "sdp_sparsemax_bwd_kernel"}
+# the same of its adjoint pair (csrc/sdp_sparsemax_adj.hip)
+SPARSEMAX_ADJOINT_KERNELS = {154: "sdp_sparsemax_adj_fwd_kernel", 155: "sdp_sparsemax_adj_bwd_kernel"}
 
 _SWEEPS = ("sdp_forward", "sdp_backward", "sdp_adjoint_forward", "sdp_adjoint_backward")
 # dtype -> (suffix of the four sweeps' entries, their launch labels (float32: where the library's plan is not asked),

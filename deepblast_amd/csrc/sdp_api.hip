@@ -583,6 +583,18 @@ int raise_soft_local_adjoint_limit(int device)
     return 0;
 }
 
+// the same for the sparsemax operator's adjoint backward sweep (sdp_sparsemax::adjoint_lds_bytes)
+int raise_sparsemax_adjoint_limit(int device)
+{
+    static thread_local unsigned long long raised = 0;
+    if (device < 64 && (raised >> device & 1ull)) return 0;
+    const hipError_t e = hipFuncSetAttribute((const void *)sdp_sparsemax_adj_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             160 * 1024);
+    if (e != hipSuccess) return fail_hip(e, "hipFuncSetAttribute(sdp_sparsemax_adj_bwd_kernel)");
+    if (device < 64) raised |= 1ull << device;
+    return 0;
+}
+
 // variant | SDP_REF_ROUNDING (sdp_ref.hip): one workgroup of 256 threads per pair, three rolling anti-diagonals of float64
 size_t ref_lds(int M) { return (size_t)3 * (M + 2) * sizeof(double); }
 size_t ref_state_bytes(int B, int N, int M) { return (size_t)B * N * M * 3 * sizeof(float); }
@@ -692,6 +704,9 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_sparsemax::ID_FWD: return "sdp_sparsemax_fwd_kernel";
     case sdp_sparsemax::ID_VAL: return "sdp_sparsemax_val_kernel";
     case sdp_sparsemax::ID_BWD: return "sdp_sparsemax_bwd_kernel";
+    // its adjoint pair (csrc/sdp_sparsemax_adj.hip)
+    case sdp_sparsemax::ID_ADJ_FWD: return "sdp_sparsemax_adj_fwd_kernel";
+    case sdp_sparsemax::ID_ADJ_BWD: return "sdp_sparsemax_adj_bwd_kernel";
     }
     return nullptr;
 }
@@ -711,7 +726,8 @@ int sdp_init(int device)
     for (const Build &b : BUILDS)
         if (int rc = raise_lds_limit(b, device)) return rc;
     if (int rc = raise_scores_limits(device)) return rc;
-    return raise_soft_local_adjoint_limit(device);
+    if (int rc = raise_soft_local_adjoint_limit(device)) return rc;
+    return raise_sparsemax_adjoint_limit(device);
 }
 
 int sdp_device_status(int device, int32_t info[4])
@@ -1645,6 +1661,44 @@ int sdp_sparsemax_backward_f32(const void *state, const float *Vt, const float *
                        static_cast<const float4 *>(state), Et, E, G, lens, N, M, lo, W);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "sdp_sparsemax_bwd_kernel");
+    return 0;
+}
+
+// ---- its second order (csrc/sdp_sparsemax_adj.hip): the adjoint pair, on the launch geometry of the first order ----
+size_t sdp_sparsemax_adjoint_state_bytes(int B, int N, int M) { return sdp_sparsemax_state_bytes(B, N, M); }
+
+int sdp_sparsemax_adjoint_forward_f32(const void *state, const float *ZE, const float *ZG, void *state_d, float *Vtd, int B, int N, int M,
+                                      const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!state || !state_d || !Vtd || (!ZE && !ZG))
+        return fail(SDP_E_NULLPTR, "sdp_sparsemax_adjoint_forward_f32: null pointer (state, state_d, Vtd; one of ZE, ZG may be NULL)");
+    int waves, lo;
+    if (int rc = sparsemax_args(variant, B, N, M, waves, lo)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    const int W = sparsemax_waves(waves, N, M);
+    hipLaunchKernelGGL(sdp_sparsemax_adj_fwd_kernel, dim3(B), dim3(64 * W), sdp_sparsemax::sweep_lds_bytes(W, M), (hipStream_t)stream,
+                       static_cast<const float4 *>(state), ZE, ZG, static_cast<float4 *>(state_d), Vtd, lens, N, M, lo, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "sdp_sparsemax_adj_fwd_kernel");
+    return 0;
+}
+
+int sdp_sparsemax_adjoint_backward_f32(const void *state, const void *state_d, const float *Et, float *Ed, float *Gd, int B, int N, int M,
+                                       const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!state || !state_d || !Et || !Ed)
+        return fail(SDP_E_NULLPTR, "sdp_sparsemax_adjoint_backward_f32: null pointer (state, state_d, Et, Ed; Gd may be NULL)");
+    int waves, lo;
+    if (int rc = sparsemax_args(variant, B, N, M, waves, lo)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = raise_sparsemax_adjoint_limit(device)) return rc;
+    const int W = sparsemax_waves(waves, N, M);
+    hipLaunchKernelGGL(sdp_sparsemax_adj_bwd_kernel, dim3(B), dim3(64 * W), sdp_sparsemax::adjoint_lds_bytes(W, M), (hipStream_t)stream,
+                       static_cast<const float4 *>(state), static_cast<const float4 *>(state_d), Et, Ed, Gd, lens, N, M, lo, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "sdp_sparsemax_adj_bwd_kernel");
     return 0;
 }
 

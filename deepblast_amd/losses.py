@@ -149,8 +149,9 @@ class _DecodeLoss(torch.autograd.Function):
 def decode_loss(decoder, loss, theta, A, first, x_len, y_len, G, lengths=None, fill=False):
     """`loss(first, decoder.decode(theta, A[, lengths]), x_len, y_len, G)` as one op -> (loss scalar, E).
 
-    decoder : NeedlemanWunschDecoder / SmithWatermanDecoder of this package, or SoftLocalDecoder(second_order=True): the unfused
-              composition like gap_gradient=True below, theta and A both get their true gradients (second_order=False raises)
+    decoder : NeedlemanWunschDecoder / SmithWatermanDecoder of this package, or SoftLocalDecoder(second_order=True) /
+              SparsemaxDecoder(second_order=True): the unfused composition like gap_gradient=True below, theta and A both get
+              their true gradients (second_order=False raises)
     loss    : MatrixCrossEntropy() / SoftPathLoss() / SoftAlignmentLoss() of this module (its `kind` is used)
     lengths : optional (B,2) per-pair sizes for the DP itself (None = the reference's full padded DP)
     The scalar is differentiable w.r.t. theta (the gradient w.r.t. A is None, as in the reference's second-order
@@ -167,12 +168,20 @@ def decode_loss(decoder, loss, theta, A, first, x_len, y_len, G, lengths=None, f
     (non-contiguous) view of the (B, M, N) matrix the sweeps wrote.  Both sides over the limit raise what decode() raises."""
     from ._engine import NW, SW
     from .local import SoftLocalDecoder
+    from .sparse import SparsemaxDecoder
     from .sw import SmithWatermanDecoder
     if isinstance(decoder, SoftLocalDecoder):
         # a kernel family of its own: never the global sweeps below.  With its second order, the unfused composition.
         if not decoder.second_order:
             raise NotImplementedError("decode_loss needs the second order of the soft local operator: build the decoder with "
                                       "SoftLocalDecoder(second_order=True)")
+        E = decoder.decode(theta, A, lengths)
+        return loss(first, E, x_len, y_len, G), E.detach()
+    if isinstance(decoder, SparsemaxDecoder):
+        # the same for the sparsemax operator
+        if not decoder.second_order:
+            raise NotImplementedError("decode_loss needs the second order of the sparsemax operator: build the decoder with "
+                                      "SparsemaxDecoder(second_order=True)")
         E = decoder.decode(theta, A, lengths)
         return loss(first, E, x_len, y_len, G), E.detach()
     variant = SW if isinstance(decoder, SmithWatermanDecoder) else NW

@@ -575,7 +575,7 @@ int sdp_soft_local_sample_paths_f32(const void *state, const float *cdf, const f
  * V = 0 and q = 0 there); a pair with n < 1 or m < 1 has Vt = 0 and E = G = 0.  fp32 only; theta finite; A finite or -inf: that
  * branch lies outside the support, its weight and G are exactly +0 and nothing is NaN.  q is exactly +0 off the support.  No
  * atomics: two calls on the same inputs give the same bits, and sdp_sparsemax_forward_value_f32 gives the bits of
- * sdp_sparsemax_forward_f32's Vt.  Not built: the second order (an adjoint pair), sampling, float64, a local form.
+ * sdp_sparsemax_forward_f32's Vt.  The second order is the adjoint pair below.  Not built: sampling, float64, a local form.
  *   state    sdp_sparsemax_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: four floats per cell {q_x, q_m, q_y,
  *            V}, private layout; written by sdp_sparsemax_forward_f32, read by sdp_sparsemax_backward_f32 with the same B, N, M,
  *            lens, variant.  Only records of cells inside a pair's block are written, and the backward pass reads no others.
@@ -591,6 +591,42 @@ int sdp_sparsemax_forward_value_f32(const float *theta, const float *A, float *V
                                     int device, void *stream);
 int sdp_sparsemax_backward_f32(const void *state, const float *Vt, const float *Et, float *E, float *G, int B, int N, int M,
                                const int32_t *lens, int variant, int device, void *stream);
+
+/* Its SECOND ORDER (csrc/sdp_sparsemax_adj.hip): the adjoint pair, for a loss on the sparse E or on G.  (Added after
+ * SDP_VERSION 106 without a version change: look the symbols up.  sdp_kernel_name answers 154 and 155 for its kernels; 149, 153 and
+ * 156 answer NULL.)  Given cotangents ZE on E and ZG on G, both (B, N, M) and ignored outside a pair's block, with the records q of
+ * the forward sweep, the support s_k = [q_k > 0] (read from the records' exact zeros, never re-derived), |S| = s_x + s_m + s_y (at
+ * least 1 on every cell of the loops), everything outside the table being 0:
+ *   adjoint forward (the direction of the forward sweep), i = lo..n, j = lo..m:
+ *     u_x = ZG[i,j] + Vd[i-1,j]     u_m = Vd[i-1,j-1]     u_y = ZG[i,j] + Vd[i,j-1]
+ *     Vd[i,j] = ZE[i,j] + q_x u_x + q_m u_m + q_y u_y;     qd_k[i,j] = s_k (u_k - (sum over S of u) / |S|),  k = x, m, y
+ *     Vtd = Vd[n,m]                                                         (0 when no cell exists)
+ *   adjoint backward (the mirror sweep; E is re-formed beside Ed by the first-order recurrence, seeded with Et; Ed has no seed):
+ *     Ed[i,j] = qd_x[i+1,j] E[i+1,j] + q_x[i+1,j] Ed[i+1,j] + qd_m[i+1,j+1] E[i+1,j+1] + q_m[i+1,j+1] Ed[i+1,j+1]
+ *               + qd_y[i,j+1] E[i,j+1] + q_y[i,j+1] Ed[i,j+1]
+ *     Gd[i,j] = Ed[i,j] (q_x + q_y)[i,j] + E[i,j] (qd_x + qd_y)[i,j]
+ * With L = <ZE,E> + <ZG,G>: dL/dtheta = Ed, dL/dA = Gd, dL/dEt = Vtd.  Vtd does not depend on Et; Et = 0 gives Ed = Gd = 0.  V is
+ * piecewise quadratic in (theta, A): these are its second derivatives away from the kinks, and AT a kink -- a weight that is exactly 0
+ * on the edge of its support -- the convention s = [q > 0].  A branch with A = -inf has s = 0 and qd = 0: Gd is +0 by bit pattern at
+ * a forbidden gap and nothing is NaN.  For SDP_SW, row 1 and column 1 of the table hold Vd = 0 and qd = 0, their ZE and ZG take no
+ * part, and Ed = Gd = +0 there.  Ed and Gd are +0 outside the pair's block, an empty pair has Vtd = 0.  The third order is not built.
+ * No exp, no log, no division (1 / |S| is 1, 1/2 or 1/3); no atomics: two calls give the same bits, and so does every SDP_WAVES(w).
+ *   state    what sdp_sparsemax_forward_f32 wrote; same B, N, M, lens, variant throughout.
+ *   state_d  sdp_sparsemax_adjoint_state_bytes(B, N, M) bytes (= sdp_sparsemax_state_bytes; 0 on a bad shape), DEVICE, caller-owned:
+ *            four floats per cell {qd_x, qd_m, qd_y, Vd} in the layout of `state`, private; written by the adjoint forward entry
+ *            (cells of a pair's block only), read by the adjoint backward entry (no others).
+ *   ZE, ZG   one of them may be NULL: zeros, and the same bits as with a tensor of zeros.  Both NULL: SDP_E_NULLPTR.
+ *   Vtd      (B,): written by the adjoint forward entry.
+ *   Gd       (B, N, M) or NULL.
+ *   variant  SDP_NW / SDP_SW | SDP_WAVES(w); any other bit is refused (SDP_E_VARIANT).
+ * The launch geometry is that of the first order; the adjoint backward kernel keeps two boundary rows per wave in LDS (up to 131008
+ * bytes), for which the entry raises the kernel's dynamic-LDS limit (sdp_init does it too, before a stream capture).  Argument
+ * checks as above, before any device call: SDP_E_NULLPTR, SDP_E_SHAPE, SDP_E_MAXCOLS, SDP_E_VARIANT, SDP_E_TOOBIG. */
+size_t sdp_sparsemax_adjoint_state_bytes(int B, int N, int M);
+int sdp_sparsemax_adjoint_forward_f32(const void *state, const float *ZE, const float *ZG, void *state_d, float *Vtd, int B, int N, int M,
+                                      const int32_t *lens, int variant, int device, void *stream);
+int sdp_sparsemax_adjoint_backward_f32(const void *state, const void *state_d, const float *Et, float *Ed, float *Gd, int B, int N, int M,
+                                       const int32_t *lens, int variant, int device, void *stream);
 
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept

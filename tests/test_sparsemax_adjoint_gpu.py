@@ -1,0 +1,338 @@
+"""GPU: the sparsemax operator's adjoint pair (csrc/sdp_sparsemax_adj.hip) through the C ABI, on the state that
+sdp_sparsemax_forward_f32 wrote, against the float64 definition (tests/sparsemax_adjoint_ref.py, held to autograd applied twice and
+to central differences by tests/test_sparsemax_adjoint.py) on the same fp32 inputs, under tests/parity.py's rules: plain
+abs_err(Ed) <= TOL, abs_err(Gd) <= TOL, rel_err(Vtd) <= TOL, cotangents uniform in [-1, 1].  Every case here passes the admission
+rule on the CPU (tests/test_sparsemax_adjoint.py: plain fp32 arithmetic alone stays within TOL / 2 and flips no support on a cell
+with E != 0; DESIGN.md 3.20 has the figures and what the rule rejects)."""
+import numpy as np
+import pytest
+import torch
+
+import sparsemax_adjoint_ref as adj
+import sparsemax_ref as ref
+import strip_schedule
+from parity import TOL, abs_err, rel_err
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+B = adj.B
+NW, SW = ref.NW, ref.SW
+NAMES = {NW: "nw", SW: "sw"}
+ABI = [c for c in adj.CASES if c[1:3] != (3, 2100)]          # 3 x 2100 exceeds the column limit: through the module, below
+TRANSPOSED = [c for c in adj.CASES if c[1:3] == (3, 2100)]
+_et = np.random.RandomState(3).uniform(0.25, 1.0, 2)
+ET = np.asarray([_et[0], -_et[1], 0.0], np.float32)            # every case again: a random Et of either sign and one Et = 0; |Et| <= 1
+LENS = ref.LENS
+
+
+def _engine():
+    from deepblast_amd._engine import get_engine
+    return get_engine()
+
+
+def _decoder(variant=NW):
+    from deepblast_amd.sparse import SparsemaxDecoder
+    return SparsemaxDecoder(NAMES[variant], second_order=True)
+
+
+def _dev(x):
+    return None if x is None else torch.from_numpy(np.array(x, copy=True, order="C")).to(DEV)
+
+
+def _bits(x):
+    return np.ascontiguousarray(x).view(np.uint32)
+
+
+def _ff(n):
+    """n floats of 0xFF bytes (NaN)"""
+    return torch.empty(n * 4, dtype=torch.uint8, device=DEV).fill_(0xFF).view(torch.float32)
+
+
+def _forward(th, a, variant, lens=None):
+    t, A, ln = _dev(th), _dev(a), _dev(lens)
+    Vt, state = _engine().sparsemax_forward(t, A, variant, ln)
+    return state, ln
+
+
+def _pair(state, ze, zg, shape, variant, ln=None, et=None, state_d=None, want_G=True, waves=0):
+    """the two adjoint entries with raw pointers; ze, zg: device tensors, addresses or None; state_d, Vtd, Ed and Gd start as 0xFF
+    bytes (NaN) -> numpy (Vtd, Ed, Gd)"""
+    lib = _engine().lib
+    Bn, N, M = shape
+    stream = torch.cuda.current_stream().cuda_stream
+    ptr = lambda z: z.data_ptr() if isinstance(z, torch.Tensor) else z
+    if state_d is None:
+        state_d = _ff(lib.sdp_sparsemax_adjoint_state_bytes(Bn, N, M) // 4)
+    Vtd, Ed, Gd = _ff(Bn), _ff(Bn * N * M), (_ff(Bn * N * M) if want_G else None)
+    Et = torch.ones(Bn, device=DEV) if et is None else _dev(et)
+    lp = None if ln is None else ln.data_ptr()
+    v = variant | (waves << 12)
+    assert lib.sdp_sparsemax_adjoint_forward_f32(state.data_ptr(), ptr(ze), ptr(zg), state_d.data_ptr(), Vtd.data_ptr(), Bn, N, M, lp,
+                                                 v, 0, stream) == 0
+    assert lib.sdp_sparsemax_adjoint_backward_f32(state.data_ptr(), state_d.data_ptr(), Et.data_ptr(), Ed.data_ptr(),
+                                                  None if Gd is None else Gd.data_ptr(), Bn, N, M, lp, v, 0, stream) == 0
+    torch.cuda.synchronize()
+    return Vtd.cpu().numpy(), Ed.view(Bn, N, M).cpu().numpy(), None if Gd is None else Gd.view(Bn, N, M).cpu().numpy()
+
+
+def _run(th, a, ze, zg, variant=NW, lens=None, et=None, **kw):
+    state, ln = _forward(th, a, variant, lens)
+    return _pair(state, _dev(ze), _dev(zg), th.shape, variant, ln, et, **kw)
+
+
+def _check(got, want, what):
+    errs = {"Vtd": rel_err(got[0], want["Vtd"]), "Ed": abs_err(got[1], want["Ed"])}
+    if got[2] is not None:
+        errs["Gd"] = abs_err(got[2], want["Gd"])
+    print(what, " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
+    assert all(np.isfinite(v) and v <= TOL for v in errs.values()), (what, errs)
+    return errs
+
+
+def _zero_outside(Ed, Gd, lens, what):
+    N, M = Ed.shape[1:]
+    for b, (n, m) in enumerate(lens):
+        mask = np.ones((N, M), bool)
+        mask[:max(min(n, N), 0), :max(min(m, M), 0)] = False
+        assert not _bits(Ed[b])[mask].any() and not _bits(Gd[b])[mask].any(), (what, b, n, m)     # +0, by bit pattern
+
+
+@pytest.mark.parametrize("family,n,m,variant", ABI, ids=[f"{f}-{n}x{m}-{NAMES[v]}" for (f, n, m, v) in ABI])
+def test_against_float64(family, n, m, variant):
+    th, a, ze, zg = adj.case(family, n, m)
+    want = adj.want(family, n, m, variant)
+    state, _ = _forward(th, a, variant)
+    ZE, ZG = _dev(ze), _dev(zg)
+    got = _pair(state, ZE, ZG, th.shape, variant)
+    _check(got, want, f"{family} {n}x{m} {NAMES[variant]}")
+    # an Et of either sign and one Et = 0: Ed and Gd scale with it, Vtd does not depend on it
+    again = _pair(state, ZE, ZG, th.shape, variant, et=ET)
+    _check(again, adj.scaled(want, ET), f"{family} {n}x{m} {NAMES[variant]} Et")
+    assert np.array_equal(_bits(again[0]), _bits(got[0])) and not again[1][2].any() and not again[2][2].any()
+    # +0 below lo (SW: row 0 and column 0 of theta take no part)
+    if variant == SW:
+        for x in got[1:]:
+            assert not _bits(x[:, 0]).any() and not _bits(x[:, :, 0]).any()
+
+
+@pytest.mark.parametrize("family,n,m,variant", TRANSPOSED, ids=[f"{f}-{n}x{m}-{NAMES[v]}" for (f, n, m, v) in TRANSPOSED])
+def test_the_transposed_route_through_the_module(family, n, m, variant):
+    """3 x 2100 is swept as 2100 x 3; the gradients of a gradient come back in the caller's coordinates"""
+    th, a, ze, zg = adj.case(family, n, m)
+    want = adj.want(family, n, m, variant)
+    for et in (np.ones(B, np.float32), ET):
+        t, A = _dev(th).requires_grad_(), _dev(a).requires_grad_()
+        c = _dev(et).requires_grad_()             # a weight on Vt: its gradient is Vtd
+        gt, ga = torch.autograd.grad((_decoder(variant)(t, A) * c).sum(), (t, A), create_graph=True)
+        Ed, Gd, Vtd = torch.autograd.grad((gt * _dev(ze)).sum() + (ga * _dev(zg)).sum(), (t, A, c))
+        torch.cuda.synchronize()
+        assert tuple(Ed.shape) == (B, n, m) and tuple(Gd.shape) == (B, n, m) and tuple(Vtd.shape) == (B,)
+        _check((Vtd.cpu().numpy(), Ed.cpu().numpy(), Gd.cpu().numpy()), adj.scaled(want, et), f"transposed {family} {NAMES[variant]} Et={et[0]}")
+
+
+# ---- full width, the 64 KB (first order) / 128 KB (adjoint backward) launch and seven waves ----
+@pytest.mark.parametrize("family,n,m,variant", adj.WIDE_CASES, ids=[f"{f}-{n}x{m}" for (f, n, m, _) in adj.WIDE_CASES])
+def test_full_width_against_float64(family, n, m, variant):
+    c = strip_schedule.check_wide_shapes("sdp_sparsemax.h")
+    assert (strip_schedule.strips(c, n), strip_schedule.waves(c, n, m)) == strip_schedule.WIDE[(n, m)]
+    got = _run(*adj.wide_case(family, n, m), variant)
+    _check(got, adj.wide_want(family, n, m, variant), f"wide {family} {n}x{m}")
+
+
+def _lens_case():
+    th, a, ze, zg = adj.case("unit", 130, 150, len(LENS))
+    return th, a, ze, zg, np.asarray(LENS, np.int32)
+
+
+def test_lengths():
+    th, a, ze, zg, lens = _lens_case()
+    want = adj.batch(th, a, ze, zg, NW, lens)
+    Vtd, Ed, Gd = _run(th, a, ze, zg, NW, lens)
+    for b, (n, m) in enumerate(LENS):       # every pair against the definition on its own slice
+        one = {k: v[b:b + 1] for k, v in want.items()}
+        _check((Vtd[b:b + 1], Ed[b:b + 1], Gd[b:b + 1]), one, f"lens {n}x{m}")
+        if n < 1 or m < 1:
+            assert _bits(Vtd[b:b + 1])[0] == 0
+    _zero_outside(Ed, Gd, LENS, "lens")
+    assert np.abs(want["Ed"][5]).max() > 0.05
+
+
+def test_forbidden_gaps():
+    """30 % of the cells of 130 x 150 `unit` given A = -inf (`model`, the first order's masked case, fails the admission rule
+    here): Gd there is bit +0, nothing is NaN"""
+    th, a, ze, zg, gone = adj.masked_case()
+    want = adj.batch(th, a, ze, zg, NW)
+    for et in (None, -np.ones(B, np.float32)):
+        Vtd, Ed, Gd = _run(th, a, ze, zg, NW, et=et)
+        assert np.isfinite(Vtd).all() and np.isfinite(Ed).all() and np.isfinite(Gd).all()
+        _check((Vtd, Ed, Gd), want if et is None else adj.scaled(want, et), f"A = -inf, Et = {1 if et is None else -1}")
+        assert not _bits(Gd)[gone].any()                  # +0, by bit pattern, whatever the sign of Et
+
+
+def test_more_pairs_than_cus():
+    th, a, ze, zg = adj.case("unit", 8, 8, 300)
+    _check(_run(th, a, ze, zg), adj.batch(th, a, ze, zg), "B=300")
+
+
+# ---- bit-level checks ----
+@pytest.mark.parametrize("family,n,m", [("unit", 130, 150), ("unit", 577, 40)])
+def test_two_calls_give_the_same_bits(family, n, m):
+    args = adj.case(family, n, m)
+    first, second = _run(*args), _run(*args)
+    for x, y in zip(first, second):
+        assert np.array_equal(_bits(x), _bits(y))
+
+
+@pytest.mark.parametrize("variant", [NW, SW], ids=["nw", "sw"])
+def test_every_wave_count_gives_the_same_bits(variant):
+    """SDP_WAVES(1) .. SDP_WAVES(8) on 577 x 40: ten strips, so every count from 1 to 8 runs as it is asked"""
+    th, a, ze, zg = adj.case("unit", 577, 40)
+    state, _ = _forward(th, a, variant)
+    ZE, ZG = _dev(ze), _dev(zg)
+    runs = [tuple(_bits(x) for x in _pair(state, ZE, ZG, th.shape, variant, et=ET, waves=w)) for w in range(0, 9)]
+    for w, run in enumerate(runs[1:], 1):
+        for x, y, what in zip(runs[0], run, ("Vtd", "Ed", "Gd")):
+            assert np.array_equal(x, y), (what, "waves", w)
+    _check(tuple(x.view(np.float32) for x in runs[0]), adj.scaled(adj.want("unit", 577, 40, variant), ET), f"waves {NAMES[variant]}")
+
+
+@pytest.mark.parametrize("family,n,m,variant", [("model", 65, 33, SW), ("unit", 130, 150, NW)])
+def test_one_cotangent_alone(family, n, m, variant):
+    """NULL means zeros, bit for bit; Gd = NULL changes no bit of Ed and Vtd"""
+    th, a, ze, zg = adj.case(family, n, m)
+    state, _ = _forward(th, a, variant)
+    ZE, ZG, zero = _dev(ze), _dev(zg), torch.zeros(th.shape, device=DEV)
+    full = _pair(state, ZE, ZG, th.shape, variant)
+    for which, (e, g), (e0, g0), (ne, ng) in (("ZG = NULL", (ZE, None), (ZE, zero), (ze, None)), ("ZE = NULL", (None, ZG), (zero, ZG), (None, zg))):
+        got, zeros = _pair(state, e, g, th.shape, variant), _pair(state, e0, g0, th.shape, variant)
+        _check(got, adj.batch(th, a, ne, ng, variant), f"{family} {n}x{m} {which}")
+        for x, y in zip(got, zeros):
+            assert np.array_equal(_bits(x), _bits(y)), which
+    Vtd, Ed, none = _pair(state, ZE, ZG, th.shape, variant, want_G=False)
+    assert none is None and np.array_equal(_bits(Ed), _bits(full[1])) and np.array_equal(_bits(Vtd), _bits(full[0]))
+
+
+@pytest.mark.parametrize("with_lens", [False, True], ids=["full", "lens"])
+def test_poisoned_buffers(with_lens):
+    """the adjoint sweeps read nothing that the sweeps before them did not write, and leave nothing unwritten: both state buffers
+    start as 0xFF bytes (NaN), and so do Vtd, Ed and Gd (_pair fills them) -- no bit of a result changes, and no NaN is left"""
+    eng = _engine()
+    if with_lens:
+        th, a, ze, zg, lens = _lens_case()
+        variant = NW
+    else:
+        (th, a, ze, zg), lens, variant = adj.case("steep", 65, 33), None, SW
+    t, A, ZE, ZG, ln = _dev(th), _dev(a), _dev(ze), _dev(zg), _dev(lens)
+    shape = tuple(t.shape)
+    # the clean run: fresh zeroed buffers through the engine
+    Vt, state = eng.sparsemax_forward(t, A, variant, ln, state_out=torch.zeros(eng.lib.sdp_sparsemax_state_bytes(*shape) // 4, device=DEV))
+    zeros = torch.zeros(eng.lib.sdp_sparsemax_adjoint_state_bytes(*shape) // 4, device=DEV)
+    Vtd0, sd = eng.sparsemax_adjoint_forward(state, ZE, ZG, shape, variant, ln, state_d_out=zeros)
+    assert sd is zeros
+    Ed0, Gd0 = eng.sparsemax_adjoint_backward(state, sd, torch.ones(shape[0], device=DEV), shape, variant, ln)
+    torch.cuda.synchronize()
+    clean = tuple(x.cpu().numpy() for x in (Vtd0, Ed0, Gd0))
+    # the poisoned run
+    poison = _ff(state.numel())
+    Vt1, state1 = eng.sparsemax_forward(t, A, variant, ln, state_out=poison)
+    state_d = _ff(zeros.numel())
+    got = _pair(state1, ZE, ZG, shape, variant, ln, state_d=state_d)
+    assert torch.isnan(state1).any() and torch.isnan(state_d).any()      # (the ramps of every strip stay unwritten)
+    for x, y in zip(clean, got):
+        assert np.isfinite(y).all() and np.array_equal(_bits(x), _bits(y))
+
+
+PAD = 4096                                      # floats in front of and behind every tensor
+POISON = np.array([np.nan, np.inf, -np.inf, 1e30, -1e30], np.float32)
+
+
+def test_what_lies_beside_the_cotangents_takes_no_part():
+    """ZE and ZG at plane offsets of 0 .. 3 floats (the four-float loads are `packed, aligned(4)` for this), once among zeros and
+    once among NaN, +-inf and +-1e30 -- in front, behind and in every pair's padding: the same bits of Vtd, Ed and Gd"""
+    th, a, ze, zg = adj.case("unit", 130, 150)
+    lens = ((127, 145), (130, 150), (65, 33))
+    Bn, N, M = th.shape
+    size = Bn * N * M
+    state, ln = _forward(th, a, NW, np.asarray(lens, np.int32))
+    rng = np.random.RandomState(77)
+    runs = []
+    for offset in range(4):
+        for dirty in (False, True):
+            ptrs, keep = [], []
+            for src in (ze, zg):
+                fill = POISON[rng.randint(0, 5, size + 2 * PAD + 4)] if dirty else np.zeros(size + 2 * PAD + 4, np.float32)
+                x = src.copy()
+                for b, (n, m) in enumerate(lens):
+                    pad = POISON[rng.randint(0, 5, (N, M))] if dirty else np.zeros((N, M), np.float32)
+                    x[b, n:, :] = pad[n:, :]
+                    x[b, :, m:] = pad[:, m:]
+                fill[PAD + offset:PAD + offset + size] = x.reshape(-1)
+                buf = torch.from_numpy(fill).to(DEV)
+                keep.append(buf)
+                ptrs.append(buf[PAD + offset:].data_ptr())
+            assert ptrs[0] % 16 == 4 * offset
+            runs.append(tuple(_bits(x) for x in _pair(state, ptrs[0], ptrs[1], (Bn, N, M), NW, ln)))
+    for k, run in enumerate(runs[1:], 1):
+        for x, y, what in zip(runs[0], run, ("Vtd", "Ed", "Gd")):
+            assert np.array_equal(x, y), (what, "offset", k // 2, "dirty", k % 2, int((x != y).sum()))
+    got = tuple(x.view(np.float32) for x in runs[0])
+    _check(got, adj.batch(th, a, ze, zg, NW, lens), "raw pointers")
+    _zero_outside(got[1], got[2], lens, "raw pointers")
+
+
+# ---- the staircase on the device ----
+@pytest.mark.parametrize("variant", [NW, SW], ids=["nw", "sw"])
+def test_on_the_staircase_the_second_order_vanishes(variant):
+    """the planted staircase at 130 x 150: every support has one element, so Ed and Gd are zero everywhere, and Vtd is the sum of
+    ZE over the path plus ZG over its gap cells"""
+    th, a, paths = ref.staircase(5, B, 130, 150)
+    ze, zg = adj.cotangents(9, B, 130, 150)
+    Vtd, Ed, Gd = _run(th, a, ze, zg, variant, et=np.asarray([1.0, -2.0, 0.5], np.float32))
+    assert not Ed.any() and not Gd.any()
+    _check((Vtd, Ed, Gd), adj.batch(th, a, ze, zg, variant), f"staircase {NAMES[variant]}")
+    for b, cells in enumerate(paths):
+        on = [(i, j) for (i, j) in cells if i >= variant and j >= variant]
+        path_sum = sum(float(ze[b, i, j]) for (i, j) in on) + sum(float(zg[b, i, j]) for (i, j) in on if a[b, i, j] == np.float32(-0.5))
+        assert abs(Vtd[b] - path_sum) <= TOL * max(1.0, abs(path_sum))
+
+
+# ---- the module ----
+def _mce_inputs():
+    rng = np.random.RandomState(31)
+    Bn, N, M = 3, 9, 12
+    th, a = ref.family("unit", 31, Bn, N, M)
+    Yt = (rng.rand(Bn, N, M) < 0.2).astype(np.float32)
+    G = (rng.rand(Bn, N, M) < 0.8).astype(np.float32)
+    return th, a, Yt, G, [9, 7, 9], [12, 12, 5]
+
+
+def test_a_loss_on_the_sparse_matrix_trains_theta_and_A():
+    """MatrixCrossEntropy on decode(), and the gradient of a gradient, against the torch float64 restatement differentiated twice"""
+    import loss_ref
+    from deepblast_amd.losses import MatrixCrossEntropy, decode_loss
+    th, a, Yt, G, xl, yl = _mce_inputs()
+    value, gt64, ga64 = adj.torch_batch(th, a, lambda E, _: loss_ref.torch_reference("mce", torch.from_numpy(Yt).double(), E, xl, yl,
+                                                                                     torch.from_numpy(G)))
+    dec = _decoder()
+    t, A = _dev(th).requires_grad_(), _dev(a).requires_grad_()
+    loss = MatrixCrossEntropy()(_dev(Yt), dec.decode(t, A), xl, yl, _dev(G))
+    loss.backward()
+    torch.cuda.synchronize()
+    errs = {"loss": rel_err(loss.item(), value), "theta": abs_err(t.grad.cpu().numpy(), gt64), "A": abs_err(A.grad.cpu().numpy(), ga64)}
+    print("mce on decode()", " ".join(f"{k}={v:.2e}" for k, v in errs.items()), "max|grad| %.3g %.3g" % (np.abs(gt64).max(), np.abs(ga64).max()))
+    assert errs["loss"] <= TOL and errs["theta"] <= TOL and errs["A"] <= TOL and np.abs(ga64).max() > 1e-3
+    # decode_loss: the same composition, the same bits
+    t2, A2 = _dev(th).requires_grad_(), _dev(a).requires_grad_()
+    value2, E = decode_loss(dec, MatrixCrossEntropy(), t2, A2, _dev(Yt), xl, yl, _dev(G))
+    value2.backward()
+    assert not E.requires_grad and torch.equal(t2.grad, t.grad) and torch.equal(A2.grad, A.grad)
+    # the gradient of a gradient, and the third order
+    _, st64, sa64 = adj.torch_batch(th, a, lambda E, _: (E * E).sum())
+    t3, A3 = _dev(th).requires_grad_(), _dev(a).requires_grad_()
+    gt, _ = torch.autograd.grad(dec(t3, A3).sum(), (t3, A3), create_graph=True)
+    st, sa = torch.autograd.grad((gt * gt).sum(), (t3, A3), create_graph=True)
+    errs = {"theta": abs_err(st.detach().cpu().numpy(), st64), "A": abs_err(sa.detach().cpu().numpy(), sa64)}
+    print("(gt * gt).sum()", " ".join(f"{k}={v:.2e}" for k, v in errs.items()), "max|grad| %.3g %.3g" % (np.abs(st64).max(), np.abs(sa64).max()))
+    assert errs["theta"] <= TOL and errs["A"] <= TOL and np.abs(sa64).max() > 1e-3
+    with pytest.raises(NotImplementedError, match="third order.*is not built"):
+        st.sum().backward()
