@@ -339,3 +339,90 @@ def test_c_abi_with_raw_pointers():
     assert np.array_equal(_bits(Vv.cpu().numpy()), _bits(want["Vt"])) and np.array_equal(ends_v.cpu().numpy(), want["ends"])
     assert np.array_equal(_bits(E_only.cpu().numpy()), _bits(want["E"]))
     assert lib.sdp_hard_local_forward_f32(t.data_ptr(), A.data_ptr(), state.data_ptr(), Vt.data_ptr(), None, 2, 9, 12, None, 0, 0, stream) == -1
+
+
+# ---- the operator at its edges: what lies beside the tensors, and what is written ----
+PAD = 4096                                      # words in front of and behind every tensor
+PATTERN = 0x5A5AC3C3                            # what every output buffer holds before a call
+POISON = np.array([np.nan, np.inf, -np.inf, 1e30, -1e30], np.float32)
+RAW_LENS = ((127, 145), (130, 150), (65, 33), (0, 9))
+
+
+def _guarded(n, offset=0, dtype=torch.float32):
+    """-> (buffer, view): `n` words at PAD + offset of a buffer filled with PATTERN"""
+    buf = torch.full((n + 2 * PAD + 4,), PATTERN, dtype=torch.int32, device=DEV)
+    return buf, buf[PAD + offset:PAD + offset + n].view(dtype)
+
+
+def _untouched(buf, n, offset, what):
+    assert bool((buf[:PAD + offset] == PATTERN).all()) and bool((buf[PAD + offset + n:] == PATTERN).all()), what
+
+
+def _raw_run(th, a, variant, lens, offset, dirty, rng):
+    """the three C entries with raw pointers: theta and A at `offset` floats inside buffers of zeros (dirty: of POISON), every
+    pair's padding beyond `lens` likewise; Vt, the ends, the state (exactly sdp_hard_state_bytes long), E, the cap * 3 list rows and
+    the counts views into buffers of PATTERN; the walk once with states / counts and once with them NULL
+    -> (Vt, ends, E, states, counts) numpy"""
+    lib = _engine().lib
+    B, N, M = th.shape
+    size = B * N * M
+    stream = torch.cuda.current_stream().cuda_stream
+    ins = []
+    for src in (th, a):
+        fill = POISON[rng.randint(0, 5, size + 2 * PAD + 4)] if dirty else np.zeros(size + 2 * PAD + 4, np.float32)
+        x = src.copy()
+        if lens is not None:
+            for b, (n, m) in enumerate(lens):
+                pad = POISON[rng.randint(0, 5, (N, M))] if dirty else np.zeros((N, M), np.float32)
+                x[b, n:, :] = pad[n:, :]
+                x[b, :, m:] = pad[:, m:]
+        fill[PAD + offset:PAD + offset + size] = x.reshape(-1)
+        ins.append(torch.from_numpy(fill).to(DEV))
+    t, A = (buf[PAD + offset:PAD + offset + size] for buf in ins)
+    assert t.data_ptr() % 16 == 4 * offset
+    lp = None if lens is None else _dev(np.asarray(lens, np.int32))
+    lpp = None if lp is None else lp.data_ptr()
+    nbytes, cap = lib.sdp_hard_state_bytes(B, N, M), lib.sdp_traceback_capacity(N, M)
+    assert nbytes % 4 == 0 and cap == N + M + 2
+    (sbuf, state), (vbuf, Vt), (wbuf, Vv) = _guarded(nbytes // 4, 0, torch.int32), _guarded(B, offset), _guarded(B, offset)
+    (nbuf, ends), (mbuf, ends_v) = _guarded(2 * B, offset, torch.int32), _guarded(2 * B, offset, torch.int32)
+    (ebuf, E), (fbuf, E2) = _guarded(size, offset), _guarded(size, offset)
+    (lbuf, states), (cbuf, counts) = _guarded(B * cap * 3, 0, torch.int32), _guarded(B, offset, torch.int32)
+    et = _dev(np.resize(np.asarray(ET, np.float32), B))
+    assert lib.sdp_hard_local_forward_f32(t.data_ptr(), A.data_ptr(), state.data_ptr(), Vt.data_ptr(), ends.data_ptr(), B, N, M, lpp,
+                                          variant, 0, stream) == 0
+    assert lib.sdp_hard_local_forward_value_f32(t.data_ptr(), A.data_ptr(), Vv.data_ptr(), ends_v.data_ptr(), B, N, M, lpp, variant, 0,
+                                                stream) == 0
+    assert lib.sdp_hard_local_walk_f32(state.data_ptr(), ends.data_ptr(), et.data_ptr(), E.data_ptr(), states.data_ptr(), counts.data_ptr(),
+                                       B, N, M, lpp, variant, 0, stream) == 0
+    assert lib.sdp_hard_local_walk_f32(state.data_ptr(), ends.data_ptr(), et.data_ptr(), E2.data_ptr(), None, None, B, N, M, lpp, variant,
+                                       0, stream) == 0
+    torch.cuda.synchronize()
+    for buf, n, off, what in ((sbuf, nbytes // 4, 0, "state"), (vbuf, B, offset, "Vt"), (wbuf, B, offset, "Vt of the value-only sweep"),
+                              (nbuf, 2 * B, offset, "ends"), (mbuf, 2 * B, offset, "ends of the value-only sweep"),
+                              (ebuf, size, offset, "E"), (fbuf, size, offset, "E with states = NULL"), (lbuf, B * cap * 3, 0, "states"),
+                              (cbuf, B, offset, "counts")):
+        _untouched(buf, n, off, (what, offset, dirty))
+    assert np.array_equal(_bits(Vv.cpu().numpy()), _bits(Vt.cpu().numpy())) and torch.equal(ends_v, ends)
+    assert np.array_equal(_bits(E2.cpu().numpy()), _bits(E.cpu().numpy()))
+    return (Vt.cpu().numpy(), ends.view(B, 2).cpu().numpy(), E.view(B, N, M).cpu().numpy(), states.view(B, cap, 3).cpu().numpy(),
+            counts.cpu().numpy())
+
+
+@pytest.mark.parametrize("variant", [0, 1], ids=["nw", "sw"])
+@pytest.mark.parametrize("with_lens", [True, False], ids=["lens", "full"])
+def test_what_lies_beside_the_matrix_takes_no_part_and_nothing_is_written_outside(with_lens, variant):
+    """theta and A at plane offsets of 0 .. 3 floats (the four-float loads are `packed, aligned(4)` for this), once among zeros and
+    once among NaN, +-inf and +-1e30 -- in front, behind and in every pair's padding: the reference's bits every time, and not a
+    word written outside Vt, the ends, the state, E, the list rows or the counts"""
+    lens = RAW_LENS if with_lens else None
+    th, a = _case("ties", 25, 4 if with_lens else 3, 130, 150)
+    want = ref.batch(th, a, variant, lens, Et=np.resize(np.asarray(ET, np.float32), th.shape[0]), fwd=ref.forward_fast)
+    assert all(want["cells"][:3])
+    rng = np.random.RandomState(77)
+    for offset in range(4):
+        for dirty in (False, True):
+            got = _raw_run(th, a, variant, lens, offset, dirty, rng)
+            _check(got, want, ("raw pointers", offset, dirty))
+            if with_lens:       # the empty pair: no alignment, and of its list rows only the last one is written
+                assert (got[3][3, :-1].view(np.uint32) == PATTERN).all() and got[4][3] == 0 and tuple(got[1][3]) == (-1, -1)

@@ -237,6 +237,18 @@ def test_the_further_gpu_cases_stay_inside_plain_fp32():
     assert np.abs(w32["E"] - w["E"]).max() > TOL / 4
 
 
+def test_the_edge_gpu_cases_stay_inside_plain_fp32():
+    """the fixed edge cases of tests/test_sparsemax_gpu.py: the raw-pointer case with and without lengths, lengths out of range,
+    more pairs than CUs, and the full-width lengths"""
+    th, a = ref.case("model", 130, 150)
+    for variant in (NW, SW):
+        _admit(th, a, variant, ("raw pointers", variant))
+        _admit(th, a, variant, ("raw pointers, lengths", variant), lens=((127, 145), (130, 150), (65, 33)))
+        _admit(*ref.case("unit", 130, 150, 4), variant, ("lengths out of range", variant), lens=[(-3, 5), (5, -1), (137, 159), (130, 0)])
+        _admit(*ref.case("model", 8, 8, 300), variant, ("B = 300", variant))
+    _admit(*ref.case("unit", 513, 2048, 5), NW, "full-width lengths", lens=((513, 2048), (449, 1983), (512, 1), (1, 2048), (0, 7)))
+
+
 def test_the_wide_shapes_are_on_the_routes_they_are_named_for():
     """8 waves and exactly 64 KB of LDS at M = 1982, seven waves from 1983 on (csrc/sdp_sparsemax.h, csrc/sdp_api.hip)"""
     c = strip_schedule.check_wide_shapes("sdp_sparsemax.h")

@@ -280,6 +280,61 @@ def test_what_lies_beside_the_cotangents_takes_no_part():
     _zero_outside(got[1], got[2], lens, "raw pointers")
 
 
+PATTERN = 0x5A5AC3C3                            # what every output buffer holds before a call (as a float: 1.5e16)
+
+
+def _guarded(n, offset=0):
+    """-> (buffer, view): `n` floats at PAD + offset of a buffer filled with PATTERN"""
+    buf = torch.full((n + 2 * PAD + 4,), PATTERN, dtype=torch.int32, device=DEV).view(torch.float32)
+    return buf, buf[PAD + offset:PAD + offset + n]
+
+
+def _untouched(buf, n, offset, what):
+    words = buf.view(torch.int32)
+    assert bool((words[:PAD + offset] == PATTERN).all()) and bool((words[PAD + offset + n:] == PATTERN).all()), what
+
+
+@pytest.mark.parametrize("variant", [NW, SW], ids=["nw", "sw"])
+@pytest.mark.parametrize("with_lens", [True, False], ids=["lens", "full"])
+def test_nothing_is_written_outside_the_outputs(with_lens, variant):
+    """the outputs' half of the test above: Vtd, Ed and Gd at plane offsets of 0 .. 3 floats and an adjoint state exactly
+    sdp_sparsemax_adjoint_state_bytes long, all inside buffers of a pattern -- with Gd and with Gd = NULL the same bits every time,
+    and not a word changes outside the outputs"""
+    lib = _engine().lib
+    th, a, ze, zg = adj.case("unit", 130, 150)
+    lens = ((127, 145), (130, 150), (65, 33)) if with_lens else None
+    Bn, N, M = th.shape
+    size = Bn * N * M
+    state, ln = _forward(th, a, variant, None if lens is None else np.asarray(lens, np.int32))
+    lp = None if ln is None else ln.data_ptr()
+    ZE, ZG, Et = _dev(ze), _dev(zg), _dev(ET)
+    stream = torch.cuda.current_stream().cuda_stream
+    nd = lib.sdp_sparsemax_adjoint_state_bytes(Bn, N, M) // 4
+    runs = []
+    for offset in range(4):
+        (dbuf, state_d), (vbuf, Vtd) = _guarded(nd), _guarded(Bn, offset)
+        (ebuf, Ed), (gbuf, Gd), (fbuf, Ed2) = _guarded(size, offset), _guarded(size, offset), _guarded(size, offset)
+        assert Ed.data_ptr() % 16 == 4 * offset
+        assert lib.sdp_sparsemax_adjoint_forward_f32(state.data_ptr(), ZE.data_ptr(), ZG.data_ptr(), state_d.data_ptr(), Vtd.data_ptr(),
+                                                     Bn, N, M, lp, variant, 0, stream) == 0
+        assert lib.sdp_sparsemax_adjoint_backward_f32(state.data_ptr(), state_d.data_ptr(), Et.data_ptr(), Ed.data_ptr(), Gd.data_ptr(),
+                                                      Bn, N, M, lp, variant, 0, stream) == 0
+        assert lib.sdp_sparsemax_adjoint_backward_f32(state.data_ptr(), state_d.data_ptr(), Et.data_ptr(), Ed2.data_ptr(), None,
+                                                      Bn, N, M, lp, variant, 0, stream) == 0
+        torch.cuda.synchronize()
+        for buf, n, off, what in ((dbuf, nd, 0, "the adjoint state"), (vbuf, Bn, offset, "Vtd"), (ebuf, size, offset, "Ed"),
+                                  (gbuf, size, offset, "Gd"), (fbuf, size, offset, "Ed with Gd = NULL")):
+            _untouched(buf, n, off, (what, offset))
+        runs.append(tuple(_bits(x.cpu().numpy()) for x in (Vtd, Ed.view(Bn, N, M), Gd.view(Bn, N, M))))
+        assert np.array_equal(_bits(Ed2.view(Bn, N, M).cpu().numpy()), runs[-1][1])
+    for k, run in enumerate(runs[1:], 1):
+        for x, y, what in zip(runs[0], run, ("Vtd", "Ed", "Gd")):
+            assert np.array_equal(x, y), (what, "offset", k, int((x != y).sum()))
+    got = tuple(x.view(np.float32) for x in runs[0])
+    _check(got, adj.scaled(adj.batch(th, a, ze, zg, variant, lens), ET), f"guarded outputs {NAMES[variant]}")
+    _zero_outside(got[1], got[2], lens if with_lens else [(N, M)] * Bn, "guarded outputs")
+
+
 # ---- the staircase on the device ----
 @pytest.mark.parametrize("variant", [NW, SW], ids=["nw", "sw"])
 def test_on_the_staircase_the_second_order_vanishes(variant):

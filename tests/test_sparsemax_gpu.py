@@ -306,3 +306,126 @@ def test_full_width_against_float64(family, n, m, variant):
     second = _run(th, a, variant)
     for x, y in zip(got, second):
         assert np.array_equal(_bits(x), _bits(y))
+
+
+WIDE_LENS = ((513, 2048), (449, 1983), (512, 1), (1, 2048), (0, 7))     # nine strips and eight; a column; a row; nothing
+
+
+def test_full_width_lengths():
+    """pairs of eight and of nine strips, a single column, a single row and an empty pair in one seven-wave launch"""
+    N, M = 513, 2048
+    th, a = _case("unit", N, M, len(WIDE_LENS))
+    lens = np.asarray(WIDE_LENS, np.int32)
+    want = ref.batch_wavefront(th, a, NW, lens)
+    Vt, E, G = _run(th, a, NW, lens)
+    for b, (n, m) in enumerate(WIDE_LENS):
+        one = {k: v[b:b + 1] for k, v in want.items()}
+        _check((Vt[b:b + 1], E[b:b + 1], G[b:b + 1]), one, f"wide lens {n}x{m}")
+        mask = np.ones((N, M), bool)
+        mask[:n, :m] = False
+        assert not _bits(E[b])[mask].any() and not _bits(G[b])[mask].any(), (n, m)     # +0, by bit pattern
+    assert _bits(Vt)[-1] == 0 and not _bits(E[-1]).any() and float(want["G"][1].max()) > 0.05
+    Vs = _decoder().score(_dev(th), _dev(a), _dev(lens))
+    assert np.array_equal(_bits(Vs.cpu().numpy()), _bits(Vt))
+
+
+# ---- the operator at its edges ----
+PAD = 4096                                      # floats in front of and behind every tensor
+PATTERN = 0x5A5AC3C3                            # what every output buffer holds before a call (as a float: 1.5e16)
+POISON = np.array([np.nan, np.inf, -np.inf, 1e30, -1e30], np.float32)
+RAW_LENS = ((127, 145), (130, 150), (65, 33))
+
+
+def _guarded(n, offset=0):
+    """-> (buffer, view): `n` floats at PAD + offset of a buffer filled with PATTERN"""
+    buf = torch.full((n + 2 * PAD + 4,), PATTERN, dtype=torch.int32, device=DEV).view(torch.float32)
+    return buf, buf[PAD + offset:PAD + offset + n]
+
+
+def _untouched(buf, n, offset, what):
+    words = buf.view(torch.int32)
+    assert bool((words[:PAD + offset] == PATTERN).all()) and bool((words[PAD + offset + n:] == PATTERN).all()), what
+
+
+def _raw_run(th, a, variant, lens, offset, dirty, rng):
+    """the three C entries with raw pointers: theta and A at `offset` floats inside buffers of zeros (dirty: of POISON), every
+    pair's padding beyond `lens` likewise; Vt, the state, E and G views into buffers of PATTERN -> bits of (Vt, E, G)"""
+    lib = _engine().lib
+    Bn, N, M = th.shape
+    size = Bn * N * M
+    stream = torch.cuda.current_stream().cuda_stream
+    ins = []
+    for src in (th, a):
+        fill = POISON[rng.randint(0, 5, size + 2 * PAD + 4)] if dirty else np.zeros(size + 2 * PAD + 4, np.float32)
+        x = src.copy()
+        if lens is not None:
+            for b, (n, m) in enumerate(lens):
+                pad = POISON[rng.randint(0, 5, (N, M))] if dirty else np.zeros((N, M), np.float32)
+                x[b, n:, :] = pad[n:, :]
+                x[b, :, m:] = pad[:, m:]
+        fill[PAD + offset:PAD + offset + size] = x.reshape(-1)
+        ins.append(torch.from_numpy(fill).to(DEV))
+    t, A = (buf[PAD + offset:PAD + offset + size] for buf in ins)
+    assert t.data_ptr() % 16 == 4 * offset
+    ln = None if lens is None else _dev(np.asarray(lens, np.int32))
+    lp = None if ln is None else ln.data_ptr()
+    nstate = lib.sdp_sparsemax_state_bytes(Bn, N, M) // 4
+    (sbuf, state), (vbuf, Vt), (wbuf, Vv) = _guarded(nstate), _guarded(Bn, offset), _guarded(Bn, offset)
+    (ebuf, E), (gbuf, G), (fbuf, E2) = _guarded(size, offset), _guarded(size, offset), _guarded(size, offset)
+    et = _dev(ET)
+    assert lib.sdp_sparsemax_forward_f32(t.data_ptr(), A.data_ptr(), state.data_ptr(), Vt.data_ptr(), Bn, N, M, lp, variant, 0, stream) == 0
+    assert lib.sdp_sparsemax_forward_value_f32(t.data_ptr(), A.data_ptr(), Vv.data_ptr(), Bn, N, M, lp, variant, 0, stream) == 0
+    assert lib.sdp_sparsemax_backward_f32(state.data_ptr(), Vt.data_ptr(), et.data_ptr(), E.data_ptr(), G.data_ptr(), Bn, N, M, lp, variant,
+                                          0, stream) == 0
+    assert lib.sdp_sparsemax_backward_f32(state.data_ptr(), Vt.data_ptr(), et.data_ptr(), E2.data_ptr(), None, Bn, N, M, lp, variant, 0,
+                                          stream) == 0
+    torch.cuda.synchronize()
+    for buf, n, off, what in ((sbuf, nstate, 0, "state"), (vbuf, Bn, offset, "Vt"), (wbuf, Bn, offset, "Vt of the value-only sweep"),
+                              (ebuf, size, offset, "E"), (gbuf, size, offset, "G"), (fbuf, size, offset, "E with G = NULL")):
+        _untouched(buf, n, off, (what, offset, dirty))
+    out = tuple(_bits(x.cpu().numpy()) for x in (Vt, E.view(Bn, N, M), G.view(Bn, N, M)))
+    assert np.array_equal(_bits(Vv.cpu().numpy()), out[0]) and np.array_equal(_bits(E2.view(Bn, N, M).cpu().numpy()), out[1])
+    for b, (n, m) in enumerate(lens if lens is not None else [(N, M)] * Bn):
+        mask = np.ones((N, M), bool)
+        mask[:n, :m] = False
+        assert not out[1][b][mask].any() and not out[2][b][mask].any(), (b, offset, dirty)      # +0, by bit pattern
+    return out
+
+
+@pytest.mark.parametrize("variant", [NW, SW], ids=["nw", "sw"])
+@pytest.mark.parametrize("with_lens", [True, False], ids=["lens", "full"])
+def test_what_lies_beside_the_matrix_takes_no_part_and_nothing_is_written_outside(with_lens, variant):
+    """theta and A at plane offsets of 0 .. 3 floats (the four-float loads and stores are `packed, aligned(4)` for this), once
+    among zeros and once among NaN, +-inf and +-1e30 -- in front, behind and in every pair's padding: the same bits of Vt, E and
+    G every time, and not a word written outside Vt, the state (exactly sdp_sparsemax_state_bytes long), E or G"""
+    th, a = _case("model", 130, 150)
+    lens = RAW_LENS if with_lens else None
+    rng = np.random.RandomState(77)
+    runs = [_raw_run(th, a, variant, lens, offset, dirty, rng) for offset in range(4) for dirty in (False, True)]
+    for k, run in enumerate(runs[1:], 1):
+        for x, y, what in zip(runs[0], run, ("Vt", "E", "G")):
+            assert np.array_equal(x, y), (what, "offset", k // 2, "dirty", k % 2, int((x != y).sum()))
+    want = ref.batch_wavefront(th, a, variant, lens)
+    _check(tuple(x.view(np.float32) for x in runs[0]), _scaled(want, ET), f"raw pointers {NAMES[variant]}")
+
+
+@pytest.mark.parametrize("variant", [NW, SW], ids=["nw", "sw"])
+def test_lengths_out_of_range_are_clamped(variant):
+    N, M = 130, 150
+    th, a = _case("unit", N, M, 4)
+    lens = np.asarray([(-3, 5), (5, -1), (N + 7, M + 9), (N, 0)], np.int32)
+    want = ref.batch_wavefront(th, a, variant, lens)          # (clamps as ref.batch does: tests/test_sparsemax.py)
+    full = ref.batch_wavefront(th[2:3], a[2:3], variant)
+    assert all(np.array_equal(want[k][2:3], full[k]) for k in want)
+    Vt, E, G = _run(th, a, variant, lens)
+    _check((Vt, E, G), want, f"lens out of range {NAMES[variant]}")
+    for b in (0, 1, 3):
+        assert _bits(Vt)[b] == 0 and not _bits(E[b]).any() and not _bits(G[b]).any(), b
+    assert Vt[2] != 0 and E[2, N - 1, M - 1] == 1.0
+    assert np.array_equal(_bits(_decoder(variant).score(_dev(th), _dev(a), _dev(lens)).cpu().numpy()), _bits(Vt))
+
+
+@pytest.mark.parametrize("variant", [NW, SW], ids=["nw", "sw"])
+def test_more_pairs_than_cus(variant):
+    th, a = _case("model", 8, 8, 300)
+    _check(_run(th, a, variant), ref.batch_wavefront(th, a, variant), f"B=300 {NAMES[variant]}")
