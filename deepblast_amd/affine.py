@@ -1,0 +1,119 @@
+"""The affine-gap soft local operator: a differentiable Smith-Waterman in which opening a gap and extending it are priced separately
+(include/sdp.h: sdp_affine_local_*) -- the Gotoh form every production aligner uses.
+
+    Vm[i,j] = theta[i,j] + log(1 + exp Vx[i-1,j-1] + exp Vm[i-1,j-1] + exp Vy[i-1,j-1])
+    Vx[i,j] = theta[i,j] + log(exp(X[i,j] + Vx[i-1,j]) + exp(O[i,j] + Vm[i-1,j]) + exp(O[i,j] + Vy[i-1,j]))
+    Vy[i,j] = theta[i,j] + log(exp(O[i,j] + Vx[i,j-1]) + exp(O[i,j] + Vm[i,j-1]) + exp(X[i,j] + Vy[i,j-1]))
+    Vt      = log(1 + sum over all cells of (exp Vx + exp Vm + exp Vy))
+
+O = gap_open, X = gap_extend.  exp(Vt) is 1 (the empty alignment) plus the sum over every local alignment of exp(score): theta on
+every cell of the path; on a cell entered through a gap step, X if the step before was the same kind of gap step and O otherwise.
+With gap_open == gap_extend == A this is SoftLocalDecoder (deepblast_amd.local) exactly.  There is no temperature parameter:
+scale theta, gap_open and gap_extend.
+
+Parity unpinned: the reference has no affine local aligner; the kernels are held to the float64 definition.
+
+Out of scope, none of it built: the second order (differentiating a gradient raises), sampling from the posterior, float64, the
+`distributed` wrappers, `search_scores` (its score(theta, A, lengths) protocol has two tensors, this operator three), and a hard
+(max-plus) affine kernel.
+"""
+import torch
+
+from . import _engine
+
+
+def _validate(theta, gap_open, gap_extend):
+    for name, t in (("theta", theta), ("gap_open", gap_open), ("gap_extend", gap_extend)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32 (the affine-gap soft local operator is fp32 only), got {t.dtype}")
+    if theta.dim() != 3 or gap_open.shape != theta.shape or gap_extend.shape != theta.shape:
+        raise ValueError(f"theta, gap_open and gap_extend must all be (B, N, M), got {tuple(theta.shape)}, {tuple(gap_open.shape)} "
+                         f"and {tuple(gap_extend.shape)}")
+
+
+def _oriented(theta, gap_open, gap_extend, lengths):
+    """_Decoder._oriented for three tensors: more columns than the sweeps take but not more rows -- the operator is symmetric under
+    transposition with x <-> y, one opening and one extension score for both directions -- so the problem is swept on the
+    TRANSPOSED tensors and autograd transposes every gradient back.  -> (theta, gap_open, gap_extend, lengths, transposed); both
+    sides above the limit: as they came (the engine raises ValueError)."""
+    cap = _engine.get_engine().max_cols()
+    if theta.shape[2] <= cap or theta.shape[1] > cap:
+        return theta, gap_open, gap_extend, lengths, False
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths)
+        lengths = torch.stack([lengths[:, 1], lengths[:, 0]], dim=1)
+    return theta.transpose(1, 2), gap_open.transpose(1, 2), gap_extend.transpose(1, 2), lengths, True
+
+
+class AffineLocalFunctionBackward(torch.autograd.Function):
+    """(E, GO, GX) of the mirror sweep.  Differentiable in nothing: this is the node at which a second differentiation stops --
+    what @once_differentiable does, with a message that names the reason."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, Et, state, Vt, lens, want_E, want_GO, want_GX):
+        # (the three inputs are here for the graph alone: the gradients depend on them, and a second differentiation must arrive below)
+        E, GO, GX = _engine.get_engine().affine_local_backward(state, Vt, Et, tuple(theta.shape), lens, want_GO=want_GO, want_GX=want_GX)
+        return (E if want_E else None), GO, GX
+
+    @staticmethod
+    def backward(ctx, ZE, ZGO, ZGX):
+        raise NotImplementedError("the affine-gap soft local operator is first order only: its second order (an adjoint pair for "
+                                  "sdp_affine_local_*) is not built")
+
+
+class AffineLocalFunction(torch.autograd.Function):
+    """Vt = affine_local(theta, gap_open, gap_extend); backward: theta.grad = E, gap_open.grad = GO, gap_extend.grad = GX, one mirror
+    sweep; GO and GX are computed only when their input needs a gradient.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, lens=None):
+        Vt, state = _engine.get_engine().affine_local_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lens)
+        ctx.save_for_backward(theta, gap_open, gap_extend, state, Vt)
+        ctx.lens = lens
+        return Vt
+
+    @staticmethod
+    def backward(ctx, Et):
+        theta, gap_open, gap_extend, state, Vt = ctx.saved_tensors
+        E, GO, GX = AffineLocalFunctionBackward.apply(theta, gap_open, gap_extend, Et, state, Vt, ctx.lens, *ctx.needs_input_grad[:3])
+        return E, GO, GX, None
+
+
+class AffineLocalDecoder(torch.nn.Module):
+    """Affine-gap local alignment scores, their gradients and the posterior alignment matrix, on a ROCm device in float32.
+
+    forward(theta, gap_open, gap_extend, lengths=None) -> Vt (B,), differentiable ONCE: theta.grad = E, gap_open.grad = GO,
+    gap_extend.grad = GX, all true gradients; GO and GX are computed only when their input needs a gradient.  Differentiating a
+    gradient raises NotImplementedError: the second order is not built.
+    decode(theta, gap_open, gap_extend, lengths=None) -> E (B, N, M) for Et = 1: E[b, i, j] is the posterior probability that cell
+    (i, j) lies on the alignment of pair b.  No autograd graph.
+    score(theta, gap_open, gap_extend, lengths=None) -> Vt (B,) through the value-only sweep: no state is allocated, no graph.
+    theta finite; gap_open and gap_extend finite or -inf (a forbidden opening or extension: the matching gradient is exactly 0
+    there).  lengths (B, 2): pair b is theta[b, :n_b, :m_b]; E, GO and GX are +0 outside it, and an empty pair has Vt = 0.
+    Problems wider than the column limit (2048) are swept transposed -- the operator is symmetric under transposition with x <-> y
+    -- and the results come back in the caller's coordinates; both sides above the limit raise ValueError.
+    Non-fp32 or non-tensor input: TypeError; a shape mismatch: ValueError.
+    Not built: the second order, sampling, float64, `distributed`, `search_scores` (a two-tensor protocol), a hard affine kernel."""
+
+    def forward(self, theta, gap_open, gap_extend, lengths=None):
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, _ = _oriented(theta, gap_open, gap_extend, lengths)
+        return AffineLocalFunction.apply(theta, gap_open, gap_extend, lengths)
+
+    def decode(self, theta, gap_open, gap_extend, lengths=None):
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, transposed = _oriented(theta, gap_open, gap_extend, lengths)
+        eng = _engine.get_engine()
+        with torch.no_grad():
+            Vt, state = eng.affine_local_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths)
+            E, _, _ = eng.affine_local_backward(state, Vt, torch.ones((), dtype=torch.float32, device=theta.device), tuple(theta.shape),
+                                                lengths, want_GO=False, want_GX=False)
+        return E.transpose(1, 2) if transposed else E
+
+    def score(self, theta, gap_open, gap_extend, lengths=None):
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, _ = _oriented(theta, gap_open, gap_extend, lengths)
+        with torch.no_grad():
+            return _engine.get_engine().affine_local_forward_value(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths)

@@ -16,6 +16,7 @@
 #include "sdp_soft_local.h"
 #include "sdp_soft_local_sample.h"
 #include "sdp_sparsemax.h"
+#include "sdp_affine_local.h"
 #include "sdp_kernels.h"
 
 namespace {
@@ -595,6 +596,25 @@ int raise_sparsemax_adjoint_limit(int device)
     return 0;
 }
 
+// the affine-gap soft local operator's three kernels keep three boundary rows per wave (sdp_affine_local::sweep_lds_bytes): up to
+// 160 KB, forward sweeps included
+int raise_affine_local_limit(int device)
+{
+    static thread_local unsigned long long raised = 0;
+    if (device < 64 && (raised >> device & 1ull)) return 0;
+    const struct { const void *f; const char *what; } ks[] = {
+        {(const void *)sdp_affine_local_fwd_kernel, "hipFuncSetAttribute(sdp_affine_local_fwd_kernel)"},
+        {(const void *)sdp_affine_local_val_kernel, "hipFuncSetAttribute(sdp_affine_local_val_kernel)"},
+        {(const void *)sdp_affine_local_bwd_kernel, "hipFuncSetAttribute(sdp_affine_local_bwd_kernel)"},
+    };
+    for (const auto &k : ks) {
+        const hipError_t e = hipFuncSetAttribute(k.f, hipFuncAttributeMaxDynamicSharedMemorySize, sdp_affine_local::LDS_BUDGET);
+        if (e != hipSuccess) return fail_hip(e, k.what);
+    }
+    if (device < 64) raised |= 1ull << device;
+    return 0;
+}
+
 // variant | SDP_REF_ROUNDING (sdp_ref.hip): one workgroup of 256 threads per pair, three rolling anti-diagonals of float64
 size_t ref_lds(int M) { return (size_t)3 * (M + 2) * sizeof(double); }
 size_t ref_state_bytes(int B, int N, int M) { return (size_t)B * N * M * 3 * sizeof(float); }
@@ -707,6 +727,10 @@ const char *sdp_kernel_name(int kernel_id)
     // its adjoint pair (csrc/sdp_sparsemax_adj.hip)
     case sdp_sparsemax::ID_ADJ_FWD: return "sdp_sparsemax_adj_fwd_kernel";
     case sdp_sparsemax::ID_ADJ_BWD: return "sdp_sparsemax_adj_bwd_kernel";
+    // the affine-gap soft local operator (csrc/sdp_affine_local.hip)
+    case sdp_affine_local::ID_FWD: return "sdp_affine_local_fwd_kernel";
+    case sdp_affine_local::ID_VAL: return "sdp_affine_local_val_kernel";
+    case sdp_affine_local::ID_BWD: return "sdp_affine_local_bwd_kernel";
     }
     return nullptr;
 }
@@ -727,7 +751,8 @@ int sdp_init(int device)
         if (int rc = raise_lds_limit(b, device)) return rc;
     if (int rc = raise_scores_limits(device)) return rc;
     if (int rc = raise_soft_local_adjoint_limit(device)) return rc;
-    return raise_sparsemax_adjoint_limit(device);
+    if (int rc = raise_sparsemax_adjoint_limit(device)) return rc;
+    return raise_affine_local_limit(device);
 }
 
 int sdp_device_status(int device, int32_t info[4])
@@ -1588,6 +1613,69 @@ int sdp_soft_local_sample_paths_f32(const void *state, const float *cdf, const f
     hipLaunchKernelGGL(sdp_soft_local_sample_kernel, dim3((unsigned)waves), dim3(sdp_soft_local_sample::LANES), 0, (hipStream_t)stream, g);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_sample_kernel");
+    return 0;
+}
+
+// ---- the affine-gap soft local operator (csrc/sdp_affine_local.hip): gap open and gap extend priced separately, first order ----
+// `flags` of the three entries: none is defined, any bit is refused
+static int affine_local_args(int B, int N, int M, int flags)
+{
+    if (int rc = check_shape(B, N, M, SDP_NW)) return rc;
+    if (flags != 0) return fail(SDP_E_VARIANT, "sdp_affine_local_*: this family defines no flags");
+    if ((size_t)B * (size_t)N * (size_t)M > ((size_t)1 << 31)) return fail(SDP_E_TOOBIG, "B*N*M exceeds 2^31 elements");
+    return 0;
+}
+
+size_t sdp_affine_local_state_bytes(int B, int N, int M)
+{
+    if (B <= 0 || N <= 0 || M <= 0 || M > sdp::MAX_COLS) return 0;
+    return (size_t)B * sdp_affine_local::pair_cells(N, M) * sdp_affine_local::CELL_BYTES;
+}
+
+static int affine_local_forward(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int B, int N,
+                                int M, const int32_t *lens, int flags, int device, void *stream, bool records)
+{
+    if (int rc = affine_local_args(B, N, M, flags)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = raise_affine_local_limit(device)) return rc;
+    const int W = sdp_affine_local::waves_for(N, M);
+    hipLaunchKernelGGL(records ? sdp_affine_local_fwd_kernel : sdp_affine_local_val_kernel, dim3(B), dim3(64 * W),
+                       sdp_affine_local::sweep_lds_bytes(W, M), (hipStream_t)stream, theta, gap_open, gap_extend,
+                       static_cast<float4 *>(state), Vt, lens, N, M, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, records ? "sdp_affine_local_fwd_kernel" : "sdp_affine_local_val_kernel");
+    return 0;
+}
+
+int sdp_affine_local_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int B, int N,
+                                 int M, const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!theta || !gap_open || !gap_extend || !state || !Vt) return fail(SDP_E_NULLPTR, "sdp_affine_local_forward_f32: null pointer");
+    return affine_local_forward(theta, gap_open, gap_extend, state, Vt, B, N, M, lens, flags, device, stream, true);
+}
+
+int sdp_affine_local_forward_value_f32(const float *theta, const float *gap_open, const float *gap_extend, float *Vt, int B, int N, int M,
+                                       const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!theta || !gap_open || !gap_extend || !Vt) return fail(SDP_E_NULLPTR, "sdp_affine_local_forward_value_f32: null pointer");
+    return affine_local_forward(theta, gap_open, gap_extend, nullptr, Vt, B, N, M, lens, flags, device, stream, false);
+}
+
+int sdp_affine_local_backward_f32(const void *state, const float *Vt, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
+                                  const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!state || !Vt || !Et || !E)
+        return fail(SDP_E_NULLPTR, "sdp_affine_local_backward_f32: null pointer (state, Vt, Et, E; GO and GX may be NULL)");
+    if (int rc = affine_local_args(B, N, M, flags)) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = raise_affine_local_limit(device)) return rc;
+    const int W = sdp_affine_local::waves_for(N, M);
+    hipLaunchKernelGGL(sdp_affine_local_bwd_kernel, dim3(B), dim3(64 * W), sdp_affine_local::sweep_lds_bytes(W, M), (hipStream_t)stream,
+                       static_cast<const float4 *>(state), Vt, Et, E, GO, GX, lens, N, M, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "sdp_affine_local_bwd_kernel");
     return 0;
 }
 

@@ -628,6 +628,49 @@ int sdp_sparsemax_adjoint_forward_f32(const void *state, const float *ZE, const 
 int sdp_sparsemax_adjoint_backward_f32(const void *state, const void *state_d, const float *Et, float *Ed, float *Gd, int B, int N, int M,
                                        const int32_t *lens, int variant, int device, void *stream);
 
+/* The AFFINE-GAP SOFT LOCAL operator (csrc/sdp_affine_local.hip): the soft local operator above with opening a gap
+ * and extending it priced separately -- the Gotoh form of Smith-Waterman, differentiable.  (Added after SDP_VERSION 106 without a
+ * version change: look the symbols up.)  With (n, m) = lens[b] clamped or (N, M), cells 1-based, theta, gap_open (O) and gap_extend
+ * (X) 0-based (B, N, M): a path starts at any cell, takes steps x (i-1,j)->(i,j), m (i-1,j-1)->(i,j) or y (i,j-1)->(i,j) and ends at
+ * any cell; its score is theta on every one of its cells, plus, on every cell entered through x or y, X[i,j] if the step before was
+ * the same kind of gap step and O[i,j] otherwise (the start cell, an m step and the OTHER gap kind all count as otherwise: an x run
+ * may follow a y run and pays an opening).  exp(Vt) = 1 + the sum over every such path of exp(score).  Three planes per cell, named
+ * by the step that entered the cell, x, m, y = 0, 1, 2; a plane value without a predecessor is -inf and its weights are 0:
+ *     Vm[i,j] = theta[i,j] + log(1 + exp Vx[i-1,j-1] + exp Vm[i-1,j-1] + exp Vy[i-1,j-1])
+ *     Vx[i,j] = theta[i,j] + log(exp(X[i,j] + Vx[i-1,j]) + exp(O[i,j] + Vm[i-1,j]) + exp(O[i,j] + Vy[i-1,j]))
+ *     Vy[i,j] = theta[i,j] + log(exp(O[i,j] + Vx[i,j-1]) + exp(O[i,j] + Vm[i,j-1]) + exp(X[i,j] + Vy[i,j-1]))
+ *     Vt      = log(1 + sum over cells of (exp Vx + exp Vm + exp Vy));      w_s = exp(V_s - Vt)
+ *     q[s<-s'][i,j] = the term of plane s' over the sum in the log of plane s      (plane m: restart weight 1 - sum of q[m<-.])
+ * The backward pass gives the TRUE gradients; Eb_s[i,j] is Et times the posterior mass of the paths that are in plane s at (i, j):
+ *     Eb_s[i,j] = Et w_s[i,j] + q[x<-s][i+1,j] Eb_x[i+1,j] + q[m<-s][i+1,j+1] Eb_m[i+1,j+1] + q[y<-s][i,j+1] Eb_y[i,j+1]
+ *     E  = Eb_x + Eb_m + Eb_y                                                  = Et dVt/dtheta
+ *     GX = Eb_x q[x<-x] + Eb_y q[y<-y]                                         = Et dVt/dX
+ *     GO = Eb_x (q[x<-m] + q[x<-y]) + Eb_y (q[y<-x] + q[y<-m])                 = Et dVt/dO
+ * With O == X == A this is the soft local operator: the same Vt and E, and GO + GX = G.  The operator is symmetric under
+ * transposition with x <-> y.  theta finite; O and X finite or -inf (a forbidden opening or extension: the matching gradient is
+ * exactly 0 there, and nothing is NaN when every gap is forbidden).  E, GO and GX are +0 by bit pattern outside the pair's [:n, :m]
+ * block (the backward kernel writes them: no extra launch); a pair with n < 1 or m < 1 has Vt = 0 and all gradients 0.  fp32 only.
+ * No floating-point atomics: two calls on the same inputs give the same bits, and sdp_affine_local_forward_value_f32 gives the bits
+ * of sdp_affine_local_forward_f32's Vt.  NOT built: the second order, sampling, float64, a hard (max-plus) affine kernel.
+ *   state    sdp_affine_local_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: 48 bytes per cell -- one record
+ *            {q[s<-x], q[s<-m], q[s<-y], V_s} per plane s -- in a private layout; written by sdp_affine_local_forward_f32, read by
+ *            sdp_affine_local_backward_f32 with the same B, N, M, lens (which needs neither theta, O nor X).  Only records of cells
+ *            inside a pair's block are written, and the backward pass uses no others.
+ *   Vt       (B,): written by the forward entries, READ by the backward entry (w needs it).
+ *   GO, GX   (B, N, M) or NULL, each on its own.
+ *   flags    this family defines none: any bit is refused (SDP_E_VARIANT).
+ * One workgroup per pair, rows unbounded, M <= sdp_max_cols().  Every kernel keeps three boundary rows per wave in LDS (up to 160 KB,
+ * eight waves up to M = 1642, six at the column limit), for which the entries raise the kernels' dynamic-LDS limit (sdp_init does it
+ * too, before a stream capture).  All arguments are checked before any device call, with the soft local family's codes and limits:
+ * SDP_E_NULLPTR, SDP_E_SHAPE, SDP_E_MAXCOLS, SDP_E_VARIANT, SDP_E_TOOBIG (N*M > 2^28, or B*N*M > 2^31 elements). */
+size_t sdp_affine_local_state_bytes(int B, int N, int M);
+int sdp_affine_local_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int B, int N,
+                                 int M, const int32_t *lens, int flags, int device, void *stream);
+int sdp_affine_local_forward_value_f32(const float *theta, const float *gap_open, const float *gap_extend, float *Vt, int B, int N, int M,
+                                       const int32_t *lens, int flags, int device, void *stream);
+int sdp_affine_local_backward_f32(const void *state, const float *Vt, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
+                                  const int32_t *lens, int flags, int device, void *stream);
+
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept
  * for callers who are short of memory, not of time; deepblast_amd.losses uses the unfused kernels by default.
