@@ -380,6 +380,80 @@ def special_case(kind, family="drift", n=130, m=150):
     raise ValueError(kind)
 
 
+# ---- the operator at its edges (tests/test_affine_local_gpu.py, modelled on tests/test_soft_local_gpu.py's at the same shapes) ----
+EDGE_SHAPE = (130, 150)
+RAW_LENS = ((127, 145), (130, 150), (65, 33))
+ET_ZERO = (1.0, -2.5, 0.0)
+TRANSPOSED_LENS = ((3, 2100), (2, 1999))
+MASKS = [(mask, on) for mask in ("-inf", "-1e30") for on in ("O", "X", "both")]
+MASKED_ROW = (1, 20)                   # (pair, row): every cell of it is forbidden, besides 30 % of all cells
+EDGES = ("clamp", "wide-lens", "raw-lens", "et-zero", "crowd", "transposed-lens") + tuple(f"mask{mask}-on-{on}" for (mask, on) in MASKS)
+
+
+def clamp_lens(N, M):
+    """lengths outside [0, N] x [0, M]: three empty pairs and one that runs past both ends"""
+    return ((-3, 5), (5, -1), (N + 7, M + 9), (N, 0))
+
+
+def wide_lens_shape():
+    """one launch on seven waves (nine strips) at the first width that no longer fits eight"""
+    return 513, widest_full() + 1
+
+
+def wide_lens():
+    """pairs of nine strips and of eight, a single column, a single row and an empty pair"""
+    N, M = wide_lens_shape()
+    return ((N, M), (449, M - 65), (N - 1, 1), (1, M), (0, 7))
+
+
+def masked(mask, on, family="drift"):
+    """-> (theta, O, X, cells of O that are masked, cells of X): `mask` on 30 % of the cells of O, of X or (independently) of both
+    and on one full row; the finite mask comes with theta = -1e9 on 10 % of the cells, as callers mask cells"""
+    th, o, x = (a.copy() for a in case_inputs(family, *EDGE_SHAPE))
+    rng = np.random.RandomState(16)
+    gone = {}
+    for key, a in (("O", o), ("X", x)):
+        g = rng.rand(*a.shape) < 0.3
+        g[MASKED_ROW[0], MASKED_ROW[1], :] = True
+        gone[key] = g if on in (key, "both") else np.zeros(a.shape, bool)
+        a[gone[key]] = -np.inf if mask == "-inf" else F(-1e30)
+    if mask == "-1e30":
+        th[rng.rand(*th.shape) < 0.1] = F(-1e9)
+    return th, o, x, gone["O"], gone["X"]
+
+
+@functools.lru_cache(None)
+def edge_case(name):
+    """-> (theta, O, X, lens, Et) of the edge test `name` (EDGES), read-only"""
+    N, M = EDGE_SHAPE
+    lens = et = None
+    if name == "clamp":
+        th, o, x = case_inputs("floor", N, M, 4)
+        lens = clamp_lens(N, M)
+    elif name == "wide-lens":
+        th, o, x = case_inputs("islands", *wide_lens_shape(), len(wide_lens()))
+        lens = wide_lens()
+    elif name == "raw-lens":
+        th, o, x = case_inputs("drift", N, M)
+        lens = RAW_LENS
+    elif name == "et-zero":
+        th, o, x = case_inputs("drift", N, M)
+        et = np.asarray(ET_ZERO, F)
+    elif name == "crowd":
+        th, o, x = case_inputs("model", 8, 8, 300)
+    elif name == "transposed-lens":
+        th, o, x = case_inputs("drift", 3, 2100, 2)
+        lens = TRANSPOSED_LENS
+    else:
+        mask, on = MASKS[EDGES.index(name) - (len(EDGES) - len(MASKS))]
+        th, o, x, _, _ = masked(mask, on)
+    out = (th, o, x, None if lens is None else np.asarray(lens, np.int32), et)
+    for a in out:
+        if a is not None:
+            a.setflags(write=False)
+    return out
+
+
 def all_gpu_cases():
     """every input set tests/test_affine_local_gpu.py runs: [(id, thunk -> (theta, O, X, lens, Et))] -- the admission rule of
     tests/test_affine_local.py goes over this list"""
@@ -388,7 +462,8 @@ def all_gpu_cases():
     special = [(f"{kind}-{f}-{n}x{m}", functools.partial(special_case, kind, f, n, m))
                for kind, cases in (("forbidden", FORBIDDEN), ("equal", EQUAL), ("et", [("drift", 65, 33)]),
                                  ("closed", [("drift", 65, 33)])) for (f, n, m) in cases]
-    return plain + special + [("lens-drift-130x150", functools.partial(special_case, "lens"))]
+    return (plain + special + [("lens-drift-130x150", functools.partial(special_case, "lens"))]
+            + [(f"edge-{name}", functools.partial(edge_case, name)) for name in EDGES])
 
 
 def errors(got, want):

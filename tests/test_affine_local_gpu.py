@@ -2,7 +2,10 @@
 (deepblast_amd/affine.py) against the float64 definition (tests/affine_local_ref.py, the wavefront form, held to the loops by
 tests/test_affine_local.py) on the same fp32 inputs, under tests/parity.py's rules: rel_err(Vt) <= TOL, abs_err <= TOL on E, GO and
 GX, TOL = 1e-4.  Every case is admitted by tests/test_affine_local.py: plain fp32 arithmetic alone stays within a quarter of the
-bound (DESIGN.md 3.22 has the figures and names the cases left out).  Parity is unpinned: there is no reference implementation."""
+bound (DESIGN.md 3.22 has the figures and names the cases left out).  Parity is unpinned: there is no reference implementation.
+The edge tests at the end are the soft local family's (tests/test_soft_local_gpu.py), at the same shapes: lengths out of range,
+lengths at full width and on the transposed route, the raw C entries with guarded buffers, Et = 0, 300 pairs, both masks on
+either gap plane.  tests/test_family_fuzz_gpu.py draws what lies between the fixed shapes."""
 import functools
 
 import numpy as np
@@ -204,3 +207,190 @@ def test_gradients_only_where_asked_and_the_second_order_refusal():
                                           "GX": gx.detach().cpu().numpy()}, want)["GX"] <= TOL
     with pytest.raises(NotImplementedError, match="second order.*is not built"):
         gt.sum().backward()
+
+
+# ---- the operator at its edges (the input sets: affine_local_ref.edge_case, admitted by tests/test_affine_local.py) ----
+PAD = 4096                                      # floats in front of and behind every tensor
+PATTERN = 0x5A5AC3C3                            # what every output buffer holds before a call (as a float: 1.5e16)
+POISON = np.array([np.nan, np.inf, -np.inf, 1e30, -1e30], np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def _edge(name):
+    th, o, x, lens, et = ref.edge_case(name)
+    want = ref.batch_wavefront(th, o, x, lens, et)
+    for v in want.values():
+        v.setflags(write=False)
+    return th, o, x, lens, et, want
+
+
+def _zero_outside(got, lens, shape):
+    for b, (n, m) in enumerate(lens):
+        mask = np.ones(shape, bool)
+        mask[:max(n, 0), :max(m, 0)] = False
+        for k in KEYS:
+            assert not _bits(got[k][b])[mask].any(), (k, b, n, m)     # +0, by bit pattern
+
+
+def test_lengths_out_of_range_are_clamped():
+    """the kernels' min(max(., 0), N): a negative length is an empty pair, one past the tensor the whole side"""
+    N, M = ref.EDGE_SHAPE
+    th, o, x, lens, _, want = _edge("clamp")
+    assert lens.tolist() == [[-3, 5], [5, -1], [N + 7, M + 9], [N, 0]]
+    full = ref.batch_wavefront(th[2:3], o[2:3], x[2:3])
+    assert all(np.array_equal(want[k][2:3], full[k]) for k in want) and want["Vt"][2] > 0
+    got = _run(th, o, x, lens)
+    _check(got, want, "lens out of range")
+    for b in (0, 1, 3):
+        assert _bits(got["Vt"])[b] == 0 and not any(_bits(got[k][b]).any() for k in KEYS), b
+    one = _run(th[2:3], o[2:3], x[2:3])          # the over-long pair is the full run, bit for bit
+    for k in got:
+        assert np.array_equal(_bits(got[k][2:3]), _bits(one[k])), k
+    _value_bits(th, o, x, got, lens)
+
+
+def test_full_width_lengths():
+    """pairs of nine strips and of eight, a single column, a single row and an empty pair in one seven-wave launch"""
+    N, M = ref.wide_lens_shape()
+    assert (N, ref.strips(N), ref.waves(N, M), ref.waves(N, M - 1)) == (513, 9, 7, 8)
+    th, o, x, lens, _, want = _edge("wide-lens")
+    assert [ref.strips(n) for n, _ in lens] == [9, 8, 8, 1, 0] and lens[2, 1] == 1 and lens[3, 0] == 1
+    got = _run(th, o, x, lens)
+    for b, (n, m) in enumerate(lens):
+        _check({k: v[b:b + 1] for k, v in got.items()}, {k: v[b:b + 1] for k, v in want.items()}, f"wide lens {n}x{m}")
+    _zero_outside(got, lens, (N, M))
+    assert _bits(got["Vt"])[-1] == 0 and float(want["E"][1].max()) > 0.05 and float(want["GO"][1].max()) > 0.01 < float(want["GX"][1].max())
+    _value_bits(th, o, x, got, lens)
+
+
+def _guarded(n, offset=0):
+    """-> (buffer, view): `n` floats at PAD + offset of a buffer filled with PATTERN"""
+    buf = torch.full((n + 2 * PAD + 4,), PATTERN, dtype=torch.int32, device=DEV).view(torch.float32)
+    return buf, buf[PAD + offset:PAD + offset + n]
+
+
+def _untouched(buf, n, offset, what):
+    words = buf.view(torch.int32)
+    assert bool((words[:PAD + offset] == PATTERN).all()) and bool((words[PAD + offset + n:] == PATTERN).all()), what
+
+
+def _raw_run(th, o, x, lens, offset, dirty, rng):
+    """the three C entries with raw pointers, the backward four times (GO and GX, GO = NULL, GX = NULL, both NULL): theta, O and X
+    at `offset` floats inside buffers of zeros (dirty: of POISON), every pair's padding beyond `lens` likewise; Vt, the state, E, GO
+    and GX views into buffers of PATTERN -> bits of (Vt, E, GO, GX)"""
+    lib = _engine().lib
+    B, N, M = th.shape
+    size = B * N * M
+    stream = torch.cuda.current_stream().cuda_stream
+    ins = []
+    for src in (th, o, x):
+        fill = POISON[rng.randint(0, 5, size + 2 * PAD + 4)] if dirty else np.zeros(size + 2 * PAD + 4, np.float32)
+        a = src.copy()
+        if lens is not None:
+            for b, (n, m) in enumerate(lens):
+                pad = POISON[rng.randint(0, 5, (N, M))] if dirty else np.zeros((N, M), np.float32)
+                a[b, n:, :] = pad[n:, :]
+                a[b, :, m:] = pad[:, m:]
+        fill[PAD + offset:PAD + offset + size] = a.reshape(-1)
+        ins.append(torch.from_numpy(fill).to(DEV))
+    t, O, X = (buf[PAD + offset:PAD + offset + size] for buf in ins)
+    assert t.data_ptr() % 16 == 4 * offset and X.data_ptr() % 16 == 4 * offset
+    ln = None if lens is None else _dev(np.asarray(lens, np.int32))
+    lp = None if ln is None else ln.data_ptr()
+    nstate = lib.sdp_affine_local_state_bytes(B, N, M) // 4
+    assert nstate == B * ref.strips(N) * ref.chunks(M) * 32 * 64 * 12
+    (sbuf, state), (vbuf, Vt), (wbuf, Vv) = _guarded(nstate), _guarded(B, offset), _guarded(B, offset)
+    planes = {name: _guarded(size, offset) for name in ("E", "GO", "GX", "E no GO", "GX no GO", "E no GX", "GO no GX", "E alone")}
+    p = {name: view.data_ptr() for name, (_, view) in planes.items()}
+    et = torch.ones(B, device=DEV)
+    assert lib.sdp_affine_local_forward_f32(t.data_ptr(), O.data_ptr(), X.data_ptr(), state.data_ptr(), Vt.data_ptr(), B, N, M, lp, 0, 0,
+                                            stream) == 0
+    assert lib.sdp_affine_local_forward_value_f32(t.data_ptr(), O.data_ptr(), X.data_ptr(), Vv.data_ptr(), B, N, M, lp, 0, 0, stream) == 0
+    for E, GO, GX in ((p["E"], p["GO"], p["GX"]), (p["E no GO"], None, p["GX no GO"]), (p["E no GX"], p["GO no GX"], None),
+                      (p["E alone"], None, None)):
+        assert lib.sdp_affine_local_backward_f32(state.data_ptr(), Vt.data_ptr(), et.data_ptr(), E, GO, GX, B, N, M, lp, 0, 0, stream) == 0
+    torch.cuda.synchronize()
+    for buf, n, off, what in [(sbuf, nstate, 0, "state"), (vbuf, B, offset, "Vt"), (wbuf, B, offset, "Vt of the value-only sweep")] + [
+            (buf, size, offset, name) for name, (buf, _) in planes.items()]:
+        _untouched(buf, n, off, (what, offset, dirty))
+    bits = {name: _bits(view.view(B, N, M).cpu().numpy()) for name, (_, view) in planes.items()}
+    out = (_bits(Vt.cpu().numpy()), bits["E"], bits["GO"], bits["GX"])
+    assert np.array_equal(_bits(Vv.cpu().numpy()), out[0])
+    for name, full in (("E no GO", "E"), ("GX no GO", "GX"), ("E no GX", "E"), ("GO no GX", "GO"), ("E alone", "E")):
+        assert np.array_equal(bits[name], bits[full]), (name, offset, dirty)
+    _zero_outside(dict(zip(KEYS, out[1:])), lens if lens is not None else [(N, M)] * B, (N, M))
+    return out
+
+
+@pytest.mark.parametrize("with_lens", [True, False], ids=["lens", "full"])
+def test_what_lies_beside_the_matrices_takes_no_part_and_nothing_is_written_outside(with_lens):
+    """theta, O and X at plane offsets of 0 .. 3 floats (the four-float loads and stores are `packed, aligned(4)` for this), once
+    among zeros and once among NaN, +-inf and +-1e30 -- in front, behind and in every pair's padding: the same bits of Vt, E, GO and
+    GX every time, with GO, GX or both NULL too, and not a word written outside Vt, the state (exactly sdp_affine_local_state_bytes
+    long), E, GO or GX"""
+    if with_lens:
+        th, o, x, lens, _, want = _edge("raw-lens")
+        lens = [tuple(r) for r in lens.tolist()]
+    else:
+        (th, o, x), lens, want = ref.case_inputs("drift", *ref.EDGE_SHAPE), None, ref.case_reference("drift", *ref.EDGE_SHAPE)
+    rng = np.random.RandomState(77)
+    runs = [_raw_run(th, o, x, lens, offset, dirty, rng) for offset in range(4) for dirty in (False, True)]
+    for k, run in enumerate(runs[1:], 1):
+        for a, b, what in zip(runs[0], run, ("Vt",) + KEYS):
+            assert np.array_equal(a, b), (what, "offset", k // 2, "dirty", k % 2, int((a != b).sum()))
+    _check(dict(zip(("Vt",) + KEYS, (a.view(np.float32) for a in runs[0]))), want, "raw pointers")
+
+
+def test_et_of_either_sign_and_zero():
+    eng = _engine()
+    th, o, x, _, et, want = _edge("et-zero")
+    one = ref.case_reference("drift", *ref.EDGE_SHAPE)
+    assert et.tolist() == [1.0, -2.5, 0.0] and want["E"][1].min() < -0.05
+    assert all(np.abs(want[k] - one[k] * et[:, None, None].astype(np.float64)).max() <= 1e-12 for k in KEYS)
+    t, O, X = _dev(th), _dev(o), _dev(x)
+    Vt, state = eng.affine_local_forward(t, O, X)
+    E, GO, GX = eng.affine_local_backward(state, Vt, _dev(et), th.shape)
+    torch.cuda.synchronize()
+    got = {"Vt": Vt.cpu().numpy(), "E": E.cpu().numpy(), "GO": GO.cpu().numpy(), "GX": GX.cpu().numpy()}
+    _check(got, want, "Et")
+    assert not any(_bits(got[k][2]).any() for k in KEYS)          # Et = 0: all-zero planes
+
+
+def test_more_pairs_than_cus():
+    th, o, x, _, _, want = _edge("crowd")
+    assert th.shape == (300, 8, 8)
+    got = _run(th, o, x)
+    _check(got, want, "B=300")
+    _value_bits(th, o, x, got)
+
+
+def test_lengths_on_the_transposed_route():
+    """2 x 3 x 2100 is swept as 2100 x 3 with the lengths swapped (and O, X as they are: the operator is symmetric under
+    transposition with x <-> y); everything comes back in the caller's coordinates"""
+    th, o, x, lens, _, want = _edge("transposed-lens")
+    assert th.shape == (2, 3, 2100) and th.shape[2] > _engine().max_cols() and lens.tolist() == [[3, 2100], [2, 1999]]
+    got = _run(th, o, x, lens)
+    assert all(got[k].shape == (2, 3, 2100) for k in KEYS)
+    _check(got, want, "transposed lens")
+    _zero_outside(got, lens, (3, 2100))
+    D = _decoder().decode(_dev(th), _dev(o), _dev(x), _dev(lens))
+    assert tuple(D.shape) == (2, 3, 2100) and np.array_equal(_bits(D.cpu().numpy()), _bits(got["E"]))
+    _value_bits(th, o, x, got, lens)
+
+
+@pytest.mark.parametrize("mask,on", ref.MASKS, ids=[f"{mask}-on-{on}" for (mask, on) in ref.MASKS])
+def test_masks(mask, on):
+    """-inf on O, on X or on both is a forbidden opening / extension (include/sdp.h): the matching gradient is exactly +0 there, for
+    one whole row too, and nothing is NaN; the large finite negatives callers use as masks behave the same, with theta = -1e9 on a
+    tenth of the cells beside them (theta = -inf stays outside the contract)"""
+    th, o, x, _, _, want = _edge(f"mask{mask}-on-{on}")
+    _, _, _, gone_o, gone_x = ref.masked(mask, on)
+    b, row = ref.MASKED_ROW
+    assert gone_o.any() == (on != "X") and gone_x.any() == (on != "O") and (on != "both" or (gone_o != gone_x).any())
+    assert (on == "X" or gone_o[b, row].all()) and (on == "O" or gone_x[b, row].all())
+    assert all(np.isfinite(v).all() for v in want.values()) and not want["GO"][gone_o].any() and not want["GX"][gone_x].any()
+    assert want["GO"].max() > 0.01 and want["GX"].max() > 0.01
+    got = _run(th, o, x)
+    _check(got, want, f"mask {mask} on {on}")
+    assert not _bits(got["GO"])[gone_o].any() and not _bits(got["GX"])[gone_x].any()          # +0, by bit pattern
+    _value_bits(th, o, x, got)

@@ -1,7 +1,8 @@
 """GPU: the seeded shape fuzz of tests/family_fuzz.py through the engine, one test per kernel family on the strip schedule (and per
 variant where the family has one): the hard and hard local sweeps and walks (csrc/sdp_hard.hip) bit for bit against hard_ref.batch
-and hard_local_ref.batch; soft local and sparsemax, first order and adjoint pair (csrc/sdp_soft_local*.hip, csrc/sdp_sparsemax*.hip)
-under tests/parity.py's rules against the float64 definition, where the admission rule lets the case in.  Every float input is a
+and hard_local_ref.batch; soft local and sparsemax, first order and adjoint pair (csrc/sdp_soft_local*.hip, csrc/sdp_sparsemax*.hip),
+and the affine-gap soft local operator (csrc/sdp_affine_local.hip: three inputs, masks on either gap plane, backward calls without GO
+or GX) under tests/parity.py's rules against the float64 definition, where the admission rule lets the case in.  Every float input is a
 view at a plane offset of 0 .. 3 floats inside a buffer of NaN, +-inf and +-1e30, with the same poison in every pair's padding;
 the value-only sweep must return the stateful sweep's Vt bit for bit.  tests/test_family_fuzz.py holds the case lists to what they
 are there to reach, without a GPU.
@@ -61,6 +62,13 @@ def _run(family, c):
         Vv, ends_v = eng.hard_local_forward_value(t, A, v, ln)
         E, states, counts = eng.hard_local_walk(P, ends, shape, v, ln, Et=et, E_out=E, states_out=states)
         return _np(Vt=Vt, Vv=Vv, ends=ends, ends_v=ends_v, E=E, states=states, counts=counts)
+    if family == ff.AFFINE:
+        X = _placed(c, "X")
+        Vt, state = eng.affine_local_forward(t, A, X, ln)
+        Vv = eng.affine_local_forward_value(t, A, X, ln)
+        E, GO, GX = eng.affine_local_backward(state, Vt, et, shape, ln, want_GO=c["want_GO"], want_GX=c["want_GX"])
+        assert (GO is None) == (not c["want_GO"]) and (GX is None) == (not c["want_GX"])
+        return _np(Vt=Vt, Vv=Vv, E=E, **{k: v for k, v in (("GO", GO), ("GX", GX)) if v is not None})
     if family.startswith("soft_local"):
         Vt, state = eng.soft_local_forward(t, A, ln)
         Vv = eng.soft_local_forward_value(t, A, ln)
@@ -80,12 +88,12 @@ def _run(family, c):
     return _np(Vt=Vt, Vv=Vv, Vtd=Vtd, Ed=Ed, Gd=Gd)
 
 
-def _fuzz(family, variant=None):
-    name = family + {None: "", ff.NW: " nw", ff.SW: " sw"}[variant]
+def _fuzz(family, variant=None, part=None):
+    name = family + {None: "", ff.NW: " nw", ff.SW: " sw"}[variant] + ("" if part is None else " part %d of %d" % (part[0] + 1, part[1]))
     print(f"\n[family fuzz] {family} seed {ff.SEED} (override with SDP_FAMILY_FUZZ_SEED), {ff.count(family)} cases of all variants")
     t0 = time.time()
     worst, compared, left_out = {}, 0, 0
-    for c in ff.cases(family, variant=variant):
+    for c in ff.cases(family, variant=variant, part=part):
         want = ff.reference(family, c)
         if family in ff.SOFT and not ff.admitted(family, c, want)[0]:
             left_out += 1
@@ -130,3 +138,10 @@ def test_sparsemax(variant):
 @BOTH
 def test_sparsemax_adjoint(variant):
     _fuzz("sparsemax_adjoint", variant)
+
+
+@pytest.mark.parametrize("part", ff.parts(ff.AFFINE), ids=lambda p: "part%d" % p[0])
+def test_affine_local(part):
+    """the forward sweep, the value-only sweep, the backward sweep with and without GO and GX; the list in two runs of consecutive
+    cases (its float64 and fp32 references take several times the soft local family's), each held to the cap"""
+    _fuzz(ff.AFFINE, part=part)
