@@ -9,8 +9,8 @@
 //     E = Eb_x + Eb_m + Eb_y;  GX = Eb_x q[x<-x] + Eb_y q[y<-y];  GO = Eb_x (q[x<-m] + q[x<-y]) + Eb_y (q[y<-x] + q[y<-m])
 //
 // a V outside the table is -inf, and so is a plane without a predecessor (x in row 1, y in column 1, both where every gap is
-// forbidden): its weights are 0.  The schedule is that of csrc/sdp_soft_local.hip, repeated here and not shared (those kernels
-// compile to what they compiled to before).  Three kernels:
+// forbidden): its weights are 0.  The schedule is the strip schedule of csrc/sdp_soft_local.hip: its lane moves,
+// stores and lse_join are shared, csrc/sdp_strip_device.h; the sweep loops are this file's own.  Three kernels:
 //
 //   forward   one workgroup per pair, one wave per strip of 64 rows (lane = row), swept along the anti-diagonals: at step s lane l
 //             is at column s - l, the three V[i-1,j] arrive from lane l - 1 by DPP, the three V[i-1,j-1] are what arrived one step
@@ -39,11 +39,12 @@
 #include <stdint.h>
 
 #include "sdp_affine_local.h"
-#include "sdp_soft_local_device.h"
+#include "sdp_strip_device.h"
 
 namespace {
 
 using namespace sdp_affine_local;
+static_assert(STRIP == sdp_strip::STRIP && CHUNK == sdp_strip::CHUNK, "csrc/sdp_affine_local.h and csrc/sdp_strip_device.h disagree");
 
 // the inputs lane `lane` of strip `s` needs in half `h` of chunk `c`: columns 32 c + 16 h - lane .. + 15 of row 64 s + lane; 0
 // where the cell does not exist (the value is then never used)
@@ -72,16 +73,6 @@ __device__ __forceinline__ void load_inputs(const float *theta, const float *O, 
             ge[t] = ok ? X[at + col] : 0.f;
         }
     }
-}
-
-// (max, sum) of a log-sum-exp joined with another: sum exp = s exp(m); an empty one is (-inf, 0).  Symmetric in its arguments
-// bit for bit, so a butterfly leaves every lane with the same pair.
-__device__ __forceinline__ void lse_join(float &m0, float &s0, float m1, float s1)
-{
-    const float mx = fmaxf(m0, m1);
-    const float e0 = m0 == mx ? 1.f : expf(m0 - mx), e1 = m1 == mx ? 1.f : expf(m1 - mx);
-    s0 = s0 * e0 + s1 * e1;
-    m0 = mx;
 }
 
 // one gap plane of a cell: the three candidates c0, c1, c2 (each finite or -inf) -> V - theta = log sum exp c, and the weights.
@@ -244,25 +235,6 @@ __device__ __forceinline__ void load_group(const float4 *state, size_t pair, int
         for (int p = 0; p < PLANES; ++p) q[t][p] = src[((size_t)t * PLANES + p) * STRIP];
 }
 
-// 4 consecutive cells of row `row` from column col0 on; only cells of the pair's block are written
-__device__ __forceinline__ void store_group(float *out, size_t plane, int M, int n, int m, int row, int col0, const float (&e)[GROUP])
-{
-    if (row >= n) return;
-    const size_t at = plane + (size_t)row * M;
-    if (col0 >= 0 && col0 + GROUP <= m) {
-        F4 x;
-#pragma unroll
-        for (int k = 0; k < GROUP; ++k) x.v[k] = e[k];
-        *reinterpret_cast<F4 *>(out + at + col0) = x;
-    } else {
-#pragma unroll
-        for (int t = 0; t < GROUP; ++t) {
-            const int col = col0 + t;
-            if (col >= 0 && col < m) out[at + col] = e[t];
-        }
-    }
-}
-
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(512) sdp_affine_local_fwd_kernel(const float *theta, const float *O, const float *X, float4 *state,
@@ -373,9 +345,9 @@ extern "C" __global__ void __launch_bounds__(512) sdp_affine_local_bwd_kernel(co
                     // what the top row pushes up enters at lane 0 and moves one lane up per step
                     ox = from_upper_lane(sendx, ox), om = from_upper_lane(sendm, om), oy = from_upper_lane(sendy, oy);
                 }
-                store_group(E, plane, M, n, m, row, colb + g * GROUP, e);
-                if (GO) store_group(GO, plane, M, n, m, row, colb + g * GROUP, go);
-                if (GX) store_group(GX, plane, M, n, m, row, colb + g * GROUP, gx);
+                store_run(E, plane, M, n, m, row, colb + g * GROUP, e);
+                if (GO) store_run(GO, plane, M, n, m, row, colb + g * GROUP, go);
+                if (GX) store_run(GX, plane, M, n, m, row, colb + g * GROUP, gx);
 #pragma unroll
                 for (int tt = 0; tt < GROUP; ++tt)
 #pragma unroll

@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 
 #include "sdp_gap.h"
@@ -394,15 +395,23 @@ inline bool routes_thin(bool exact, int N, int M, const int32_t *lens)
     return lens != nullptr && !exact && (N > sdp::THIN_HI || M > sdp::THIN_HI);
 }
 
+// SDP_WAVES(w) cut out of `variant`: returns w, 0 where the caller gave none
+int take_waves(int &variant)
+{
+    const int w = (variant >> 12) & 0xf;
+    variant &= ~(0xf << 12);
+    return w;
+}
+
 VariantBits split_variant(int variant)
 {
     VariantBits v;
     v.exact = (variant & SDP_EXACT_STATE) != 0;
     v.et_bcast = (variant & SDP_ET_BROADCAST) != 0;
-    v.waves = (variant >> 12) & 0xf;
+    v.waves = take_waves(variant);
     v.ref = (variant & SDP_REF_ROUNDING) != 0;
     v.flags = ((variant & SDP_NO_ZERO_SKIP) ? 1 : 0) | ((variant & SDP_NO_FILL) ? 2 : 0);
-    v.variant = variant & ~(SDP_EXACT_STATE | SDP_ET_BROADCAST | SDP_REF_ROUNDING | SDP_NO_ZERO_SKIP | SDP_NO_FILL | (0xf << 12));
+    v.variant = variant & ~(SDP_EXACT_STATE | SDP_ET_BROADCAST | SDP_REF_ROUNDING | SDP_NO_ZERO_SKIP | SDP_NO_FILL);
     return v;
 }
 
@@ -571,29 +580,38 @@ int raise_scores_limits(int device)
     return 0;
 }
 
+// the same for strip-schedule kernels whose ring outgrows the 64 KB a kernel gets unasked: `bytes` for every kernel of `ks`, once
+// per (thread, device) of the family that owns the mask `raised` -- by sdp_init, or lazily by the first call
+struct LimitKernel {
+    const void *f;
+    const char *what;
+};
+int raise_strip_limits(unsigned long long &raised, int device, std::initializer_list<LimitKernel> ks, int bytes)
+{
+    if (device < 64 && (raised >> device & 1ull)) return 0;
+    for (const LimitKernel &k : ks) {
+        const hipError_t e = hipFuncSetAttribute(k.f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return fail_hip(e, k.what);
+    }
+    if (device < 64) raised |= 1ull << device;
+    return 0;
+}
+
 // the soft local operator's adjoint backward sweep keeps two boundary rows per wave (sdp_soft_local::adjoint_lds_bytes): up to
-// 2 x 64 KB, so its limit is raised like the ones above -- by sdp_init, or lazily by the first call
+// 2 x 64 KB
 int raise_soft_local_adjoint_limit(int device)
 {
     static thread_local unsigned long long raised = 0;
-    if (device < 64 && (raised >> device & 1ull)) return 0;
-    const hipError_t e = hipFuncSetAttribute((const void *)sdp_soft_local_adj_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             160 * 1024);
-    if (e != hipSuccess) return fail_hip(e, "hipFuncSetAttribute(sdp_soft_local_adj_bwd_kernel)");
-    if (device < 64) raised |= 1ull << device;
-    return 0;
+    return raise_strip_limits(raised, device, {{(const void *)sdp_soft_local_adj_bwd_kernel, "hipFuncSetAttribute(sdp_soft_local_adj_bwd_kernel)"}},
+                              160 * 1024);
 }
 
 // the same for the sparsemax operator's adjoint backward sweep (sdp_sparsemax::adjoint_lds_bytes)
 int raise_sparsemax_adjoint_limit(int device)
 {
     static thread_local unsigned long long raised = 0;
-    if (device < 64 && (raised >> device & 1ull)) return 0;
-    const hipError_t e = hipFuncSetAttribute((const void *)sdp_sparsemax_adj_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             160 * 1024);
-    if (e != hipSuccess) return fail_hip(e, "hipFuncSetAttribute(sdp_sparsemax_adj_bwd_kernel)");
-    if (device < 64) raised |= 1ull << device;
-    return 0;
+    return raise_strip_limits(raised, device, {{(const void *)sdp_sparsemax_adj_bwd_kernel, "hipFuncSetAttribute(sdp_sparsemax_adj_bwd_kernel)"}},
+                              160 * 1024);
 }
 
 // the affine-gap soft local operator's three kernels keep three boundary rows per wave (sdp_affine_local::sweep_lds_bytes): up to
@@ -601,18 +619,48 @@ int raise_sparsemax_adjoint_limit(int device)
 int raise_affine_local_limit(int device)
 {
     static thread_local unsigned long long raised = 0;
-    if (device < 64 && (raised >> device & 1ull)) return 0;
-    const struct { const void *f; const char *what; } ks[] = {
-        {(const void *)sdp_affine_local_fwd_kernel, "hipFuncSetAttribute(sdp_affine_local_fwd_kernel)"},
-        {(const void *)sdp_affine_local_val_kernel, "hipFuncSetAttribute(sdp_affine_local_val_kernel)"},
-        {(const void *)sdp_affine_local_bwd_kernel, "hipFuncSetAttribute(sdp_affine_local_bwd_kernel)"},
-    };
-    for (const auto &k : ks) {
-        const hipError_t e = hipFuncSetAttribute(k.f, hipFuncAttributeMaxDynamicSharedMemorySize, sdp_affine_local::LDS_BUDGET);
-        if (e != hipSuccess) return fail_hip(e, k.what);
+    return raise_strip_limits(raised, device,
+                              {{(const void *)sdp_affine_local_fwd_kernel, "hipFuncSetAttribute(sdp_affine_local_fwd_kernel)"},
+                               {(const void *)sdp_affine_local_val_kernel, "hipFuncSetAttribute(sdp_affine_local_val_kernel)"},
+                               {(const void *)sdp_affine_local_bwd_kernel, "hipFuncSetAttribute(sdp_affine_local_bwd_kernel)"}},
+                              sdp_affine_local::LDS_BUDGET);
+}
+
+// ---- what the entries of the strip-schedule families share ----
+// waves of a workgroup: one per strip in flight, lowered to `forced` if 0 < forced, then until the family's ring fits its budget
+int strip_waves(int strips, int max_waves, int forced, int M, size_t (*lds_bytes)(int, int), int budget)
+{
+    int w = strips < max_waves ? strips : max_waves;
+    if (forced > 0 && forced < w) w = forced;
+    while (w > 1 && lds_bytes(w, M) > (size_t)budget) --w;
+    return w;
+}
+
+// the checks of a family whose entries take `flags` and define none: any bit is refused
+int flagless_args(const char *family, int B, int N, int M, int flags)
+{
+    if (int rc = check_shape(B, N, M, SDP_NW)) return rc;
+    if (flags != 0) {
+        snprintf(g_err, sizeof(g_err), "%s_*: this family defines no flags", family);
+        return SDP_E_VARIANT;
     }
-    if (device < 64) raised |= 1ull << device;
+    if ((size_t)B * (size_t)N * (size_t)M > ((size_t)1 << 31)) return fail(SDP_E_TOOBIG, "B*N*M exceeds 2^31 elements");
     return 0;
+}
+
+int use_device(int device)
+{
+    const hipError_t e = hipSetDevice(device);
+    return e == hipSuccess ? 0 : fail_hip(e, "hipSetDevice");
+}
+
+// one launch of `grid` workgroups of W waves with `lds` bytes of dynamic LDS; `name` is what a failure reports
+template <typename Kernel, typename... Args>
+int strip_launch(Kernel kernel, const char *name, unsigned grid, int W, size_t lds, void *stream, Args... args)
+{
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * W), lds, (hipStream_t)stream, args...);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail_hip(e, name);
 }
 
 // variant | SDP_REF_ROUNDING (sdp_ref.hip): one workgroup of 256 threads per pair, three rolling anti-diagonals of float64
@@ -1347,8 +1395,8 @@ int sdp_selftest(int device)
 static int hard_variant(int variant, int B, int N, int M, bool &ymx, int &waves, int &lo)
 {
     ymx = (variant & SDP_HARD_TIES_YMX) != 0;
-    waves = (variant >> 12) & 0xf;
-    variant &= ~(SDP_HARD_TIES_YMX | (0xf << 12));
+    waves = take_waves(variant);
+    variant &= ~SDP_HARD_TIES_YMX;
     if (int rc = check_shape(B, N, M, variant)) return rc;
     lo = variant == SDP_SW ? 2 : 1;
     return 0;
@@ -1357,10 +1405,7 @@ static int hard_variant(int variant, int B, int N, int M, bool &ymx, int &waves,
 // waves of a workgroup: one per strip in flight, as many as the boundary rows fit LDS for
 static int hard_waves(int forced, int N, int M)
 {
-    int w = sdp_hard::strips(N) < sdp_hard::MAX_WAVES ? sdp_hard::strips(N) : sdp_hard::MAX_WAVES;
-    if (forced > 0 && forced < w) w = forced;
-    while (w > 1 && sdp_hard::forward_lds_bytes(w, M) > (size_t)sdp_hard::LDS_BUDGET) --w;
-    return w;
+    return strip_waves(sdp_hard::strips(N), sdp_hard::MAX_WAVES, forced, M, sdp_hard::forward_lds_bytes, sdp_hard::LDS_BUDGET);
 }
 
 size_t sdp_hard_state_bytes(int B, int N, int M)
@@ -1375,15 +1420,11 @@ static int hard_forward(const float *theta, const float *A, void *state, float *
     bool ymx;
     int waves, lo;
     if (int rc = hard_variant(variant, B, N, M, ymx, waves, lo)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     const int W = hard_waves(waves, N, M);
     auto kernel = pointers ? (ymx ? sdp_hard_fwd_t_kernel : sdp_hard_fwd_kernel) : (ymx ? sdp_hard_val_t_kernel : sdp_hard_val_kernel);
-    hipLaunchKernelGGL(kernel, dim3(B), dim3(64 * W), sdp_hard::forward_lds_bytes(W, M), (hipStream_t)stream, theta, A,
-                       static_cast<uint32_t *>(state), Vt, lens, N, M, lo, W);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, pointers ? "sdp_hard_fwd_kernel" : "sdp_hard_val_kernel");
-    return 0;
+    return strip_launch(kernel, pointers ? "sdp_hard_fwd_kernel" : "sdp_hard_val_kernel", B, W, sdp_hard::forward_lds_bytes(W, M), stream,
+                        theta, A, static_cast<uint32_t *>(state), Vt, lens, N, M, lo, W);
 }
 
 int sdp_hard_forward_f32(const float *theta, const float *A, void *state, float *Vt, int B, int N, int M, const int32_t *lens,
@@ -1408,14 +1449,10 @@ int sdp_hard_walk_f32(const void *state, const float *Et, float *E, int32_t *sta
     bool ymx;
     int waves, lo;
     if (int rc = hard_variant(variant, B, N, M, ymx, waves, lo)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-    hipLaunchKernelGGL(sdp_hard_walk_kernel, dim3(B), dim3(64), sdp_hard::walk_lds_bytes(M), (hipStream_t)stream,
-                       static_cast<const uint32_t *>(state), Et, E, states, counts, lens, N, M, lo, sdp_traceback_capacity(N, M),
-                       ymx ? 1 : 0);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "sdp_hard_walk_kernel");
-    return 0;
+    if (int rc = use_device(device)) return rc;
+    return strip_launch(sdp_hard_walk_kernel, "sdp_hard_walk_kernel", B, 1, sdp_hard::walk_lds_bytes(M), stream,
+                        static_cast<const uint32_t *>(state), Et, E, states, counts, lens, N, M, lo, sdp_traceback_capacity(N, M),
+                        ymx ? 1 : 0);
 }
 
 // ---- local alignment on the hard-max family: the zero floor, Vt = the best cell, ends = the first cell that holds it ----
@@ -1425,16 +1462,12 @@ static int hard_local_forward(const float *theta, const float *A, void *state, f
     bool ymx;
     int waves, lo;
     if (int rc = hard_variant(variant, B, N, M, ymx, waves, lo)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     const int W = hard_waves(waves, N, M);
     auto kernel = pointers ? (ymx ? sdp_hard_local_fwd_t_kernel : sdp_hard_local_fwd_kernel)
                            : (ymx ? sdp_hard_local_val_t_kernel : sdp_hard_local_val_kernel);
-    hipLaunchKernelGGL(kernel, dim3(B), dim3(64 * W), sdp_hard::forward_lds_bytes(W, M), (hipStream_t)stream, theta, A,
-                       static_cast<uint32_t *>(state), Vt, ends, lens, N, M, lo, W);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, pointers ? "sdp_hard_local_fwd_kernel" : "sdp_hard_local_val_kernel");
-    return 0;
+    return strip_launch(kernel, pointers ? "sdp_hard_local_fwd_kernel" : "sdp_hard_local_val_kernel", B, W,
+                        sdp_hard::forward_lds_bytes(W, M), stream, theta, A, static_cast<uint32_t *>(state), Vt, ends, lens, N, M, lo, W);
 }
 
 int sdp_hard_local_forward_f32(const float *theta, const float *A, void *state, float *Vt, int32_t *ends, int B, int N, int M,
@@ -1459,32 +1492,20 @@ int sdp_hard_local_walk_f32(const void *state, const int32_t *ends, const float 
     bool ymx;
     int waves, lo;
     if (int rc = hard_variant(variant, B, N, M, ymx, waves, lo)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-    hipLaunchKernelGGL(sdp_hard_local_walk_kernel, dim3(B), dim3(64), sdp_hard::walk_lds_bytes(M), (hipStream_t)stream,
-                       static_cast<const uint32_t *>(state), ends, Et, E, states, counts, lens, N, M, lo, sdp_traceback_capacity(N, M),
-                       ymx ? 1 : 0);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "sdp_hard_local_walk_kernel");
-    return 0;
+    if (int rc = use_device(device)) return rc;
+    return strip_launch(sdp_hard_local_walk_kernel, "sdp_hard_local_walk_kernel", B, 1, sdp_hard::walk_lds_bytes(M), stream,
+                        static_cast<const uint32_t *>(state), ends, Et, E, states, counts, lens, N, M, lo, sdp_traceback_capacity(N, M),
+                        ymx ? 1 : 0);
 }
 
 // ---- the soft local operator (csrc/sdp_soft_local.hip): a differentiable Smith-Waterman, first order ----
 // `flags` of the three entries: none is defined, any bit is refused
-static int soft_local_args(int B, int N, int M, int flags)
-{
-    if (int rc = check_shape(B, N, M, SDP_NW)) return rc;
-    if (flags != 0) return fail(SDP_E_VARIANT, "sdp_soft_local_*: this family defines no flags");
-    if ((size_t)B * (size_t)N * (size_t)M > ((size_t)1 << 31)) return fail(SDP_E_TOOBIG, "B*N*M exceeds 2^31 elements");
-    return 0;
-}
+static int soft_local_args(int B, int N, int M, int flags) { return flagless_args("sdp_soft_local", B, N, M, flags); }
 
 // waves of a workgroup: one per strip in flight, as many as the boundary rows fit LDS for
 static int soft_local_waves(int N, int M)
 {
-    int w = sdp_soft_local::strips(N) < sdp_soft_local::MAX_WAVES ? sdp_soft_local::strips(N) : sdp_soft_local::MAX_WAVES;
-    while (w > 1 && sdp_soft_local::sweep_lds_bytes(w, M) > (size_t)sdp_soft_local::LDS_BUDGET) --w;
-    return w;
+    return strip_waves(sdp_soft_local::strips(N), sdp_soft_local::MAX_WAVES, 0, M, sdp_soft_local::sweep_lds_bytes, sdp_soft_local::LDS_BUDGET);
 }
 
 size_t sdp_soft_local_state_bytes(int B, int N, int M)
@@ -1497,14 +1518,11 @@ static int soft_local_forward(const float *theta, const float *A, void *state, f
                               int flags, int device, void *stream, bool records)
 {
     if (int rc = soft_local_args(B, N, M, flags)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     const int W = soft_local_waves(N, M);
-    hipLaunchKernelGGL(records ? sdp_soft_local_fwd_kernel : sdp_soft_local_val_kernel, dim3(B), dim3(64 * W),
-                       sdp_soft_local::sweep_lds_bytes(W, M), (hipStream_t)stream, theta, A, static_cast<float4 *>(state), Vt, lens, N, M, W);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, records ? "sdp_soft_local_fwd_kernel" : "sdp_soft_local_val_kernel");
-    return 0;
+    return strip_launch(records ? sdp_soft_local_fwd_kernel : sdp_soft_local_val_kernel,
+                        records ? "sdp_soft_local_fwd_kernel" : "sdp_soft_local_val_kernel", B, W, sdp_soft_local::sweep_lds_bytes(W, M), stream,
+                        theta, A, static_cast<float4 *>(state), Vt, lens, N, M, W);
 }
 
 int sdp_soft_local_forward_f32(const float *theta, const float *A, void *state, float *Vt, int B, int N, int M, const int32_t *lens,
@@ -1526,14 +1544,10 @@ int sdp_soft_local_backward_f32(const void *state, const float *Vt, const float 
 {
     if (!state || !Vt || !Et || !E) return fail(SDP_E_NULLPTR, "sdp_soft_local_backward_f32: null pointer (state, Vt, Et, E; G may be NULL)");
     if (int rc = soft_local_args(B, N, M, flags)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     const int W = soft_local_waves(N, M);
-    hipLaunchKernelGGL(sdp_soft_local_bwd_kernel, dim3(B), dim3(64 * W), sdp_soft_local::sweep_lds_bytes(W, M), (hipStream_t)stream,
-                       static_cast<const float4 *>(state), Vt, Et, E, G, lens, N, M, W);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_bwd_kernel");
-    return 0;
+    return strip_launch(sdp_soft_local_bwd_kernel, "sdp_soft_local_bwd_kernel", B, W, sdp_soft_local::sweep_lds_bytes(W, M), stream,
+                        static_cast<const float4 *>(state), Vt, Et, E, G, lens, N, M, W);
 }
 
 // ---- its second order (csrc/sdp_soft_local_adj.hip): the adjoint pair, on the launch geometry of the first order ----
@@ -1545,14 +1559,10 @@ int sdp_soft_local_adjoint_forward_f32(const void *state, const float *Vt, const
     if (!state || !Vt || !state_d || !Vtd || (!ZE && !ZG))
         return fail(SDP_E_NULLPTR, "sdp_soft_local_adjoint_forward_f32: null pointer (state, Vt, state_d, Vtd; one of ZE, ZG may be NULL)");
     if (int rc = soft_local_args(B, N, M, flags)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     const int W = soft_local_waves(N, M);
-    hipLaunchKernelGGL(sdp_soft_local_adj_fwd_kernel, dim3(B), dim3(64 * W), sdp_soft_local::sweep_lds_bytes(W, M), (hipStream_t)stream,
-                       static_cast<const float4 *>(state), Vt, ZE, ZG, static_cast<float4 *>(state_d), Vtd, lens, N, M, W);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_adj_fwd_kernel");
-    return 0;
+    return strip_launch(sdp_soft_local_adj_fwd_kernel, "sdp_soft_local_adj_fwd_kernel", B, W, sdp_soft_local::sweep_lds_bytes(W, M), stream,
+                        static_cast<const float4 *>(state), Vt, ZE, ZG, static_cast<float4 *>(state_d), Vtd, lens, N, M, W);
 }
 
 int sdp_soft_local_adjoint_backward_f32(const void *state, const void *state_d, const float *Vt, const float *Vtd, const float *Et,
@@ -1561,33 +1571,28 @@ int sdp_soft_local_adjoint_backward_f32(const void *state, const void *state_d, 
     if (!state || !state_d || !Vt || !Vtd || !Et || !Ed)
         return fail(SDP_E_NULLPTR, "sdp_soft_local_adjoint_backward_f32: null pointer (state, state_d, Vt, Vtd, Et, Ed; Gd may be NULL)");
     if (int rc = soft_local_args(B, N, M, flags)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     if (int rc = raise_soft_local_adjoint_limit(device)) return rc;
     const int W = soft_local_waves(N, M);
-    hipLaunchKernelGGL(sdp_soft_local_adj_bwd_kernel, dim3(B), dim3(64 * W), sdp_soft_local::adjoint_lds_bytes(W, M), (hipStream_t)stream,
-                       static_cast<const float4 *>(state), static_cast<const float4 *>(state_d), Vt, Vtd, Et, Ed, Gd, lens, N, M, W);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_adj_bwd_kernel");
-    return 0;
+    return strip_launch(sdp_soft_local_adj_bwd_kernel, "sdp_soft_local_adj_bwd_kernel", B, W, sdp_soft_local::adjoint_lds_bytes(W, M), stream,
+                        static_cast<const float4 *>(state), static_cast<const float4 *>(state_d), Vt, Vtd, Et, Ed, Gd, lens, N, M, W);
 }
 
 // ---- alignments sampled from its posterior (csrc/sdp_soft_local_sample.hip): the end-cell tables, then one walk per sample ----
+constexpr int SAMPLE_WAVES = sdp_soft_local_sample::LANES / 64;   // one wave per workgroup, in both kernels
+static_assert(sdp_soft_local_sample::LANES % 64 == 0, "a workgroup of the sampling kernels is whole waves");
 int sdp_soft_local_end_tables_f32(const void *state, const float *Vt, float *cdf, float *rows, int B, int N, int M, const int32_t *lens,
                                   int flags, int device, void *stream)
 {
     if (!state || !Vt || !cdf || !rows) return fail(SDP_E_NULLPTR, "sdp_soft_local_end_tables_f32: null pointer (state, Vt, cdf, rows)");
     if (int rc = soft_local_args(B, N, M, flags)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     // cdf by one wave per (pair, strip); then, behind it on the stream, rows by one wave per pair
     const unsigned waves = (unsigned)B * (unsigned)sdp_soft_local::strips(N);   // <= B N <= 2^31 / M
-    for (int pass = 0; pass < 2; ++pass) {
-        hipLaunchKernelGGL(sdp_soft_local_tables_kernel, dim3(pass ? (unsigned)B : waves), dim3(sdp_soft_local_sample::LANES), 0,
-                           (hipStream_t)stream, static_cast<const float4 *>(state), Vt, cdf, rows, lens, N, M, pass);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_tables_kernel");
-    }
+    for (int pass = 0; pass < 2; ++pass)
+        if (int rc = strip_launch(sdp_soft_local_tables_kernel, "sdp_soft_local_tables_kernel", pass ? (unsigned)B : waves, SAMPLE_WAVES, 0,
+                                  stream, static_cast<const float4 *>(state), Vt, cdf, rows, lens, N, M, pass))
+            return rc;
     return 0;
 }
 
@@ -1604,27 +1609,17 @@ int sdp_soft_local_sample_paths_f32(const void *state, const float *cdf, const f
     const size_t lim = 0x7fffffffu, waves = (size_t)B * ((K + sdp_soft_local_sample::LANES - 1) / sdp_soft_local_sample::LANES);
     if ((states && (size_t)B * K * cap * 3 > lim) || (size_t)B * K * 2 > lim || waves > lim)
         return fail(SDP_E_TOOBIG, "sdp_soft_local_sample_paths_f32: an output exceeds 2^31 elements");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     sdp_soft_local_sample::Params g = {};
     g.state = static_cast<const float4 *>(state), g.cdf = cdf, g.rows = rows;
     g.states = states, g.counts = counts, g.visits = visits, g.ends = ends, g.lens = lens, g.seed = seed;
     g.B = B, g.N = N, g.M = M, g.K = K, g.sample0 = sample0, g.cap = cap;
-    hipLaunchKernelGGL(sdp_soft_local_sample_kernel, dim3((unsigned)waves), dim3(sdp_soft_local_sample::LANES), 0, (hipStream_t)stream, g);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "sdp_soft_local_sample_kernel");
-    return 0;
+    return strip_launch(sdp_soft_local_sample_kernel, "sdp_soft_local_sample_kernel", (unsigned)waves, SAMPLE_WAVES, 0, stream, g);
 }
 
 // ---- the affine-gap soft local operator (csrc/sdp_affine_local.hip): gap open and gap extend priced separately, first order ----
 // `flags` of the three entries: none is defined, any bit is refused
-static int affine_local_args(int B, int N, int M, int flags)
-{
-    if (int rc = check_shape(B, N, M, SDP_NW)) return rc;
-    if (flags != 0) return fail(SDP_E_VARIANT, "sdp_affine_local_*: this family defines no flags");
-    if ((size_t)B * (size_t)N * (size_t)M > ((size_t)1 << 31)) return fail(SDP_E_TOOBIG, "B*N*M exceeds 2^31 elements");
-    return 0;
-}
+static int affine_local_args(int B, int N, int M, int flags) { return flagless_args("sdp_affine_local", B, N, M, flags); }
 
 size_t sdp_affine_local_state_bytes(int B, int N, int M)
 {
@@ -1636,16 +1631,12 @@ static int affine_local_forward(const float *theta, const float *gap_open, const
                                 int M, const int32_t *lens, int flags, int device, void *stream, bool records)
 {
     if (int rc = affine_local_args(B, N, M, flags)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     if (int rc = raise_affine_local_limit(device)) return rc;
     const int W = sdp_affine_local::waves_for(N, M);
-    hipLaunchKernelGGL(records ? sdp_affine_local_fwd_kernel : sdp_affine_local_val_kernel, dim3(B), dim3(64 * W),
-                       sdp_affine_local::sweep_lds_bytes(W, M), (hipStream_t)stream, theta, gap_open, gap_extend,
-                       static_cast<float4 *>(state), Vt, lens, N, M, W);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, records ? "sdp_affine_local_fwd_kernel" : "sdp_affine_local_val_kernel");
-    return 0;
+    return strip_launch(records ? sdp_affine_local_fwd_kernel : sdp_affine_local_val_kernel,
+                        records ? "sdp_affine_local_fwd_kernel" : "sdp_affine_local_val_kernel", B, W, sdp_affine_local::sweep_lds_bytes(W, M),
+                        stream, theta, gap_open, gap_extend, static_cast<float4 *>(state), Vt, lens, N, M, W);
 }
 
 int sdp_affine_local_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int B, int N,
@@ -1668,23 +1659,18 @@ int sdp_affine_local_backward_f32(const void *state, const float *Vt, const floa
     if (!state || !Vt || !Et || !E)
         return fail(SDP_E_NULLPTR, "sdp_affine_local_backward_f32: null pointer (state, Vt, Et, E; GO and GX may be NULL)");
     if (int rc = affine_local_args(B, N, M, flags)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     if (int rc = raise_affine_local_limit(device)) return rc;
     const int W = sdp_affine_local::waves_for(N, M);
-    hipLaunchKernelGGL(sdp_affine_local_bwd_kernel, dim3(B), dim3(64 * W), sdp_affine_local::sweep_lds_bytes(W, M), (hipStream_t)stream,
-                       static_cast<const float4 *>(state), Vt, Et, E, GO, GX, lens, N, M, W);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "sdp_affine_local_bwd_kernel");
-    return 0;
+    return strip_launch(sdp_affine_local_bwd_kernel, "sdp_affine_local_bwd_kernel", B, W, sdp_affine_local::sweep_lds_bytes(W, M), stream,
+                        static_cast<const float4 *>(state), Vt, Et, E, GO, GX, lens, N, M, W);
 }
 
 // ---- the sparsemax operator (csrc/sdp_sparsemax.hip): the global recurrence under the sparse smoothed maximum, first order ----
 // `variant` of the three entries: SDP_NW / SDP_SW | SDP_WAVES(w); anything else is refused
 static int sparsemax_args(int variant, int B, int N, int M, int &waves, int &lo)
 {
-    waves = (variant >> 12) & 0xf;
-    variant &= ~(0xf << 12);
+    waves = take_waves(variant);
     if (int rc = check_shape(B, N, M, variant)) return rc;
     if ((size_t)B * (size_t)N * (size_t)M > ((size_t)1 << 31)) return fail(SDP_E_TOOBIG, "B*N*M exceeds 2^31 elements");
     lo = variant == SDP_SW ? 2 : 1;
@@ -1694,10 +1680,7 @@ static int sparsemax_args(int variant, int B, int N, int M, int &waves, int &lo)
 // waves of a workgroup: one per strip in flight, as many as the boundary rows fit LDS for
 static int sparsemax_waves(int forced, int N, int M)
 {
-    int w = sdp_sparsemax::strips(N) < sdp_sparsemax::MAX_WAVES ? sdp_sparsemax::strips(N) : sdp_sparsemax::MAX_WAVES;
-    if (forced > 0 && forced < w) w = forced;
-    while (w > 1 && sdp_sparsemax::sweep_lds_bytes(w, M) > (size_t)sdp_sparsemax::LDS_BUDGET) --w;
-    return w;
+    return strip_waves(sdp_sparsemax::strips(N), sdp_sparsemax::MAX_WAVES, forced, M, sdp_sparsemax::sweep_lds_bytes, sdp_sparsemax::LDS_BUDGET);
 }
 
 size_t sdp_sparsemax_state_bytes(int B, int N, int M)
@@ -1711,14 +1694,11 @@ static int sparsemax_forward(const float *theta, const float *A, void *state, fl
 {
     int waves, lo;
     if (int rc = sparsemax_args(variant, B, N, M, waves, lo)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     const int W = sparsemax_waves(waves, N, M);
-    hipLaunchKernelGGL(records ? sdp_sparsemax_fwd_kernel : sdp_sparsemax_val_kernel, dim3(B), dim3(64 * W),
-                       sdp_sparsemax::sweep_lds_bytes(W, M), (hipStream_t)stream, theta, A, static_cast<float4 *>(state), Vt, lens, N, M, lo, W);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, records ? "sdp_sparsemax_fwd_kernel" : "sdp_sparsemax_val_kernel");
-    return 0;
+    return strip_launch(records ? sdp_sparsemax_fwd_kernel : sdp_sparsemax_val_kernel,
+                        records ? "sdp_sparsemax_fwd_kernel" : "sdp_sparsemax_val_kernel", B, W, sdp_sparsemax::sweep_lds_bytes(W, M), stream,
+                        theta, A, static_cast<float4 *>(state), Vt, lens, N, M, lo, W);
 }
 
 int sdp_sparsemax_forward_f32(const float *theta, const float *A, void *state, float *Vt, int B, int N, int M, const int32_t *lens,
@@ -1742,14 +1722,10 @@ int sdp_sparsemax_backward_f32(const void *state, const float *Vt, const float *
     if (!state || !Vt || !Et || !E) return fail(SDP_E_NULLPTR, "sdp_sparsemax_backward_f32: null pointer (state, Vt, Et, E; G may be NULL)");
     int waves, lo;
     if (int rc = sparsemax_args(variant, B, N, M, waves, lo)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     const int W = sparsemax_waves(waves, N, M);
-    hipLaunchKernelGGL(sdp_sparsemax_bwd_kernel, dim3(B), dim3(64 * W), sdp_sparsemax::sweep_lds_bytes(W, M), (hipStream_t)stream,
-                       static_cast<const float4 *>(state), Et, E, G, lens, N, M, lo, W);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "sdp_sparsemax_bwd_kernel");
-    return 0;
+    return strip_launch(sdp_sparsemax_bwd_kernel, "sdp_sparsemax_bwd_kernel", B, W, sdp_sparsemax::sweep_lds_bytes(W, M), stream,
+                        static_cast<const float4 *>(state), Et, E, G, lens, N, M, lo, W);
 }
 
 // ---- its second order (csrc/sdp_sparsemax_adj.hip): the adjoint pair, on the launch geometry of the first order ----
@@ -1762,14 +1738,10 @@ int sdp_sparsemax_adjoint_forward_f32(const void *state, const float *ZE, const 
         return fail(SDP_E_NULLPTR, "sdp_sparsemax_adjoint_forward_f32: null pointer (state, state_d, Vtd; one of ZE, ZG may be NULL)");
     int waves, lo;
     if (int rc = sparsemax_args(variant, B, N, M, waves, lo)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     const int W = sparsemax_waves(waves, N, M);
-    hipLaunchKernelGGL(sdp_sparsemax_adj_fwd_kernel, dim3(B), dim3(64 * W), sdp_sparsemax::sweep_lds_bytes(W, M), (hipStream_t)stream,
-                       static_cast<const float4 *>(state), ZE, ZG, static_cast<float4 *>(state_d), Vtd, lens, N, M, lo, W);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "sdp_sparsemax_adj_fwd_kernel");
-    return 0;
+    return strip_launch(sdp_sparsemax_adj_fwd_kernel, "sdp_sparsemax_adj_fwd_kernel", B, W, sdp_sparsemax::sweep_lds_bytes(W, M), stream,
+                        static_cast<const float4 *>(state), ZE, ZG, static_cast<float4 *>(state_d), Vtd, lens, N, M, lo, W);
 }
 
 int sdp_sparsemax_adjoint_backward_f32(const void *state, const void *state_d, const float *Et, float *Ed, float *Gd, int B, int N, int M,
@@ -1779,15 +1751,11 @@ int sdp_sparsemax_adjoint_backward_f32(const void *state, const void *state_d, c
         return fail(SDP_E_NULLPTR, "sdp_sparsemax_adjoint_backward_f32: null pointer (state, state_d, Et, Ed; Gd may be NULL)");
     int waves, lo;
     if (int rc = sparsemax_args(variant, B, N, M, waves, lo)) return rc;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (int rc = use_device(device)) return rc;
     if (int rc = raise_sparsemax_adjoint_limit(device)) return rc;
     const int W = sparsemax_waves(waves, N, M);
-    hipLaunchKernelGGL(sdp_sparsemax_adj_bwd_kernel, dim3(B), dim3(64 * W), sdp_sparsemax::adjoint_lds_bytes(W, M), (hipStream_t)stream,
-                       static_cast<const float4 *>(state), static_cast<const float4 *>(state_d), Et, Ed, Gd, lens, N, M, lo, W);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "sdp_sparsemax_adj_bwd_kernel");
-    return 0;
+    return strip_launch(sdp_sparsemax_adj_bwd_kernel, "sdp_sparsemax_adj_bwd_kernel", B, W, sdp_sparsemax::adjoint_lds_bytes(W, M), stream,
+                        static_cast<const float4 *>(state), static_cast<const float4 *>(state_d), Et, Ed, Gd, lens, N, M, lo, W);
 }
 
 // ---- the gap-score gradient (csrc/sdp_gap.hip): G = E (Qx + Qy), Gd = Ed (Qx + Qy) + E (Qdx + Qdy) ----

@@ -4,7 +4,8 @@
 //     k = first maximum of c (strict '>'),   V[i,j] = theta[i,j] + c[k],   P[i,j] = k
 //
 // its single best path and the gradient that is Et on that path (include/sdp.h: sdp_hard_*).  Adds and
-// compares only: every build gives the bits of the plain loop over cells.  Three kernels, none shared with the soft sweeps:
+// compares only: every build gives the bits of the plain loop over cells.  Three kernels, none shared with the soft sweeps
+// (the strip schedule's lane moves and score loads, csrc/sdp_strip_device.h, are):
 //
 //   forward   one workgroup per pair, one wave per strip of 64 rows (lane = row), swept along the anti-diagonals: at step s
 //             lane l is at column s - l, V[i-1,j] arrives from lane l - 1 by DPP, V[i-1,j-1] is what arrived one step before.
@@ -27,53 +28,12 @@
 #include <stdint.h>
 
 #include "sdp_hard.h"
+#include "sdp_strip_device.h"
 
 namespace {
 
 using namespace sdp_hard;
-
-constexpr int DPP_WAVE_SHR1 = 0x138;   // lane i <- lane i - 1; lane 0 keeps `old`
-
-__device__ __forceinline__ float from_upper_lane(float lane0, float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0), __float_as_int(v), DPP_WAVE_SHR1, 0xf, 0xf, false));
-}
-
-__device__ __forceinline__ float of_lane(float v, int lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-struct __attribute__((packed, aligned(4))) F4 {   // four floats at any 4-byte boundary
-    float v[4];
-};
-
-// the scores lane `lane` of strip `s` needs in chunk `c`: columns 32 c - lane .. 32 c - lane + 31 of row 64 s + lane; 0 where
-// the cell does not exist (the value is then never used)
-__device__ __forceinline__ void load_chunk(const float *theta, const float *A, size_t plane, int M, int n, int m, int s, int c,
-                                           int lane, float (&th)[CHUNK], float (&a)[CHUNK])
-{
-    const int row = s * STRIP + lane, col0 = c * CHUNK - lane;
-    const bool rowok = row < n;
-    const size_t at = plane + (size_t)(rowok ? row : 0) * M;
-    if (rowok && col0 >= 0 && col0 + CHUNK <= m) {
-        const F4 *pt = reinterpret_cast<const F4 *>(theta + at + col0), *pa = reinterpret_cast<const F4 *>(A + at + col0);
-#pragma unroll
-        for (int g = 0; g < CHUNK / 4; ++g) {
-            const F4 t4 = pt[g], a4 = pa[g];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) th[4 * g + e] = t4.v[e], a[4 * g + e] = a4.v[e];
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < CHUNK; ++t) {
-            const int col = col0 + t;
-            const bool ok = rowok && col >= 0 && col < m;
-            th[t] = ok ? theta[at + col] : 0.f;
-            a[t] = ok ? A[at + col] : 0.f;
-        }
-    }
-}
+static_assert(STRIP == sdp_strip::STRIP && CHUNK == sdp_strip::CHUNK, "csrc/sdp_hard.h and csrc/sdp_strip_device.h disagree");
 
 // PTR: write the pointers (else: the value-only sweep); YMX: ties in the order column step, diagonal, row step
 template <bool PTR, bool YMX>

@@ -6,8 +6,8 @@
 //     Ed[i,j] = Et w (Vd - Vtd) + (qd_x E + q_x Ed)[i+1,j] + (qd_m E + q_m Ed)[i+1,j+1] + (qd_y E + q_y Ed)[i,j+1]
 //     Gd[i,j] = Ed (q_x + q_y) + E (qd_x + qd_y)               E: the first-order recurrence, re-formed beside Ed and not read
 //
-// Two kernels on the schedule of csrc/sdp_soft_local.hip, with which they share the lane moves (csrc/sdp_soft_local_device.h: moved
-// there verbatim, the three first-order kernels compile to what they compiled to before):
+// Two kernels on the schedule of csrc/sdp_soft_local.hip (the strip schedule: DESIGN.md 3.23), with which they share the lane
+// moves, the loads and the stores (csrc/sdp_strip_device.h):
 //
 //   adjoint forward   the forward sweep's schedule with Vd in the place of V: Vd[i-1,j] arrives from lane l - 1 by DPP, a strip's
 //                     bottom row crosses through the LDS ring, ZE and ZG are loaded half a chunk ahead, the records a group of 8
@@ -29,71 +29,16 @@
 #include <stdint.h>
 
 #include "sdp_soft_local.h"
-#include "sdp_soft_local_device.h"
+#include "sdp_strip_device.h"
 
 namespace {
 
 using namespace sdp_soft_local;
+static_assert(STRIP == sdp_strip::STRIP && CHUNK == sdp_strip::CHUNK, "csrc/sdp_soft_local.h and csrc/sdp_strip_device.h disagree");
 
 constexpr int GROUPS = CHUNK / ADJ_GROUP;
 // the dot record of lane 1 at step 0 of chunk 0 of strip 0 -- column -1 of row 1: no cell, so neither sweep writes or uses it as one
 constexpr int NORM_SLOT = 1;
-
-// the cotangents lane `lane` of strip `s` needs in half `h` of chunk `c`: columns 32 c + 16 h - lane .. + 15 of row 64 s + lane,
-// into v[16 h ..]; 0 where the cell does not exist, and everywhere when z is NULL (uniform over the grid)
-__device__ __forceinline__ void load_half(const float *z, size_t plane, int M, int n, int m, int s, int c, int h, int lane,
-                                          float (&v)[CHUNK])
-{
-    const int row = s * STRIP + lane, col0 = c * CHUNK + h * HALF - lane;
-    const bool rowok = z != nullptr && row < n;
-    const size_t at = plane + (size_t)(rowok ? row : 0) * M;
-    if (rowok && col0 >= 0 && col0 + HALF <= m) {
-        const F4 *p = reinterpret_cast<const F4 *>(z + at + col0);
-#pragma unroll
-        for (int g = 0; g < HALF / 4; ++g) {
-            const F4 z4 = p[g];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[h * HALF + 4 * g + e] = z4.v[e];
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < HALF; ++t) {
-            const int col = col0 + t;
-            v[h * HALF + t] = (rowok && col >= 0 && col < m) ? z[at + col] : 0.f;
-        }
-    }
-}
-
-// the records lane `lane` of strip `s` reads in group `g` of chunk `c`: steps 8 g .. 8 g + 7
-__device__ __forceinline__ void load_group(const float4 *state, size_t pair, int CH, int s, int c, int g, int lane, float4 (&q)[ADJ_GROUP])
-{
-    const float4 *src = state + (((pair + s) * CH + c) * CHUNK + g * ADJ_GROUP) * STRIP + lane;
-#pragma unroll
-    for (int t = 0; t < ADJ_GROUP; ++t) q[t] = src[(size_t)t * STRIP];
-}
-
-// 8 consecutive cells of row `row` from column col0 on; only cells of the pair's block are written
-__device__ __forceinline__ void store_group(float *out, size_t plane, int M, int n, int m, int row, int col0, const float (&e)[ADJ_GROUP])
-{
-    if (row >= n) return;
-    const size_t at = plane + (size_t)row * M;
-    if (col0 >= 0 && col0 + ADJ_GROUP <= m) {
-        F4 *p = reinterpret_cast<F4 *>(out + at + col0);
-#pragma unroll
-        for (int g = 0; g < ADJ_GROUP / 4; ++g) {
-            F4 x;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) x.v[k] = e[4 * g + k];
-            p[g] = x;
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < ADJ_GROUP; ++t) {
-            const int col = col0 + t;
-            if (col >= 0 && col < m) out[at + col] = e[t];
-        }
-    }
-}
 
 }  // namespace
 
@@ -131,7 +76,7 @@ extern "C" __global__ void __launch_bounds__(512) sdp_soft_local_adj_fwd_kernel(
         load_half(ZG, plane, M, n, m, s, c, h, lane, zg);
     }
     float4 cur[ADJ_GROUP], nxt[ADJ_GROUP];
-    if (s < S) load_group(state, pair, CH, s, 0, 0, lane, cur);
+    if (s < S) load_records(state, pair, CH, s, 0, 0, lane, cur);
     float vcur = 0.f, up_old = 0.f;   // no cell to the left, none above
     float acc = 0.f;                  // the lane's cells so far: sum of w Vd
     float sw = 0.f, swc = 0.f;        // and sum of w, compensated (Kahan): the normaliser the records themselves imply
@@ -156,9 +101,9 @@ extern "C" __global__ void __launch_bounds__(512) sdp_soft_local_adj_fwd_kernel(
 #pragma unroll
             for (int g = 0; g < GROUPS; ++g) {
                 if (g + 1 < GROUPS)
-                    load_group(state, pair, CH, s, c, g + 1, lane, nxt);
+                    load_records(state, pair, CH, s, c, g + 1, lane, nxt);
                 else if (ns < S)
-                    load_group(state, pair, CH, ns, nc, 0, lane, nxt);
+                    load_records(state, pair, CH, ns, nc, 0, lane, nxt);
                 if (g == GROUPS / 2) {   // steps 0 .. 15 are done: their registers take the next chunk's
                     load_half(ZE, plane, M, n, m, ns, nc, 0, lane, ze);
                     load_half(ZG, plane, M, n, m, ns, nc, 0, lane, zg);
@@ -255,8 +200,8 @@ extern "C" __global__ void __launch_bounds__(512) sdp_soft_local_adj_bwd_kernel(
     int rs = w, rc = 0;
     float4 cur[ADJ_GROUP], curd[ADJ_GROUP], nxt[ADJ_GROUP], nxtd[ADJ_GROUP];
     if (rs < S) {
-        load_group(state, pair, CH, S - 1 - rs, C - 1, GROUPS - 1, lane, cur);
-        load_group(stated, pair, CH, S - 1 - rs, C - 1, GROUPS - 1, lane, curd);
+        load_records(state, pair, CH, S - 1 - rs, C - 1, GROUPS - 1, lane, cur);
+        load_records(stated, pair, CH, S - 1 - rs, C - 1, GROUPS - 1, lane, curd);
     }
     // what this lane's cell of the step before pushes, of E and of Ed: `send` to the row above (the x push, plus the m push of the
     // step before that, which is due one column further left), `py` to its own row; pm: the m push of the step before
@@ -285,11 +230,11 @@ extern "C" __global__ void __launch_bounds__(512) sdp_soft_local_adj_bwd_kernel(
 #pragma unroll
             for (int g = GROUPS - 1; g >= 0; --g) {
                 if (g > 0) {
-                    load_group(state, pair, CH, s, c, g - 1, lane, nxt);
-                    load_group(stated, pair, CH, s, c, g - 1, lane, nxtd);
+                    load_records(state, pair, CH, s, c, g - 1, lane, nxt);
+                    load_records(stated, pair, CH, s, c, g - 1, lane, nxtd);
                 } else if (nrs < S) {
-                    load_group(state, pair, CH, S - 1 - nrs, C - 1 - nrc, GROUPS - 1, lane, nxt);
-                    load_group(stated, pair, CH, S - 1 - nrs, C - 1 - nrc, GROUPS - 1, lane, nxtd);
+                    load_records(state, pair, CH, S - 1 - nrs, C - 1 - nrc, GROUPS - 1, lane, nxt);
+                    load_records(stated, pair, CH, S - 1 - nrs, C - 1 - nrc, GROUPS - 1, lane, nxtd);
                 }
                 float ed[ADJ_GROUP], gd[ADJ_GROUP];
 #pragma unroll
@@ -320,8 +265,8 @@ extern "C" __global__ void __launch_bounds__(512) sdp_soft_local_adj_bwd_kernel(
                     bout = (lane == t) ? tv : bout;
                     boutd = (lane == t) ? tvd : boutd;
                 }
-                store_group(Ed, plane, M, n, m, row, colb + g * ADJ_GROUP, ed);
-                if (Gd) store_group(Gd, plane, M, n, m, row, colb + g * ADJ_GROUP, gd);
+                store_run(Ed, plane, M, n, m, row, colb + g * ADJ_GROUP, ed);
+                if (Gd) store_run(Gd, plane, M, n, m, row, colb + g * ADJ_GROUP, gd);
 #pragma unroll
                 for (int tt = 0; tt < ADJ_GROUP; ++tt) cur[tt] = nxt[tt], curd[tt] = nxtd[tt];
             }

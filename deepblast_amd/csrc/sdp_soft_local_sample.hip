@@ -22,35 +22,13 @@
 
 #include "sdp_sample.h"
 #include "sdp_soft_local.h"
-#include "sdp_soft_local_device.h"
+#include "sdp_strip_device.h"
 #include "sdp_soft_local_sample.h"
 
 namespace {
 
 using namespace sdp_soft_local;
-
-// 16 consecutive cells of row `row` from column col0 on; only cells of the pair's block are written
-__device__ __forceinline__ void store_run(float *out, size_t plane, int M, int n, int m, int row, int col0, const float (&e)[HALF])
-{
-    if (row >= n) return;
-    const size_t at = plane + (size_t)row * M;
-    if (col0 >= 0 && col0 + HALF <= m) {
-        F4 *p = reinterpret_cast<F4 *>(out + at + col0);
-#pragma unroll
-        for (int g = 0; g < HALF / 4; ++g) {
-            F4 x;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) x.v[k] = e[4 * g + k];
-            p[g] = x;
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < HALF; ++t) {
-            const int col = col0 + t;
-            if (col >= 0 && col < m) out[at + col] = e[t];
-        }
-    }
-}
+static_assert(STRIP == sdp_strip::STRIP && CHUNK == sdp_strip::CHUNK, "csrc/sdp_soft_local.h and csrc/sdp_strip_device.h disagree");
 
 // the first index i in [0, count) with x < a[i], or count - 1 if there is none; a non-decreasing (count >= 1)
 __device__ __forceinline__ int first_above(const float *a, int count, float x)

@@ -6,8 +6,9 @@
 //     V[i,j] = theta[i,j] + sum over the support of q_s (c_s - q_s / 2);   Vt = V[n,m]
 //     E[i,j] = q_x[i+1,j] E[i+1,j] + q_m[i+1,j+1] E[i+1,j+1] + q_y[i,j+1] E[i,j+1],  E[n,m] = Et;   G = E (q_x + q_y)
 //
-// a V outside the table is 0, and the loops start at lo = 1 (SDP_NW) or 2 (SDP_SW), as for csrc/sdp_hard.hip.  The schedule is that
-// of csrc/sdp_soft_local.hip, repeated here and not shared (those kernels compile to what they compiled to before).  Three kernels:
+// a V outside the table is 0, and the loops start at lo = 1 (SDP_NW) or 2 (SDP_SW), as for csrc/sdp_hard.hip.  The schedule is the
+// strip schedule of csrc/sdp_soft_local.hip: its lane moves, loads and stores are shared,
+// csrc/sdp_strip_device.h; the sweep loops are this file's own.  Three kernels:
 //
 //   forward   one workgroup per pair, one wave per strip of 64 rows (lane = row), swept along the anti-diagonals: at step s lane l
 //             is at column s - l, V[i-1,j] arrives from lane l - 1 by DPP, V[i-1,j-1] is what arrived one step before.  The waves
@@ -33,59 +34,12 @@
 #include <stdint.h>
 
 #include "sdp_sparsemax.h"
+#include "sdp_strip_device.h"
 
 namespace {
 
 using namespace sdp_sparsemax;
-
-constexpr int DPP_WAVE_SHL1 = 0x130;   // lane i <- lane i + 1; lane 63 keeps `old`
-constexpr int DPP_WAVE_SHR1 = 0x138;   // lane i <- lane i - 1; lane 0 keeps `old`
-
-__device__ __forceinline__ float from_upper_lane(float lane0, float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0), __float_as_int(v), DPP_WAVE_SHR1, 0xf, 0xf, false));
-}
-
-__device__ __forceinline__ float from_lower_lane(float lane63, float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane63), __float_as_int(v), DPP_WAVE_SHL1, 0xf, 0xf, false));
-}
-
-__device__ __forceinline__ float of_lane(float v, int lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-struct __attribute__((packed, aligned(4))) F4 {   // four floats at any 4-byte boundary
-    float v[4];
-};
-
-// the scores lane `lane` of strip `s` needs in chunk `c`: columns 32 c - lane .. 32 c - lane + 31 of row 64 s + lane; 0 where
-// the cell does not exist (the value is then never used)
-__device__ __forceinline__ void load_chunk(const float *theta, const float *A, size_t plane, int M, int n, int m, int s, int c,
-                                           int lane, float (&th)[CHUNK], float (&a)[CHUNK])
-{
-    const int row = s * STRIP + lane, col0 = c * CHUNK - lane;
-    const bool rowok = row < n;
-    const size_t at = plane + (size_t)(rowok ? row : 0) * M;
-    if (rowok && col0 >= 0 && col0 + CHUNK <= m) {
-        const F4 *pt = reinterpret_cast<const F4 *>(theta + at + col0), *pa = reinterpret_cast<const F4 *>(A + at + col0);
-#pragma unroll
-        for (int g = 0; g < CHUNK / 4; ++g) {
-            const F4 t4 = pt[g], a4 = pa[g];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) th[4 * g + e] = t4.v[e], a[4 * g + e] = a4.v[e];
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < CHUNK; ++t) {
-            const int col = col0 + t;
-            const bool ok = rowok && col >= 0 && col < m;
-            th[t] = ok ? theta[at + col] : 0.f;
-            a[t] = ok ? A[at + col] : 0.f;
-        }
-    }
-}
+static_assert(STRIP == sdp_strip::STRIP && CHUNK == sdp_strip::CHUNK, "csrc/sdp_sparsemax.h and csrc/sdp_strip_device.h disagree");
 
 // sparsemax over three values, cm finite, cx and cy finite or -inf -> the value max_q <q, c> - |q|^2 / 2; q: its maximiser.
 // With d = c - max(c) sorted 0 = d1 >= d2 >= d3, tau - max(c) is the largest of -1, (d2 - 1) / 2 and (d2 + d3 - 1) / 3 (the
@@ -190,37 +144,6 @@ __device__ __forceinline__ void sparsemax_forward(const float *theta, const floa
     if (w == lastw && lane == (n - 1) % STRIP) Vt[b] = corner;
 }
 
-// the records lane `lane` of strip `s` reads in half `h` of chunk `c`: steps 16 h .. 16 h + 15
-__device__ __forceinline__ void load_half(const float4 *state, size_t pair, int CH, int s, int c, int h, int lane, float4 (&q)[HALF])
-{
-    const float4 *src = state + (((pair + s) * CH + c) * CHUNK + h * HALF) * STRIP + lane;
-#pragma unroll
-    for (int t = 0; t < HALF; ++t) q[t] = src[(size_t)t * STRIP];
-}
-
-// 16 consecutive cells of row `row` from column col0 on; only cells of the pair's block are written
-__device__ __forceinline__ void store_half(float *out, size_t plane, int M, int n, int m, int row, int col0, const float (&e)[HALF])
-{
-    if (row >= n) return;
-    const size_t at = plane + (size_t)row * M;
-    if (col0 >= 0 && col0 + HALF <= m) {
-        F4 *p = reinterpret_cast<F4 *>(out + at + col0);
-#pragma unroll
-        for (int g = 0; g < HALF / 4; ++g) {
-            F4 x;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) x.v[k] = e[4 * g + k];
-            p[g] = x;
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < HALF; ++t) {
-            const int col = col0 + t;
-            if (col >= 0 && col < m) out[at + col] = e[t];
-        }
-    }
-}
-
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(512) sdp_sparsemax_fwd_kernel(const float *theta, const float *A, float4 *state, float *Vt,
@@ -269,7 +192,7 @@ extern "C" __global__ void __launch_bounds__(512) sdp_sparsemax_bwd_kernel(const
 
     int rs = w, rc = 0;
     float4 cur[HALF], nxt[HALF];
-    if (rs < S) load_half(state, pair, CH, S - 1 - rs, C - 1, 1, lane, cur);
+    if (rs < S) load_records(state, pair, CH, S - 1 - rs, C - 1, 1, lane, cur);
     // what this lane's cell of the step before pushes: `send` to the row above (q_x E, plus q_m E of the step before that, which
     // is due one column further left), `py` to its own row; pm: q_m E of the step before
     float send = 0.f, pm = 0.f, py = 0.f;
@@ -295,9 +218,9 @@ extern "C" __global__ void __launch_bounds__(512) sdp_sparsemax_bwd_kernel(const
 #pragma unroll
             for (int h = 1; h >= 0; --h) {
                 if (h == 1)
-                    load_half(state, pair, CH, s, c, 0, lane, nxt);
+                    load_records(state, pair, CH, s, c, 0, lane, nxt);
                 else if (nrs < S)
-                    load_half(state, pair, CH, S - 1 - nrs, C - 1 - nrc, 1, lane, nxt);
+                    load_records(state, pair, CH, S - 1 - nrs, C - 1 - nrc, 1, lane, nxt);
                 float e[HALF], g[HALF];
 #pragma unroll
                 for (int tt = HALF - 1; tt >= 0; --tt) {
@@ -316,8 +239,8 @@ extern "C" __global__ void __launch_bounds__(512) sdp_sparsemax_bwd_kernel(const
                     const float tv = of_lane(send, 0);
                     bout = (lane == t) ? tv : bout;
                 }
-                store_half(E, plane, M, n, m, row, colb + h * HALF, e);
-                if (G) store_half(G, plane, M, n, m, row, colb + h * HALF, g);
+                store_run(E, plane, M, n, m, row, colb + h * HALF, e);
+                if (G) store_run(G, plane, M, n, m, row, colb + h * HALF, g);
 #pragma unroll
                 for (int tt = 0; tt < HALF; ++tt) cur[tt] = nxt[tt];
             }

@@ -10,8 +10,8 @@
 // V is piecewise quadratic in (theta, A): this is its second derivative away from the kinks, and at a kink -- a q that is exactly 0
 // on the edge of its support -- the convention s = [q > 0].  No exp, no log, and no division: 1 / |S| is one of 1, 1/2, 1/3.
 //
-// Two kernels on the schedule of csrc/sdp_sparsemax.hip (its lane moves are repeated here and not shared: that file and what it
-// compiles to are unchanged), turned into an adjoint pair the way csrc/sdp_soft_local_adj.hip turns csrc/sdp_soft_local.hip:
+// Two kernels on the schedule of csrc/sdp_sparsemax.hip (the strip schedule: DESIGN.md 3.23, its device helpers
+// csrc/sdp_strip_device.h), turned into an adjoint pair the way csrc/sdp_soft_local_adj.hip turns csrc/sdp_soft_local.hip:
 //
 //   adjoint forward   the forward sweep's schedule with Vd in the place of V: Vd[i-1,j] arrives from lane l - 1 by DPP, a strip's
 //                     bottom row crosses through the LDS ring, ZE and ZG are loaded half a chunk ahead, the records a group of 8
@@ -29,90 +29,14 @@
 #include <stdint.h>
 
 #include "sdp_sparsemax.h"
+#include "sdp_strip_device.h"
 
 namespace {
 
 using namespace sdp_sparsemax;
+static_assert(STRIP == sdp_strip::STRIP && CHUNK == sdp_strip::CHUNK, "csrc/sdp_sparsemax.h and csrc/sdp_strip_device.h disagree");
 
 constexpr int GROUPS = CHUNK / ADJ_GROUP;
-constexpr int DPP_WAVE_SHL1 = 0x130;   // lane i <- lane i + 1; lane 63 keeps `old`
-constexpr int DPP_WAVE_SHR1 = 0x138;   // lane i <- lane i - 1; lane 0 keeps `old`
-
-__device__ __forceinline__ float from_upper_lane(float lane0, float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0), __float_as_int(v), DPP_WAVE_SHR1, 0xf, 0xf, false));
-}
-
-__device__ __forceinline__ float from_lower_lane(float lane63, float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane63), __float_as_int(v), DPP_WAVE_SHL1, 0xf, 0xf, false));
-}
-
-__device__ __forceinline__ float of_lane(float v, int lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-struct __attribute__((packed, aligned(4))) F4 {   // four floats at any 4-byte boundary
-    float v[4];
-};
-
-// the cotangents lane `lane` of strip `s` needs in half `h` of chunk `c`: columns 32 c + 16 h - lane .. + 15 of row 64 s + lane,
-// into v[16 h ..]; 0 where the cell does not exist, and everywhere when z is NULL (uniform over the grid)
-__device__ __forceinline__ void load_half(const float *z, size_t plane, int M, int n, int m, int s, int c, int h, int lane,
-                                          float (&v)[CHUNK])
-{
-    const int row = s * STRIP + lane, col0 = c * CHUNK + h * HALF - lane;
-    const bool rowok = z != nullptr && row < n;
-    const size_t at = plane + (size_t)(rowok ? row : 0) * M;
-    if (rowok && col0 >= 0 && col0 + HALF <= m) {
-        const F4 *p = reinterpret_cast<const F4 *>(z + at + col0);
-#pragma unroll
-        for (int g = 0; g < HALF / 4; ++g) {
-            const F4 z4 = p[g];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[h * HALF + 4 * g + e] = z4.v[e];
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < HALF; ++t) {
-            const int col = col0 + t;
-            v[h * HALF + t] = (rowok && col >= 0 && col < m) ? z[at + col] : 0.f;
-        }
-    }
-}
-
-// the records lane `lane` of strip `s` reads in group `g` of chunk `c`: steps 8 g .. 8 g + 7
-__device__ __forceinline__ void load_group(const float4 *state, size_t pair, int CH, int s, int c, int g, int lane, float4 (&q)[ADJ_GROUP])
-{
-    const float4 *src = state + (((pair + s) * CH + c) * CHUNK + g * ADJ_GROUP) * STRIP + lane;
-#pragma unroll
-    for (int t = 0; t < ADJ_GROUP; ++t) q[t] = src[(size_t)t * STRIP];
-}
-
-// 8 consecutive cells of row `row` from column col0 on; only cells of the pair's block are written
-__device__ __forceinline__ void store_group(float *out, size_t plane, int M, int n, int m, int row, int col0, const float (&e)[ADJ_GROUP])
-{
-    if (row >= n) return;
-    const size_t at = plane + (size_t)row * M;
-    if (col0 >= 0 && col0 + ADJ_GROUP <= m) {
-        F4 *p = reinterpret_cast<F4 *>(out + at + col0);
-#pragma unroll
-        for (int g = 0; g < ADJ_GROUP / 4; ++g) {
-            F4 x;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) x.v[k] = e[4 * g + k];
-            p[g] = x;
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < ADJ_GROUP; ++t) {
-            const int col = col0 + t;
-            if (col >= 0 && col < m) out[at + col] = e[t];
-        }
-    }
-}
-
 }  // namespace
 
 // ZE or ZG may be NULL (zeros).  Strips, chunks, the ring and the progress words are those of sdp_sparsemax_fwd_kernel.
@@ -148,7 +72,7 @@ extern "C" __global__ void __launch_bounds__(512) sdp_sparsemax_adj_fwd_kernel(c
         load_half(ZG, plane, M, n, m, s, c, h, lane, zg);
     }
     float4 cur[ADJ_GROUP], nxt[ADJ_GROUP];
-    if (s < S) load_group(state, pair, CH, s, 0, 0, lane, cur);
+    if (s < S) load_records(state, pair, CH, s, 0, 0, lane, cur);
     float vcur = 0.f, up_old = 0.f;   // the zero border: column 0 of the table, and its cell of the row above
     float corner = 0.f;               // Vd of this lane's cell in column m: Vtd, in the lane of row n
 
@@ -173,9 +97,9 @@ extern "C" __global__ void __launch_bounds__(512) sdp_sparsemax_adj_fwd_kernel(c
 #pragma unroll
             for (int g = 0; g < GROUPS; ++g) {
                 if (g + 1 < GROUPS)
-                    load_group(state, pair, CH, s, c, g + 1, lane, nxt);
+                    load_records(state, pair, CH, s, c, g + 1, lane, nxt);
                 else if (ns < S)
-                    load_group(state, pair, CH, ns, nc, 0, lane, nxt);
+                    load_records(state, pair, CH, ns, nc, 0, lane, nxt);
                 if (g == GROUPS / 2) {   // steps 0 .. 15 are done: their registers take the next chunk's
                     load_half(ZE, plane, M, n, m, ns, nc, 0, lane, ze);
                     load_half(ZG, plane, M, n, m, ns, nc, 0, lane, zg);
@@ -259,8 +183,8 @@ extern "C" __global__ void __launch_bounds__(512) sdp_sparsemax_adj_bwd_kernel(c
     int rs = w, rc = 0;
     float4 cur[ADJ_GROUP], curd[ADJ_GROUP], nxt[ADJ_GROUP], nxtd[ADJ_GROUP];
     if (rs < S) {
-        load_group(state, pair, CH, S - 1 - rs, C - 1, GROUPS - 1, lane, cur);
-        load_group(stated, pair, CH, S - 1 - rs, C - 1, GROUPS - 1, lane, curd);
+        load_records(state, pair, CH, S - 1 - rs, C - 1, GROUPS - 1, lane, cur);
+        load_records(stated, pair, CH, S - 1 - rs, C - 1, GROUPS - 1, lane, curd);
     }
     // what this lane's cell of the step before pushes, of E and of Ed: `send` to the row above (the x push, plus the m push of the
     // step before that, which is due one column further left), `py` to its own row; pm: the m push of the step before
@@ -290,11 +214,11 @@ extern "C" __global__ void __launch_bounds__(512) sdp_sparsemax_adj_bwd_kernel(c
 #pragma unroll
             for (int g = GROUPS - 1; g >= 0; --g) {
                 if (g > 0) {
-                    load_group(state, pair, CH, s, c, g - 1, lane, nxt);
-                    load_group(stated, pair, CH, s, c, g - 1, lane, nxtd);
+                    load_records(state, pair, CH, s, c, g - 1, lane, nxt);
+                    load_records(stated, pair, CH, s, c, g - 1, lane, nxtd);
                 } else if (nrs < S) {
-                    load_group(state, pair, CH, S - 1 - nrs, C - 1 - nrc, GROUPS - 1, lane, nxt);
-                    load_group(stated, pair, CH, S - 1 - nrs, C - 1 - nrc, GROUPS - 1, lane, nxtd);
+                    load_records(state, pair, CH, S - 1 - nrs, C - 1 - nrc, GROUPS - 1, lane, nxt);
+                    load_records(stated, pair, CH, S - 1 - nrs, C - 1 - nrc, GROUPS - 1, lane, nxtd);
                 }
                 float ed[ADJ_GROUP], gd[ADJ_GROUP];
 #pragma unroll
@@ -323,8 +247,8 @@ extern "C" __global__ void __launch_bounds__(512) sdp_sparsemax_adj_bwd_kernel(c
                     bout = (lane == t) ? tv : bout;
                     boutd = (lane == t) ? tvd : boutd;
                 }
-                store_group(Ed, plane, M, n, m, row, colb + g * ADJ_GROUP, ed);
-                if (Gd) store_group(Gd, plane, M, n, m, row, colb + g * ADJ_GROUP, gd);
+                store_run(Ed, plane, M, n, m, row, colb + g * ADJ_GROUP, ed);
+                if (Gd) store_run(Gd, plane, M, n, m, row, colb + g * ADJ_GROUP, gd);
 #pragma unroll
                 for (int tt = 0; tt < ADJ_GROUP; ++tt) cur[tt] = nxt[tt], curd[tt] = nxtd[tt];
             }
