@@ -745,6 +745,77 @@ class HipEngine:
         self.call("sdp_affine_local_backward_f32", AFFINE_LOCAL_KERNELS[162], dev, state, Vt, Et, E, GO, GX, B, N, M, lens, 0)
         return E, GO, GX
 
+    # ---- the hard affine-gap local operator (include/sdp.h: sdp_hard_affine_local_*) ------------
+    def _hard_affine_variant(self, ymx, waves=True):
+        """`variant` of the sdp_hard_affine_local_* entries; waves=False for the walk, which runs one wave per pair."""
+        w = self.force_waves.get("hard_affine", 0) if waves else 0
+        return (_lib.SDP_HARD_TIES_YMX if ymx else 0) | (_lib.SDP_WAVES(w) if w else 0)
+
+    def _hard_affine_inputs(self, theta, gap_open, gap_extend):
+        check_args(theta, torch.float32, theta=theta, gap_open=gap_open, gap_extend=gap_extend)
+        check_args(theta, None, tuple(theta.shape), gap_open=gap_open, gap_extend=gap_extend)
+        return theta.contiguous(), gap_open.contiguous(), gap_extend.contiguous()
+
+    def hard_affine_local_forward(self, theta, gap_open, gap_extend, lens=None, ymx=False):
+        """-> (Vt (B,), state, ends (B, 3) int32): the Gotoh max-plus sweep -- Vt the best plane value, ends its 0-based (i, j) and
+        plane, (-1, -1, -1) where nothing is positive -- and its 2-bit pointers, three planes (opaque int32 tensor of
+        sdp_hard_affine_local_state_bytes).  ymx: the tensors are a TRANSPOSED problem; ends come back in the coordinates and
+        plane names handed over."""
+        dev = self.device_of(theta)
+        theta, gap_open, gap_extend = self._hard_affine_inputs(theta, gap_open, gap_extend)
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        nbytes = self.lib.sdp_hard_affine_local_state_bytes(B, N, M)
+        state = torch.empty(max(nbytes, 4) // 4, dtype=torch.int32, device=theta.device)
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        ends = torch.empty((B, 3), dtype=torch.int32, device=theta.device)
+        self.call("sdp_hard_affine_local_forward_f32", HARD_AFFINE_LOCAL_KERNELS[171 if ymx else 170], dev, theta, gap_open, gap_extend,
+                  state, Vt, ends, B, N, M, lens, self._hard_affine_variant(ymx))
+        return Vt, state, ends
+
+    def hard_affine_local_forward_value(self, theta, gap_open, gap_extend, lens=None, ymx=False, want_ends=True):
+        """-> (Vt (B,), ends (B, 3) int32 or None): the same sweep with the pointers compiled out (the same bits)."""
+        dev = self.device_of(theta)
+        theta, gap_open, gap_extend = self._hard_affine_inputs(theta, gap_open, gap_extend)
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        ends = torch.empty((B, 3), dtype=torch.int32, device=theta.device) if want_ends else None
+        self.call("sdp_hard_affine_local_forward_value_f32", HARD_AFFINE_LOCAL_KERNELS[173 if ymx else 172], dev, theta, gap_open,
+                  gap_extend, Vt, ends, B, N, M, lens, self._hard_affine_variant(ymx))
+        return Vt, ends
+
+    def hard_affine_local_walk(self, state, ends, shape, lens=None, Et=None, ymx=False, want_E=True, want_GO=False, want_GX=False,
+                               want_states=True, E_out=None, GO_out=None, GX_out=None, states_out=None):
+        """The walk along the pointers of hard_affine_local_forward, from `ends` -> (E, GO, GX (B,N,M) or None each, states
+        (B,cap,3) int32 or None, counts (B,) or None).  E: Et[b] on pair b's path, GO / GX: Et[b] on its gap cells entered from
+        another plane / the same plane, +0 on every other cell of the plane; states / counts: the path alone (no padding), start
+        first; row cap - 1 of states: (number of path cells, i and j of its first cell).  *_out: buffers to write into."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        lens = self._lens(lens, B, state.device)
+        check_args(state, torch.int32, (B, 3), True, ValueError, ends=ends)
+        planes = [None, None, None]
+        states = counts = None
+        wants = (want_E, want_GO, want_GX)
+        if any(wants):
+            if Et is None:
+                raise ValueError("hard_affine_local_walk: E, GO and GX need Et")
+            check_args(state, Et=Et)
+            Et = Et.detach().to(torch.float32).expand(B).contiguous()
+            check_args(state, torch.float32, (B, N, M), True, ValueError, E_out=E_out, GO_out=GO_out, GX_out=GX_out)
+            for k, (want, buf) in enumerate(zip(wants, (E_out, GO_out, GX_out))):
+                if want:
+                    planes[k] = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if buf is None else buf
+        if want_states:
+            cap = self.lib.sdp_traceback_capacity(N, M)
+            check_args(state, torch.int32, (B, cap, 3), True, ValueError, states_out=states_out)
+            states = torch.empty((B, cap, 3), dtype=torch.int32, device=state.device) if states_out is None else states_out
+            counts = torch.empty(B, dtype=torch.int32, device=state.device)
+        self.call("sdp_hard_affine_local_walk_f32", HARD_AFFINE_LOCAL_KERNELS[174], dev, state, ends, Et if any(wants) else None, *planes,
+                  states, counts, B, N, M, lens, self._hard_affine_variant(ymx, waves=False))
+        return planes[0], planes[1], planes[2], states, counts
+
     # ---- alignments sampled from the posterior (include/sdp.h: sdp_sample_paths_*) -------------------
     def sample_paths(self, state, shape, variant, K, lens=None, seed=0, sample0=0, exact_state=False, transposed=False,
                      want_states=True, want_visits=False):
@@ -836,6 +907,10 @@ SPARSEMAX_KERNELS = {150: "sdp_sparsemax_fwd_kernel", 151: "sdp_sparsemax_val_ke
 SPARSEMAX_ADJOINT_KERNELS = {154: "sdp_sparsemax_adj_fwd_kernel", 155: "sdp_sparsemax_adj_bwd_kernel"}
 # kernel id (csrc/sdp_affine_local.h) -> symbol of the affine-gap soft local operator's kernels
 AFFINE_LOCAL_KERNELS = {160: "sdp_affine_local_fwd_kernel", 161: "sdp_affine_local_val_kernel", 162: "sdp_affine_local_bwd_kernel"}
+# kernel id (csrc/sdp_hard_affine.h) -> symbol of the hard affine-gap local operator's kernels
+HARD_AFFINE_LOCAL_KERNELS = {170: "sdp_hard_affine_local_fwd_kernel", 171: "sdp_hard_affine_local_fwd_t_kernel",
+                             172: "sdp_hard_affine_local_val_kernel", 173: "sdp_hard_affine_local_val_t_kernel",
+                             174: "sdp_hard_affine_local_walk_kernel"}
 
 _SWEEPS = ("sdp_forward", "sdp_backward", "sdp_adjoint_forward", "sdp_adjoint_backward")
 # dtype -> (suffix of the four sweeps' entries, their launch labels (float32: where the library's plan is not asked),

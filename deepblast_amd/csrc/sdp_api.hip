@@ -18,6 +18,7 @@
 #include "sdp_soft_local_sample.h"
 #include "sdp_sparsemax.h"
 #include "sdp_affine_local.h"
+#include "sdp_hard_affine.h"
 #include "sdp_kernels.h"
 
 namespace {
@@ -626,6 +627,20 @@ int raise_affine_local_limit(int device)
                               sdp_affine_local::LDS_BUDGET);
 }
 
+// the hard affine-gap local operator's sweeps keep three boundary rows per wave (sdp_hard_affine::sweep_lds_bytes), and its walk
+// three planes of a strip's pointer lines (sdp_hard_affine::walk_lds_bytes): up to 160 KB and 99 KB
+int raise_hard_affine_limit(int device)
+{
+    static thread_local unsigned long long raised = 0;
+    return raise_strip_limits(raised, device,
+                              {{(const void *)sdp_hard_affine_local_fwd_kernel, "hipFuncSetAttribute(sdp_hard_affine_local_fwd_kernel)"},
+                               {(const void *)sdp_hard_affine_local_fwd_t_kernel, "hipFuncSetAttribute(sdp_hard_affine_local_fwd_t_kernel)"},
+                               {(const void *)sdp_hard_affine_local_val_kernel, "hipFuncSetAttribute(sdp_hard_affine_local_val_kernel)"},
+                               {(const void *)sdp_hard_affine_local_val_t_kernel, "hipFuncSetAttribute(sdp_hard_affine_local_val_t_kernel)"},
+                               {(const void *)sdp_hard_affine_local_walk_kernel, "hipFuncSetAttribute(sdp_hard_affine_local_walk_kernel)"}},
+                              sdp_hard_affine::LDS_BUDGET);
+}
+
 // ---- what the entries of the strip-schedule families share ----
 // waves of a workgroup: one per strip in flight, lowered to `forced` if 0 < forced, then until the family's ring fits its budget
 int strip_waves(int strips, int max_waves, int forced, int M, size_t (*lds_bytes)(int, int), int budget)
@@ -779,6 +794,12 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_affine_local::ID_FWD: return "sdp_affine_local_fwd_kernel";
     case sdp_affine_local::ID_VAL: return "sdp_affine_local_val_kernel";
     case sdp_affine_local::ID_BWD: return "sdp_affine_local_bwd_kernel";
+    // the hard affine-gap local operator (csrc/sdp_hard_affine.hip)
+    case sdp_hard_affine::ID_FWD: return "sdp_hard_affine_local_fwd_kernel";
+    case sdp_hard_affine::ID_FWD_T: return "sdp_hard_affine_local_fwd_t_kernel";
+    case sdp_hard_affine::ID_VAL: return "sdp_hard_affine_local_val_kernel";
+    case sdp_hard_affine::ID_VAL_T: return "sdp_hard_affine_local_val_t_kernel";
+    case sdp_hard_affine::ID_WALK: return "sdp_hard_affine_local_walk_kernel";
     }
     return nullptr;
 }
@@ -800,7 +821,8 @@ int sdp_init(int device)
     if (int rc = raise_scores_limits(device)) return rc;
     if (int rc = raise_soft_local_adjoint_limit(device)) return rc;
     if (int rc = raise_sparsemax_adjoint_limit(device)) return rc;
-    return raise_affine_local_limit(device);
+    if (int rc = raise_affine_local_limit(device)) return rc;
+    return raise_hard_affine_limit(device);
 }
 
 int sdp_device_status(int device, int32_t info[4])
@@ -1664,6 +1686,72 @@ int sdp_affine_local_backward_f32(const void *state, const float *Vt, const floa
     const int W = sdp_affine_local::waves_for(N, M);
     return strip_launch(sdp_affine_local_bwd_kernel, "sdp_affine_local_bwd_kernel", B, W, sdp_affine_local::sweep_lds_bytes(W, M), stream,
                         static_cast<const float4 *>(state), Vt, Et, E, GO, GX, lens, N, M, W);
+}
+
+// ---- the hard affine-gap local operator (csrc/sdp_hard_affine.hip): the max-plus member of the affine family ----
+// `variant` of the three entries: SDP_HARD_TIES_YMX | SDP_WAVES(w); anything else, SDP_SW included, is refused
+static int hard_affine_args(int variant, int B, int N, int M, bool &ymx, int &waves)
+{
+    ymx = (variant & SDP_HARD_TIES_YMX) != 0;
+    waves = take_waves(variant);
+    variant &= ~SDP_HARD_TIES_YMX;
+    if (int rc = check_shape(B, N, M, SDP_NW)) return rc;
+    if (variant != 0) return fail(SDP_E_VARIANT, "sdp_hard_affine_local_*: variant takes SDP_HARD_TIES_YMX and SDP_WAVES(w) only");
+    if ((size_t)B * (size_t)N * (size_t)M > ((size_t)1 << 31)) return fail(SDP_E_TOOBIG, "B*N*M exceeds 2^31 elements");
+    return 0;
+}
+
+size_t sdp_hard_affine_local_state_bytes(int B, int N, int M)
+{
+    if (B <= 0 || N <= 0 || M <= 0 || M > sdp::MAX_COLS) return 0;
+    return (size_t)B * sdp_hard_affine::pair_words(N, M) * 4;
+}
+
+static int hard_affine_forward(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int32_t *ends,
+                               int B, int N, int M, const int32_t *lens, int variant, int device, void *stream, bool pointers)
+{
+    bool ymx;
+    int waves;
+    if (int rc = hard_affine_args(variant, B, N, M, ymx, waves)) return rc;
+    if (int rc = use_device(device)) return rc;
+    if (int rc = raise_hard_affine_limit(device)) return rc;
+    const int W = sdp_hard_affine::waves_for(N, M, waves);
+    auto kernel = pointers ? (ymx ? sdp_hard_affine_local_fwd_t_kernel : sdp_hard_affine_local_fwd_kernel)
+                           : (ymx ? sdp_hard_affine_local_val_t_kernel : sdp_hard_affine_local_val_kernel);
+    return strip_launch(kernel, pointers ? "sdp_hard_affine_local_fwd_kernel" : "sdp_hard_affine_local_val_kernel", B, W,
+                        sdp_hard_affine::sweep_lds_bytes(W, M), stream, theta, gap_open, gap_extend, static_cast<uint32_t *>(state), Vt, ends,
+                        lens, N, M, W);
+}
+
+int sdp_hard_affine_local_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt,
+                                      int32_t *ends, int B, int N, int M, const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!theta || !gap_open || !gap_extend || !state || !Vt || !ends)
+        return fail(SDP_E_NULLPTR, "sdp_hard_affine_local_forward_f32: null pointer");
+    return hard_affine_forward(theta, gap_open, gap_extend, state, Vt, ends, B, N, M, lens, variant, device, stream, true);
+}
+
+int sdp_hard_affine_local_forward_value_f32(const float *theta, const float *gap_open, const float *gap_extend, float *Vt, int32_t *ends,
+                                            int B, int N, int M, const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!theta || !gap_open || !gap_extend || !Vt) return fail(SDP_E_NULLPTR, "sdp_hard_affine_local_forward_value_f32: null pointer");
+    return hard_affine_forward(theta, gap_open, gap_extend, nullptr, Vt, ends, B, N, M, lens, variant, device, stream, false);
+}
+
+int sdp_hard_affine_local_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, float *GO, float *GX, int32_t *states,
+                                   int32_t *counts, int B, int N, int M, const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!state || !ends || (!E && !GO && !GX && !states) || ((E || GO || GX) && !Et) || (states && !counts))
+        return fail(SDP_E_NULLPTR,
+                    "sdp_hard_affine_local_walk_f32: null pointer (state, ends; E, GO or GX with Et, or states with counts, or both)");
+    bool ymx;
+    int waves;
+    if (int rc = hard_affine_args(variant, B, N, M, ymx, waves)) return rc;
+    if (int rc = use_device(device)) return rc;
+    if (int rc = raise_hard_affine_limit(device)) return rc;
+    return strip_launch(sdp_hard_affine_local_walk_kernel, "sdp_hard_affine_local_walk_kernel", B, 1, sdp_hard_affine::walk_lds_bytes(M),
+                        stream, static_cast<const uint32_t *>(state), ends, Et, E, GO, GX, states, counts, lens, N, M,
+                        sdp_traceback_capacity(N, M), ymx ? 1 : 0);
 }
 
 // ---- the sparsemax operator (csrc/sdp_sparsemax.hip): the global recurrence under the sparse smoothed maximum, first order ----

@@ -651,7 +651,8 @@ int sdp_sparsemax_adjoint_backward_f32(const void *state, const void *state_d, c
  * exactly 0 there, and nothing is NaN when every gap is forbidden).  E, GO and GX are +0 by bit pattern outside the pair's [:n, :m]
  * block (the backward kernel writes them: no extra launch); a pair with n < 1 or m < 1 has Vt = 0 and all gradients 0.  fp32 only.
  * No floating-point atomics: two calls on the same inputs give the same bits, and sdp_affine_local_forward_value_f32 gives the bits
- * of sdp_affine_local_forward_f32's Vt.  NOT built: the second order, sampling, float64, a hard (max-plus) affine kernel.
+ * of sdp_affine_local_forward_f32's Vt.  NOT built: the second order, sampling, float64.  The hard (max-plus) member of the family is
+ * sdp_hard_affine_local_* below.
  *   state    sdp_affine_local_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: 48 bytes per cell -- one record
  *            {q[s<-x], q[s<-m], q[s<-y], V_s} per plane s -- in a private layout; written by sdp_affine_local_forward_f32, read by
  *            sdp_affine_local_backward_f32 with the same B, N, M, lens (which needs neither theta, O nor X).  Only records of cells
@@ -670,6 +671,64 @@ int sdp_affine_local_forward_value_f32(const float *theta, const float *gap_open
                                        const int32_t *lens, int flags, int device, void *stream);
 int sdp_affine_local_backward_f32(const void *state, const float *Vt, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
                                   const int32_t *lens, int flags, int device, void *stream);
+
+/* The HARD AFFINE-GAP LOCAL operator (csrc/sdp_hard_affine.hip): the max-plus member of the affine family above, as
+ * sdp_hard_local_* is of the one-score family -- the optimal affine-gap Smith-Waterman (Gotoh) alignment of every pair, its score,
+ * its end and its path.  (Added after SDP_VERSION 106 without a version change: look the symbols up.)  Adds and compares only: the
+ * results are the BITS of this loop.  (n, m) = lens[b] clamped to [0, N] x [0, M], or (N, M); cells 1-based; theta, O = gap_open and
+ * X = gap_extend 0-based (B, N, M) fp32; planes x, m, y = 0, 1, 2, named by the step that entered the cell; H outside the table is
+ * -inf; every `+` is one rounded fp32 addition:
+ *
+ *     for i in 1..n, j in 1..m:
+ *         t, o, x = theta[i-1,j-1], O[i-1,j-1], X[i-1,j-1]
+ *         m plane: best = +0, k = 3 (START: the alignment begins at this cell)
+ *                  for p in (x, m, y): if H[i-1,j-1,p] > best: best, k = H[i-1,j-1,p], p      (strict '>')
+ *                  H[i,j,m] = t + best;  P[i,j,m] = k
+ *         x plane: c = (x + H[i-1,j,x],  o + H[i-1,j,m],  o + H[i-1,j,y]);  k = FIRST maximum in that order (strict '>')
+ *                  H[i,j,x] = t + c[k];  P[i,j,x] = k
+ *         y plane: c = (o + H[i,j-1,x],  o + H[i,j-1,m],  x + H[i,j-1,y]);  k likewise
+ *                  H[i,j,y] = t + c[k];  P[i,j,y] = k
+ *     Vt  = the maximum of +0 and every H[i,j,s]                      (+0 for an empty pair or when nothing is positive)
+ *     end = the FIRST (i, j, s) that holds Vt, cells in row-major order, planes x, m, y within a cell, if Vt > 0; else none
+ *     path: from end: record (i-1, j-1, s); k = P[i,j,s]; step to the predecessor cell of plane s; stop after the record if
+ *           k == START, else s = k.  The first cell of a path is always in plane m.
+ *
+ * theta is finite; O and X are finite or -inf (a forbidden opening or extension); +inf and NaN are unspecified.  No inf - inf can
+ * form.  A plane that is -inf is never on a path: its pointer is unspecified and never read.  The path model is the soft
+ * operator's: a gap run of one kind may follow the other kind and pays an opening; the start cell and an m step count as
+ * "otherwise".  The floor is "start here", taken BEFORE theta (not the after-theta floor of sdp_hard_local_*).  With O == X <= 0,
+ * Vt has the bits of sdp_hard_local_*'s Vt on (theta, O).
+ *   variant  SDP_HARD_TIES_YMX | SDP_WAVES(w); anything else, SDP_SW included: SDP_E_VARIANT.
+ *            SDP_HARD_TIES_YMX: for a problem handed over TRANSPOSED (theta^T, O^T, X^T, swapped lens).  Planes are scanned
+ *            y, m, x in all three recurrences and at the end cell (START still wins ties), cells column-major for the end, and the
+ *            walk reports the original's state names (plane x as 2, plane y as 0): Vt, the end and the path are then those of the
+ *            problem as it was before it was transposed.  (i, j) and ends stay in the coordinates and plane names handed over.
+ *   state    sdp_hard_affine_local_state_bytes(B, N, M) = B strips(N) words(M) 3 * 64 * 4 bytes, strips(N) = ceil(N / 64),
+ *            words(M) = 2 ceil((M + 63) / 32); 0 on a bad shape or M > sdp_max_cols().  DEVICE, caller-owned: 2 bits per cell and
+ *            plane, state[((((pair strips(N) + S) words(M) + q) 3 + s) 64 + lane].  Only lines of the pair's block are written and read.
+ *   ends     (B, 3) int32: the 0-based end cell and its plane, (-1, -1, -1) where no cell is positive.  Written by the forward
+ *            entries (sdp_hard_affine_local_forward_value_f32: may be NULL), read by the walk; an end outside the pair's block or
+ *            the three planes is no end, and nothing is read through it.
+ * sdp_hard_affine_local_walk_f32: one wavefront per pair, from ends[b].  Outputs, each nullable on its own:
+ *   E        (B, N, M): the whole plane is written, Et[b] on path cells, +0 elsewhere.
+ *   GO, GX   (B, N, M): whole planes, Et[b] on a path cell entered through a gap step whose predecessor plane differs (GO) or is
+ *            the same (GX), +0 elsewhere: the subgradients of Vt in gap_open and gap_extend.
+ *   states   (B, sdp_traceback_capacity(N, M), 3) int32 with counts (B,): the path alone, start first, no padding, rows (i, j, s)
+ *            0-based; row cap - 1 is (cells, first i, first j), (0, -1, -1) for a pair without a positive cell -- the format of
+ *            sdp_hard_local_walk_f32.
+ *   Et       (B,): needed when any of E, GO, GX is asked for; counts is needed when states is given.
+ * One workgroup per pair in the sweeps, rows unbounded, M <= sdp_max_cols(); three boundary rows per wave in LDS (eight waves up to
+ * M = 1642, six at the column limit) and three planes of pointer lines in the walk, for which the entries raise the kernels'
+ * dynamic-LDS limit (sdp_init does it too, before a stream capture).  Plain vector stores only, no atomics: two calls give the same
+ * bits, and the value-only entry gives the bits of the pointer entry's Vt and ends.  All arguments are checked before any device
+ * call: SDP_E_NULLPTR, SDP_E_SHAPE, SDP_E_MAXCOLS, SDP_E_VARIANT, SDP_E_TOOBIG (N*M > 2^28, or B*N*M > 2^31 elements). */
+size_t sdp_hard_affine_local_state_bytes(int B, int N, int M);
+int sdp_hard_affine_local_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt,
+                                      int32_t *ends, int B, int N, int M, const int32_t *lens, int variant, int device, void *stream);
+int sdp_hard_affine_local_forward_value_f32(const float *theta, const float *gap_open, const float *gap_extend, float *Vt, int32_t *ends,
+                                            int B, int N, int M, const int32_t *lens, int variant, int device, void *stream);
+int sdp_hard_affine_local_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, float *GO, float *GX, int32_t *states,
+                                   int32_t *counts, int B, int N, int M, const int32_t *lens, int variant, int device, void *stream);
 
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept
