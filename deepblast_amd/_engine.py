@@ -745,6 +745,53 @@ class HipEngine:
         self.call("sdp_affine_local_backward_f32", AFFINE_LOCAL_KERNELS[162], dev, state, Vt, Et, E, GO, GX, B, N, M, lens, 0)
         return E, GO, GX
 
+    # ---- alignments sampled from its posterior (include/sdp.h: sdp_affine_local_end_tables_f32, sdp_affine_local_sample_paths_f32) ----
+    def affine_local_end_tables(self, state, Vt, shape, lens=None, cdf_out=None, rows_out=None):
+        """The end-cell tables over the records of affine_local_forward -> (cdf (B,N,M), rows (B,N+1)) fp32: the running sums of
+        (w_x + w_y) + w_m, w_s = exp(V_s - Vt), along every row, and of the rows' totals from exp(-Vt) on.  Only entries inside a
+        pair's block are written; fresh tensors are zero outside.  cdf_out / rows_out: buffers to write into instead of fresh ones."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        check_args(state, torch.float32, (B,), True, Vt=Vt)
+        check_args(state, torch.float32, (B, N, M), True, ValueError, cdf_out=cdf_out)
+        check_args(state, torch.float32, (B, N + 1), True, ValueError, rows_out=rows_out)
+        lens = self._lens(lens, B, state.device)
+        new = torch.empty if lens is None else torch.zeros      # (without lengths every entry is written)
+        cdf = new((B, N, M), dtype=torch.float32, device=state.device) if cdf_out is None else cdf_out
+        rows = new((B, N + 1), dtype=torch.float32, device=state.device) if rows_out is None else rows_out
+        self.call("sdp_affine_local_end_tables_f32", AFFINE_LOCAL_SAMPLE_KERNELS[164], dev, state, Vt, cdf, rows, B, N, M, lens, 0)
+        return cdf, rows
+
+    def affine_local_sample_paths(self, state, Vt, cdf, rows, shape, K, lens=None, seed=0, sample0=0, want_states=True,
+                                  want_visits=False, want_opens=False, want_extends=False, want_ends=False):
+        """K local alignments per pair drawn from the posterior, on the `state` and `Vt` of affine_local_forward and the tables of
+        affine_local_end_tables -> (states (B,K,cap,3) int32 or None, counts (B,K) int32 or None, visits, opens, extends (B,N,M)
+        int32 or None, ends (B,K,3) int32 or None).  Sample (b, k) is sample number sample0 + k of pair b under `seed` whatever K
+        is; its list -- the path alone, start first, rows (i, j, plane) -- is RIGHT-aligned in states[b, k]: rows
+        cap-1-counts[b,k] .. cap-2, and row cap-1 holds (number of path cells, i, j of the first one), (0, -1, -1) for an empty
+        sample; rows in front of the list are unspecified.  ends: the end cell and its plane, (-1, -1, -1) for an empty sample.
+        visits: how many of the K paths pass through each cell; opens / extends: how many of them open / extend a gap into it."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        if not (want_states or want_visits or want_opens or want_extends or want_ends):
+            raise ValueError("affine_local_sample_paths: nothing asked for (want_states, want_visits, want_opens, want_extends, want_ends)")
+        check_args(state, torch.float32, (B,), True, Vt=Vt)
+        check_args(state, torch.float32, (B, N, M), True, ValueError, cdf=cdf)
+        check_args(state, torch.float32, (B, N + 1), True, ValueError, rows=rows)
+        lens = self._lens(lens, B, state.device)
+        states = counts = ends = None
+        if want_states:
+            cap = self.lib.sdp_traceback_capacity(N, M)
+            states = torch.empty((B, int(K), cap, 3), dtype=torch.int32, device=state.device)
+            counts = torch.empty((B, int(K)), dtype=torch.int32, device=state.device)
+        visits, opens, extends = (torch.zeros((B, N, M), dtype=torch.int32, device=state.device) if want else None
+                                  for want in (want_visits, want_opens, want_extends))
+        if want_ends:
+            ends = torch.empty((B, int(K), 3), dtype=torch.int32, device=state.device)
+        self.call("sdp_affine_local_sample_paths_f32", AFFINE_LOCAL_SAMPLE_KERNELS[165], dev, state, Vt, cdf, rows, states, counts, visits,
+                  opens, extends, ends, B, N, M, int(K), int(sample0), int(seed) & 0xffffffffffffffff, lens, 0)
+        return states, counts, visits, opens, extends, ends
+
     # ---- the hard affine-gap local operator (include/sdp.h: sdp_hard_affine_local_*) ------------
     def _hard_affine_variant(self, ymx, waves=True):
         """`variant` of the sdp_hard_affine_local_* entries; waves=False for the walk, which runs one wave per pair."""
@@ -907,6 +954,8 @@ SPARSEMAX_KERNELS = {150: "sdp_sparsemax_fwd_kernel", 151: "sdp_sparsemax_val_ke
 SPARSEMAX_ADJOINT_KERNELS = {154: "sdp_sparsemax_adj_fwd_kernel", 155: "sdp_sparsemax_adj_bwd_kernel"}
 # kernel id (csrc/sdp_affine_local.h) -> symbol of the affine-gap soft local operator's kernels
 AFFINE_LOCAL_KERNELS = {160: "sdp_affine_local_fwd_kernel", 161: "sdp_affine_local_val_kernel", 162: "sdp_affine_local_bwd_kernel"}
+# and of the kernels that sample from its posterior (csrc/sdp_affine_local_sample.h)
+AFFINE_LOCAL_SAMPLE_KERNELS = {164: "sdp_affine_local_tables_kernel", 165: "sdp_affine_local_sample_kernel"}
 # kernel id (csrc/sdp_hard_affine.h) -> symbol of the hard affine-gap local operator's kernels
 HARD_AFFINE_LOCAL_KERNELS = {170: "sdp_hard_affine_local_fwd_kernel", 171: "sdp_hard_affine_local_fwd_t_kernel",
                              172: "sdp_hard_affine_local_val_kernel", 173: "sdp_hard_affine_local_val_t_kernel",

@@ -17,12 +17,17 @@ The hard (max-plus) member of the family is built (include/sdp.h: sdp_hard_affin
 Smith-Waterman (Gotoh) alignment -- AffineLocalDecoder.optimal_paths / optimal_alignments / optimal_score on every decoder, and
 AffineLocalDecoder(operator="hardmax"), whose forward is the max-plus score with the path's indicator matrices as subgradients.
 
-Out of scope, none of it built: the second order (differentiating a gradient raises), sampling from the posterior, float64, the
-`distributed` wrappers and `search_scores` (its score(theta, A, lengths) protocol has two tensors, this operator three).
+Sampling from the posterior the soft operator defines is built as well (include/sdp.h: sdp_affine_local_end_tables_f32,
+sdp_affine_local_sample_paths_f32): AffineLocalDecoder.sample_paths / sample_alignments, on every decoder; only
+sampling a problem that is swept transposed is out of scope.
+
+Out of scope, none of it built: the second order (differentiating a gradient raises), float64, the `distributed` wrappers and
+`search_scores` (its score(theta, A, lengths) protocol has two tensors, this operator three).
 """
 import torch
 
 from . import _engine
+from .local import left_aligned
 
 
 def _validate(theta, gap_open, gap_extend):
@@ -143,7 +148,8 @@ class AffineLocalDecoder(torch.nn.Module):
     that open / extend; only the ones asked for are computed); decode returns the path's indicator matrix; score is
     optimal_score.  Any other string: ValueError.
     optimal_paths / optimal_alignments / optimal_score: the optimal alignment itself, on every decoder whatever its operator.
-    Not built: the second order, sampling, float64, `distributed`, `search_scores` (a two-tensor protocol)."""
+    sample_paths / sample_alignments: alignments drawn from the soft operator's posterior, on every decoder whatever its operator.
+    Not built: the second order, float64, `distributed`, `search_scores` (a two-tensor protocol)."""
 
     def __init__(self, operator="softmax"):
         super().__init__()
@@ -221,3 +227,47 @@ class AffineLocalDecoder(torch.nn.Module):
             if transposed:   # (j, i) and the other gap plane; no end stays (-1, -1, -1)
                 ends = torch.stack([ends[:, 1], ends[:, 0], torch.where(ends[:, 2] < 0, ends[:, 2], 2 - ends[:, 2])], dim=1).contiguous()
         return Vt, ends
+
+    def sample_paths(self, theta, gap_open, gap_extend, num_samples, lengths=None, seed=0, sample0=0, return_visits=False,
+                     return_gaps=False, return_ends=False):
+        """Local alignments drawn from the POSTERIOR the soft operator defines -- the empty alignment with probability exp(-Vt), a
+        path with exp(score - Vt); decode() of the softmax decoder returns its marginals, optimal_paths() its mode -- from one
+        forward sweep, the end-cell tables and one walk per sample (include/sdp.h: sdp_affine_local_end_tables_f32,
+        sdp_affine_local_sample_paths_f32; no backward sweep).  Available whatever the operator.  -> (Vt (B,), states
+        (B, K, cap, 3) int32, counts (B, K) int32[, visits (B, N, M) int32][, opens, extends (B, N, M) int32][, ends (B, K, 3)
+        int32]), K = num_samples, device tensors without an autograd graph: sample k of pair b is states[b, k, :counts[b, k]], rows
+        (i, j, plane), the path alone, start first, in the format of optimal_paths() (rows between the list and the last one are
+        unspecified); states[b, k, cap - 1] is (number of path cells, i, j of the first one), (0, -1, -1) for an empty sample, which
+        has counts = 0.  The start cell carries plane m (1).  visits: how many of the K paths pass through each cell; opens /
+        extends (return_gaps): how many of them enter it through a gap step that opens / extends a gap -- over K they estimate E,
+        GO and GX for Et = 1.  ends: the end cell and its plane, (-1, -1, -1) for an empty sample, as
+        optimal_score(return_ends=True) returns them.
+        The draws are reproducible: sample k is sample number sample0 + k of pair b under `seed` (a counter-based generator: 64
+        samples at sample0 = 0 are 32 at 0 followed by 32 at 32).
+        Problems wider than the column limit are swept transposed by forward() and decode(); sampling them is NOT built (the draw
+        must not depend on the sweep direction): ValueError."""
+        _validate(theta, gap_open, gap_extend)
+        K = int(num_samples)
+        if K < 1:
+            raise ValueError(f"num_samples must be positive, got {num_samples}")
+        eng = _engine.get_engine()
+        if theta.shape[2] > eng.max_cols():
+            raise ValueError(f"sample_paths is out of scope for problems swept transposed (M = {theta.shape[2]} exceeds the column "
+                             f"limit {eng.max_cols()}): sampling on a transposed state is not built")
+        with torch.no_grad():
+            shape = tuple(theta.shape)
+            Vt, state = eng.affine_local_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths)
+            cdf, rows = eng.affine_local_end_tables(state, Vt, shape, lengths)
+            states, counts, visits, opens, extends, ends = eng.affine_local_sample_paths(
+                state, Vt, cdf, rows, shape, K, lengths, seed=seed, sample0=sample0, want_visits=bool(return_visits),
+                want_opens=bool(return_gaps), want_extends=bool(return_gaps), want_ends=bool(return_ends))
+            states = left_aligned(states, counts)
+        return ((Vt, states, counts) + ((visits,) if return_visits else ()) + ((opens, extends) if return_gaps else ())
+                + ((ends,) if return_ends else ()))
+
+    def sample_alignments(self, theta, gap_open, gap_extend, num_samples, lengths=None, seed=0, sample0=0):
+        """sample_paths() as lists: (Vt, list of B lists of K lists of (i, j, plane)); an empty sample is an empty list."""
+        Vt, states, counts = self.sample_paths(theta, gap_open, gap_extend, num_samples, lengths, seed, sample0)
+        states, counts = states.cpu().numpy(), counts.cpu().numpy()
+        return Vt, [[[tuple(int(v) for v in row) for row in states[b, k, :counts[b, k]]] for k in range(counts.shape[1])]
+                    for b in range(counts.shape[0])]

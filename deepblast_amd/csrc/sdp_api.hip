@@ -18,6 +18,7 @@
 #include "sdp_soft_local_sample.h"
 #include "sdp_sparsemax.h"
 #include "sdp_affine_local.h"
+#include "sdp_affine_local_sample.h"
 #include "sdp_hard_affine.h"
 #include "sdp_kernels.h"
 
@@ -794,6 +795,9 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_affine_local::ID_FWD: return "sdp_affine_local_fwd_kernel";
     case sdp_affine_local::ID_VAL: return "sdp_affine_local_val_kernel";
     case sdp_affine_local::ID_BWD: return "sdp_affine_local_bwd_kernel";
+    // sampling from its posterior (csrc/sdp_affine_local_sample.hip)
+    case sdp_affine_local_sample::ID_TABLES: return "sdp_affine_local_tables_kernel";
+    case sdp_affine_local_sample::ID_SAMPLE: return "sdp_affine_local_sample_kernel";
     // the hard affine-gap local operator (csrc/sdp_hard_affine.hip)
     case sdp_hard_affine::ID_FWD: return "sdp_hard_affine_local_fwd_kernel";
     case sdp_hard_affine::ID_FWD_T: return "sdp_hard_affine_local_fwd_t_kernel";
@@ -1686,6 +1690,45 @@ int sdp_affine_local_backward_f32(const void *state, const float *Vt, const floa
     const int W = sdp_affine_local::waves_for(N, M);
     return strip_launch(sdp_affine_local_bwd_kernel, "sdp_affine_local_bwd_kernel", B, W, sdp_affine_local::sweep_lds_bytes(W, M), stream,
                         static_cast<const float4 *>(state), Vt, Et, E, GO, GX, lens, N, M, W);
+}
+
+// ---- alignments sampled from its posterior (csrc/sdp_affine_local_sample.hip): the end-cell tables, then one walk per sample ----
+static_assert(sdp_affine_local_sample::LANES == sdp_soft_local_sample::LANES, "the two samplers launch the same workgroups");
+int sdp_affine_local_end_tables_f32(const void *state, const float *Vt, float *cdf, float *rows, int B, int N, int M, const int32_t *lens,
+                                    int flags, int device, void *stream)
+{
+    if (!state || !Vt || !cdf || !rows) return fail(SDP_E_NULLPTR, "sdp_affine_local_end_tables_f32: null pointer (state, Vt, cdf, rows)");
+    if (int rc = affine_local_args(B, N, M, flags)) return rc;
+    if (int rc = use_device(device)) return rc;
+    // cdf by one wave per (pair, strip); then, behind it on the stream, rows by one wave per pair
+    const unsigned waves = (unsigned)B * (unsigned)sdp_affine_local::strips(N);   // <= B N <= 2^31 / M
+    for (int pass = 0; pass < 2; ++pass)
+        if (int rc = strip_launch(sdp_affine_local_tables_kernel, "sdp_affine_local_tables_kernel", pass ? (unsigned)B : waves, SAMPLE_WAVES,
+                                  0, stream, static_cast<const float4 *>(state), Vt, cdf, rows, lens, N, M, pass))
+            return rc;
+    return 0;
+}
+
+int sdp_affine_local_sample_paths_f32(const void *state, const float *Vt, const float *cdf, const float *rows, int32_t *states,
+                                      int32_t *counts, int32_t *visits, int32_t *opens, int32_t *extends, int32_t *ends, int B, int N,
+                                      int M, int K, int sample0, uint64_t seed, const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!state || !Vt || !cdf || !rows || (states && !counts) || (!states && !counts && !visits && !opens && !extends && !ends))
+        return fail(SDP_E_NULLPTR, "sdp_affine_local_sample_paths_f32: null pointer (state, Vt, cdf, rows; states with counts, or visits, "
+                                   "or opens, or extends, or ends)");
+    if (int rc = affine_local_args(B, N, M, flags)) return rc;
+    if (K < 1 || sample0 < 0 || (long long)sample0 + K > 0x7fffffffLL)
+        return fail(SDP_E_SHAPE, "sdp_affine_local_sample_paths_f32: K must be positive, sample0 non-negative and sample0 + K below 2^31");
+    const int cap = sdp_traceback_capacity(N, M);
+    const size_t lim = 0x7fffffffu, waves = (size_t)B * ((K + sdp_affine_local_sample::LANES - 1) / sdp_affine_local_sample::LANES);
+    if ((states && (size_t)B * K * cap * 3 > lim) || (size_t)B * K * 3 > lim || waves > lim)
+        return fail(SDP_E_TOOBIG, "sdp_affine_local_sample_paths_f32: an output exceeds 2^31 elements");
+    if (int rc = use_device(device)) return rc;
+    sdp_affine_local_sample::Params g = {};
+    g.state = static_cast<const float4 *>(state), g.Vt = Vt, g.cdf = cdf, g.rows = rows;
+    g.states = states, g.counts = counts, g.visits = visits, g.opens = opens, g.extends = extends, g.ends = ends, g.lens = lens;
+    g.seed = seed, g.B = B, g.N = N, g.M = M, g.K = K, g.sample0 = sample0, g.cap = cap;
+    return strip_launch(sdp_affine_local_sample_kernel, "sdp_affine_local_sample_kernel", (unsigned)waves, SAMPLE_WAVES, 0, stream, g);
 }
 
 // ---- the hard affine-gap local operator (csrc/sdp_hard_affine.hip): the max-plus member of the affine family ----

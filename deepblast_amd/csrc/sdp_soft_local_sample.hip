@@ -13,7 +13,8 @@
 //             totals are loaded 64 at a time, the adds are sequential in i (a readlane per row).  No floating-point atomics: the
 //             same bits on every call, and both tables are non-decreasing by construction.
 //   sample    lane = sample, one wave = 64 samples of a pair, grid B x ceil(K / 64), as csrc/sdp_sample.hip.  Two binary searches
-//             for the end cell -- each returns the FIRST index whose entry exceeds the scaled uniform, which is what a linear scan
+//             for the end cell (first_above, csrc/sdp_strip_device.h, shared with csrc/sdp_affine_local_sample.hip like pass 1 of
+//             the tables) -- each returns the FIRST index whose entry exceeds the scaled uniform, which is what a linear scan
 //             returns because the tables never decrease -- then one 16-byte gather per step.  The records have q = 0 towards
 //             anything outside the table, so the walk stays inside the block; the loop also ends at the block's edge, so that a
 //             state that is not one reads nothing out of bounds.
@@ -29,20 +30,6 @@ namespace {
 
 using namespace sdp_soft_local;
 static_assert(STRIP == sdp_strip::STRIP && CHUNK == sdp_strip::CHUNK, "csrc/sdp_soft_local.h and csrc/sdp_strip_device.h disagree");
-
-// the first index i in [0, count) with x < a[i], or count - 1 if there is none; a non-decreasing (count >= 1)
-__device__ __forceinline__ int first_above(const float *a, int count, float x)
-{
-    int lo = 0, hi = count;   // every index below lo has a[i] <= x, every index from hi on (if any) has x < a[i]
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (x < a[mid])
-            hi = mid;
-        else
-            lo = mid + 1;
-    }
-    return lo < count ? lo : count - 1;
-}
 
 }  // namespace
 
@@ -64,20 +51,7 @@ extern "C" __global__ void __launch_bounds__(sdp_soft_local_sample::LANES) sdp_s
     const float vt = Vt[b];
 
     if (pass) {
-        float *out = rows + (size_t)b * (N + 1);
-        float acc = expf(-vt);
-        if (lane == 0) out[0] = acc;
-        for (int base = 0; base < n; base += STRIP) {
-            const int r = base + lane;
-            const float tot = r < n ? cdf[plane + (size_t)r * M + (m - 1)] : 0.f;   // (+ 0 behind the last row: nothing reads it)
-            float mine = 0.f;
-#pragma unroll 4
-            for (int l = 0; l < STRIP; ++l) {   // (a chain of adds: unrolled in full it only keeps 64 totals in scalar registers)
-                acc = acc + of_lane(tot, l);
-                mine = (lane == l) ? acc : mine;
-            }
-            if (r < n) out[r + 1] = mine;
-        }
+        running_row_totals(cdf + plane, M, n, m, expf(-vt), rows + (size_t)b * (N + 1), lane);
         return;
     }
 

@@ -1,6 +1,6 @@
 // sdp_strip_device.h -- device helpers of the strip schedule, one copy for every kernel file
 // that sweeps on it: the lane moves, the unaligned four-float access, and the loads and stores that move a lane's run of
-// consecutive steps.  For .hip files only (internal linkage: every including file has its own copy).
+// consecutive steps, and what the two samplers' end-cell tables share.  For .hip files only (internal linkage: every including file has its own copy).
 #ifndef SDP_STRIP_DEVICE_H_
 #define SDP_STRIP_DEVICE_H_
 
@@ -134,6 +134,42 @@ __device__ __forceinline__ void lse_join(float &m0, float &s0, float m1, float s
     const float e0 = m0 == mx ? 1.f : expf(m0 - mx), e1 = m1 == mx ? 1.f : expf(m1 - mx);
     s0 = s0 * e0 + s1 * e1;
     m0 = mx;
+}
+
+// ---- the end-cell tables of the samplers (csrc/sdp_soft_local_sample.hip, csrc/sdp_affine_local_sample.hip) ----
+
+// the first index i in [0, count) with x < a[i], or count - 1 if there is none; a non-decreasing (count >= 1)
+__device__ __forceinline__ int first_above(const float *a, int count, float x)
+{
+    int lo = 0, hi = count;   // every index below lo has a[i] <= x, every index from hi on (if any) has x < a[i]
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (x < a[mid])
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    return lo < count ? lo : count - 1;
+}
+
+// one wave: out[0] = first, out[i + 1] = out[i] + cdf[i, m - 1] for the n rows of a pair's (.., M) plane `cdf` -- the totals are
+// loaded 64 at a time, the adds are sequential in i (a readlane per row)
+__device__ __forceinline__ void running_row_totals(const float *cdf, int M, int n, int m, float first, float *out, int lane)
+{
+    using namespace sdp_strip;
+    float acc = first;
+    if (lane == 0) out[0] = acc;
+    for (int base = 0; base < n; base += STRIP) {
+        const int r = base + lane;
+        const float tot = r < n ? cdf[(size_t)r * M + (m - 1)] : 0.f;   // (+ 0 behind the last row: nothing reads it)
+        float mine = 0.f;
+#pragma unroll 4
+        for (int l = 0; l < STRIP; ++l) {   // (a chain of adds: unrolled in full it only keeps 64 totals in scalar registers)
+            acc = acc + of_lane(tot, l);
+            mine = (lane == l) ? acc : mine;
+        }
+        if (r < n) out[r + 1] = mine;
+    }
 }
 
 }  // namespace

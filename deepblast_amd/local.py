@@ -24,6 +24,17 @@ def _validate(theta, A):
         raise ValueError(f"theta and A must both be (B, N, M), got {tuple(theta.shape)} and {tuple(A.shape)}")
 
 
+def left_aligned(states, counts):
+    """states (B, K, cap, 3) as a sampling kernel leaves them -- the list of sample (b, k) RIGHT-aligned in rows
+    cap-1-counts[b,k] .. cap-2 (every sample wrote from the end) -> the lists at rows 0 .. counts[b,k]-1: one gather, the last
+    row stays, the rows between hold a copy of it"""
+    cap = states.shape[2]
+    row = torch.arange(cap, device=states.device)[None, None, :]
+    cnt = counts.long()[..., None]
+    src = torch.where(row < cnt, row + (cap - 1 - cnt), torch.full_like(row, cap - 1))
+    return torch.gather(states, 2, src[..., None].expand(-1, -1, -1, 3))
+
+
 class SoftLocalFunctionBackward(torch.autograd.Function):
     """(E, G) of the mirror sweep.  Differentiable in nothing: this is the node at which a second differentiation stops -- what
     @once_differentiable does, with a message that names the reason."""
@@ -191,12 +202,7 @@ class SoftLocalDecoder(torch.nn.Module):
             cdf, rows = eng.soft_local_end_tables(state, Vt, shape, lengths)
             states, counts, visits, ends = eng.soft_local_sample_paths(state, cdf, rows, shape, K, lengths, seed=seed, sample0=sample0,
                                                                        want_visits=bool(return_visits), want_ends=bool(return_ends))
-            # the lists come right-aligned (every sample wrote from the end): one gather moves them to the front, the last row stays
-            cap = states.shape[2]
-            row = torch.arange(cap, device=states.device)[None, None, :]
-            cnt = counts.long()[..., None]
-            src = torch.where(row < cnt, row + (cap - 1 - cnt), torch.full_like(row, cap - 1))
-            states = torch.gather(states, 2, src[..., None].expand(-1, -1, -1, 3))
+            states = left_aligned(states, counts)
         return (Vt, states, counts) + ((visits,) if return_visits else ()) + ((ends,) if return_ends else ())
 
     def sample_alignments(self, theta, A, num_samples, lengths=None, seed=0, sample0=0):

@@ -651,8 +651,9 @@ int sdp_sparsemax_adjoint_backward_f32(const void *state, const void *state_d, c
  * exactly 0 there, and nothing is NaN when every gap is forbidden).  E, GO and GX are +0 by bit pattern outside the pair's [:n, :m]
  * block (the backward kernel writes them: no extra launch); a pair with n < 1 or m < 1 has Vt = 0 and all gradients 0.  fp32 only.
  * No floating-point atomics: two calls on the same inputs give the same bits, and sdp_affine_local_forward_value_f32 gives the bits
- * of sdp_affine_local_forward_f32's Vt.  NOT built: the second order, sampling, float64.  The hard (max-plus) member of the family is
- * sdp_hard_affine_local_* below.
+ * of sdp_affine_local_forward_f32's Vt.  NOT built: the second order, float64.  Sampling from the posterior is
+ * sdp_affine_local_end_tables_f32 / sdp_affine_local_sample_paths_f32 below; the hard (max-plus) member of the family is
+ * sdp_hard_affine_local_* after them.
  *   state    sdp_affine_local_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: 48 bytes per cell -- one record
  *            {q[s<-x], q[s<-m], q[s<-y], V_s} per plane s -- in a private layout; written by sdp_affine_local_forward_f32, read by
  *            sdp_affine_local_backward_f32 with the same B, N, M, lens (which needs neither theta, O nor X).  Only records of cells
@@ -671,6 +672,65 @@ int sdp_affine_local_forward_value_f32(const float *theta, const float *gap_open
                                        const int32_t *lens, int flags, int device, void *stream);
 int sdp_affine_local_backward_f32(const void *state, const float *Vt, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
                                   const int32_t *lens, int flags, int device, void *stream);
+
+/* Alignments SAMPLED from its posterior (csrc/sdp_affine_local_sample.hip): what sdp_soft_local_sample_paths_f32 is
+ * to the soft local operator.  (Added after SDP_VERSION 106 without a version change: look the symbols up.  sdp_kernel_name answers
+ * 164 and 165 for their kernels.)  The empty alignment has probability exp(-Vt), a path exp(score - Vt); E, GO and GX over Et are
+ * the marginals of "the path passes through the cell", "opens a gap into it" and "extends a gap into it".
+ * Planes x, m, y = 0, 1, 2.  (n, m) = lens[b] clamped to [0, N] x [0, M], or (N, M); cells 0-based; U(seed, pair, sample, t) the
+ * generator of sdp_sample_paths_* (sdp_sample_uniform is its host twin); the sample number of sample k is sample0 + k.
+ * TABLES (sdp_affine_local_end_tables_f32, from the state and the Vt that sdp_affine_local_forward_f32 wrote), row-major float32:
+ *     cdf (B, N, M)    the running sum along row i of ws[i,j] = (expf(Vx - Vt) + expf(Vy - Vt)) + expf(Vm - Vt), in exactly this order
+ *                      of adds; the sums are sequential fp32 adds in increasing j
+ *     rows (B, N + 1)  rows[0] = expf(-Vt);  rows[i+1] = rows[i] + cdf[i, m-1], by sequential fp32 adds
+ * Everything else as in sdp_soft_local_end_tables_f32: both tables are non-decreasing by construction; only entries inside the
+ * pair's block are written -- cdf: i < n and j < m; rows: index <= n; a pair with n < 1 or m < 1 has rows[0] = 1 and nothing else;
+ * no floating-point atomics, the same bits on every call.
+ * END CELL: t = 0 and t = 1 exactly as in the soft local sampler -- g = U(.., 0) * rows[n], the EMPTY alignment if g < rows[0],
+ * else i the first row with g < rows[i+1], or n - 1 if there is none; h = U(.., 1) * cdf[i, m-1], j the first column with
+ * h < cdf[i, j], or m - 1 if there is none.
+ * END PLANE, t = 2: wx, wy, wm of the end cell by the same fp32 expressions (which is why the sample entry takes Vt), then
+ * p = U(.., 2) * ((wx + wy) + wm) and
+ *     p < wx                   plane x
+ *     else p < wx + wy         plane y
+ *     else                     plane m
+ * The fall-through is m on purpose: plane m always holds a finite value and a valid record, and neither test before it can choose
+ * a plane of weight 0.
+ * WALK, t = 3, 4, ...: at (i, j, s), with that plane's record {q[s<-x], q[s<-m], q[s<-y], V_s} and u = U(.., t).  The predecessor
+ * CELL is (i-1, j) for s = x, (i-1, j-1) for s = m, (i, j-1) for s = y; the predecessor's PLANE is
+ *     u < q[s<-x]                                  x
+ *     else u < q[s<-x] + q[s<-y]  (one fp32 add)   y
+ *     else, for s = m:   u < (q[s<-x] + q[s<-y]) + q[s<-m]  m;  otherwise the walk STOPS: this cell is the alignment's start, and
+ *                        it is recorded as plane m
+ *     else, for s = x or y:  there is no stop here -- the weights sum to 1 up to rounding -- and the choice is the last of m, y, x
+ *                        whose weight is non-zero: m if q[s<-m] > 0, else y if q[s<-y] > 0, else x
+ * So a predecessor of weight exactly 0 -- a forbidden opening or extension, anything outside the block, a plane that is -inf -- is
+ * never chosen: by induction the walk never stands in a -inf plane and never leaves the block.  (The kernel still ends a walk at
+ * the block's edge: a buffer that is not a state is not read out of bounds.)  Every step lowers i or j: at most n + m - 1 cells.
+ * NaN weights: unspecified.
+ * OUTPUTS, each nullable; if nothing is asked for, SDP_E_NULLPTR:
+ *   states   (B, K, cap, 3) int32, cap = sdp_traceback_capacity(N, M), and counts (B, K) (required with states), in the format of
+ *            the soft local sampler: the path alone, start first, RIGHT-aligned -- rows cap-1-counts[b,k] .. cap-2; row cap-1 holds
+ *            (number of path cells, i, j of the first cell), (0, -1, -1) for an empty sample; rows in front of the list are not
+ *            written.  Each row is (i, j, plane), the plane as in sdp_hard_affine_local_walk_f32: how the cell was entered, m for
+ *            the start.
+ *   ends     (B, K, 3) int32: (i, j, plane) of the end, (-1, -1, -1) for an empty sample.
+ *   visits, opens, extends   (B, N, M) int32, incremented by no-return integer atomic adds -- the caller zeroes them; the result is
+ *            deterministic.  visits: + 1 per path cell; opens: + 1 on a path cell in plane x or y whose predecessor on the path is
+ *            in a different plane; extends: + 1 where it is in the same plane.  Over K they estimate E, GO and GX for Et = 1.
+ * The same call twice gives the same tensors, and K = 64 at sample0 = 0 equals 32 at 0 joined with 32 at 32.
+ *   state, Vt  what sdp_affine_local_forward_f32 wrote; cdf, rows: what sdp_affine_local_end_tables_f32 wrote from them; the same
+ *              B, N, M, lens throughout.
+ *   flags    none is defined: any bit is refused (SDP_E_VARIANT).
+ * K >= 1 and sample0 >= 0 (and sample0 + K < 2^31), else SDP_E_SHAPE; an output of more than 2^31 - 1 elements: SDP_E_TOOBIG; M
+ * above sdp_max_cols(): SDP_E_MAXCOLS.  All arguments are checked before any device call.  Tables: one wave per strip of 64 rows,
+ * then one per pair; samples: one wave per 64 samples of a pair.  A problem that was swept TRANSPOSED is out of scope, as in the
+ * soft local sampler. */
+int sdp_affine_local_end_tables_f32(const void *state, const float *Vt, float *cdf, float *rows, int B, int N, int M, const int32_t *lens,
+                                    int flags, int device, void *stream);
+int sdp_affine_local_sample_paths_f32(const void *state, const float *Vt, const float *cdf, const float *rows, int32_t *states,
+                                      int32_t *counts, int32_t *visits, int32_t *opens, int32_t *extends, int32_t *ends, int B, int N,
+                                      int M, int K, int sample0, uint64_t seed, const int32_t *lens, int flags, int device, void *stream);
 
 /* The HARD AFFINE-GAP LOCAL operator (csrc/sdp_hard_affine.hip): the max-plus member of the affine family above, as
  * sdp_hard_local_* is of the one-score family -- the optimal affine-gap Smith-Waterman (Gotoh) alignment of every pair, its score,
