@@ -745,6 +745,44 @@ class HipEngine:
         self.call("sdp_affine_local_backward_f32", AFFINE_LOCAL_KERNELS[162], dev, state, Vt, Et, E, GO, GX, B, N, M, lens, 0)
         return E, GO, GX
 
+    def affine_local_adjoint_forward(self, state, Vt, ZE, ZGO, ZGX, shape, lens=None, state_d_out=None):
+        """The adjoint forward sweep over the records of affine_local_forward -> (Vtd (B,), state_d): ZE, ZGO, ZGX (B,N,M) the
+        cotangents of E, GO and GX, each may be None (zeros) but not all three; state_d the dot records (opaque float32 tensor of
+        sdp_affine_local_adjoint_state_bytes; state_d_out: a buffer of that size to write into instead of a fresh one)."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        if ZE is None and ZGO is None and ZGX is None:
+            raise ValueError("affine_local_adjoint_forward: ZE, ZGO and ZGX are all None")
+        check_args(state, torch.float32, (B,), True, Vt=Vt)
+        check_args(state, torch.float32, (B, N, M), ZE=ZE, ZGO=ZGO, ZGX=ZGX)
+        ZE, ZGO, ZGX = (None if z is None else z.detach().contiguous() for z in (ZE, ZGO, ZGX))
+        lens = self._lens(lens, B, state.device)
+        nfloats = max(self.lib.sdp_affine_local_adjoint_state_bytes(B, N, M), 4) // 4
+        check_args(state, torch.float32, (nfloats,), True, ValueError, state_d_out=state_d_out)
+        state_d = torch.empty(nfloats, dtype=torch.float32, device=state.device) if state_d_out is None else state_d_out
+        Vtd = torch.empty(B, dtype=torch.float32, device=state.device)
+        self.call("sdp_affine_local_adjoint_forward_f32", AFFINE_LOCAL_ADJOINT_KERNELS[167], dev, state, Vt, ZE, ZGO, ZGX, state_d, Vtd,
+                  B, N, M, lens, 0)
+        return Vtd, state_d
+
+    def affine_local_adjoint_backward(self, state, state_d, Vt, Vtd, Et, shape, lens=None, want_GO=True, want_GX=True):
+        """The adjoint mirror sweep -> (Ed (B,N,M), GOd (B,N,M) or None, GXd (B,N,M) or None): the gradients of <ZE,E> + <ZGO,GO> +
+        <ZGX,GX> with respect to theta, gap_open and gap_extend, +0 outside each pair's block.  state, Vt: of affine_local_forward;
+        state_d, Vtd: of affine_local_adjoint_forward; Et: what affine_local_backward was given."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        check_args(state, torch.float32, (B,), True, Vt=Vt, Vtd=Vtd)
+        check_args(state, torch.float32, None, True, state_d=state_d)
+        check_args(state, Et=Et)
+        Et = Et.detach().to(torch.float32).expand(B).contiguous()
+        lens = self._lens(lens, B, state.device)
+        Ed = torch.empty((B, N, M), dtype=torch.float32, device=state.device)
+        GOd = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if want_GO else None
+        GXd = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if want_GX else None
+        self.call("sdp_affine_local_adjoint_backward_f32", AFFINE_LOCAL_ADJOINT_KERNELS[168], dev, state, state_d, Vt, Vtd, Et, Ed, GOd,
+                  GXd, B, N, M, lens, 0)
+        return Ed, GOd, GXd
+
     # ---- alignments sampled from its posterior (include/sdp.h: sdp_affine_local_end_tables_f32, sdp_affine_local_sample_paths_f32) ----
     def affine_local_end_tables(self, state, Vt, shape, lens=None, cdf_out=None, rows_out=None):
         """The end-cell tables over the records of affine_local_forward -> (cdf (B,N,M), rows (B,N+1)) fp32: the running sums of
@@ -954,6 +992,8 @@ SPARSEMAX_KERNELS = {150: "sdp_sparsemax_fwd_kernel", 151: "sdp_sparsemax_val_ke
 SPARSEMAX_ADJOINT_KERNELS = {154: "sdp_sparsemax_adj_fwd_kernel", 155: "sdp_sparsemax_adj_bwd_kernel"}
 # kernel id (csrc/sdp_affine_local.h) -> symbol of the affine-gap soft local operator's kernels
 AFFINE_LOCAL_KERNELS = {160: "sdp_affine_local_fwd_kernel", 161: "sdp_affine_local_val_kernel", 162: "sdp_affine_local_bwd_kernel"}
+# of its adjoint pair (the same header)
+AFFINE_LOCAL_ADJOINT_KERNELS = {167: "sdp_affine_local_adj_fwd_kernel", 168: "sdp_affine_local_adj_bwd_kernel"}
 # and of the kernels that sample from its posterior (csrc/sdp_affine_local_sample.h)
 AFFINE_LOCAL_SAMPLE_KERNELS = {164: "sdp_affine_local_tables_kernel", 165: "sdp_affine_local_sample_kernel"}
 # kernel id (csrc/sdp_hard_affine.h) -> symbol of the hard affine-gap local operator's kernels

@@ -21,8 +21,12 @@ Sampling from the posterior the soft operator defines is built as well (include/
 sdp_affine_local_sample_paths_f32): AffineLocalDecoder.sample_paths / sample_alignments, on every decoder; only
 sampling a problem that is swept transposed is out of scope.
 
-Out of scope, none of it built: the second order (differentiating a gradient raises), float64, the `distributed` wrappers and
-`search_scores` (its score(theta, A, lengths) protocol has two tensors, this operator three).
+The second order is opt-in (`second_order=True`): forward() is then differentiable twice and decode() returns E with a graph,
+through the adjoint pair (include/sdp.h: sdp_affine_local_adjoint_*), so that a loss on the alignment matrix trains
+theta, gap_open and gap_extend -- loss(first, dec.decode(theta, gap_open, gap_extend, lengths), x_len, y_len, G).backward().
+
+Out of scope, none of it built: the third order, float64, the `distributed` wrappers, `search_scores` and `losses.decode_loss`
+(their protocols have two tensors, this operator three).
 """
 import torch
 
@@ -71,22 +75,76 @@ class AffineLocalFunctionBackward(torch.autograd.Function):
                                   "sdp_affine_local_*) is not built")
 
 
-class AffineLocalFunction(torch.autograd.Function):
-    """Vt = affine_local(theta, gap_open, gap_extend); backward: theta.grad = E, gap_open.grad = GO, gap_extend.grad = GX, one mirror
-    sweep; GO and GX are computed only when their input needs a gradient.  Once differentiable."""
+class AffineLocalAdjoint(torch.autograd.Function):
+    """(Ed, GOd, GXd, Vtd) of the adjoint pair (include/sdp.h: sdp_affine_local_adjoint_*): the gradients of <ZE, E> + <ZGO, GO> +
+    <ZGX, GX> with respect to theta, gap_open, gap_extend and Et.  Differentiable in nothing: the third order is not built, and
+    this is the node that says so."""
 
     @staticmethod
-    def forward(ctx, theta, gap_open, gap_extend, lens=None):
+    def forward(ctx, theta, gap_open, gap_extend, Et, ZE, ZGO, ZGX, state, Vt, lens, want_GO, want_GX):
+        # (the inputs and the cotangents are here for the graph: a third differentiation must arrive below)
+        eng = _engine.get_engine()
+        shape = tuple(theta.shape)
+        Vtd, state_d = eng.affine_local_adjoint_forward(state, Vt, ZE, ZGO, ZGX, shape, lens)
+        Ed, GOd, GXd = eng.affine_local_adjoint_backward(state, state_d, Vt, Vtd, Et, shape, lens, want_GO=want_GO, want_GX=want_GX)
+        return Ed, GOd, GXd, Vtd
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError("the affine-gap soft local operator is second order only: its third order (the derivative of the "
+                                  "adjoint pair sdp_affine_local_adjoint_*) is not built")
+
+
+class AffineLocalFunctionBackward2(torch.autograd.Function):
+    """AffineLocalFunctionBackward for AffineLocalDecoder(second_order=True): the same (E, GO, GX), differentiable once more through
+    the adjoint pair.  backward(ZE, ZGO, ZGX) -> the gradients of <ZE, E> + <ZGO, GO> + <ZGX, GX>: Ed for theta, GOd for gap_open,
+    GXd for gap_extend, Vtd for Et; only the outputs whose input needs a gradient are asked for."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, Et, state, Vt, lens, want_E, want_GO, want_GX):
+        E, GO, GX = _engine.get_engine().affine_local_backward(state, Vt, Et, tuple(theta.shape), lens, want_GO=want_GO, want_GX=want_GX)
+        ctx.save_for_backward(theta, gap_open, gap_extend, Et, state, Vt)
+        ctx.lens = lens
+        ctx.set_materialize_grads(False)
+        return (E if want_E else None), GO, GX
+
+    @staticmethod
+    def backward(ctx, ZE, ZGO, ZGX):
+        theta, gap_open, gap_extend, Et, state, Vt = ctx.saved_tensors
+        none = (None,) * 6
+        if ZE is None and ZGO is None and ZGX is None:
+            return (None, None, None, None) + none
+        need = ctx.needs_input_grad
+        Ed, GOd, GXd, Vtd = AffineLocalAdjoint.apply(theta, gap_open, gap_extend, Et, ZE, ZGO, ZGX, state, Vt, ctx.lens, need[1], need[2])
+        if Vtd.shape != Et.shape:       # Et was broadcast over the batch
+            Vtd = Vtd.sum_to_size(Et.shape)
+        return (Ed if need[0] else None, GOd, GXd, Vtd if need[3] else None) + none
+
+
+class AffineLocalFunction(torch.autograd.Function):
+    """Vt = affine_local(theta, gap_open, gap_extend); backward: theta.grad = E, gap_open.grad = GO, gap_extend.grad = GX, one mirror
+    sweep; GO and GX are computed only when their input needs a gradient.  Once differentiable: differentiating E, GO or GX raises
+    NotImplementedError (AffineLocalFunctionBackward) -- unless second_order is set: they are then differentiable through the
+    adjoint pair (AffineLocalFunctionBackward2), and the third order raises."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, lens=None, second_order=False):
         Vt, state = _engine.get_engine().affine_local_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lens)
         ctx.save_for_backward(theta, gap_open, gap_extend, state, Vt)
         ctx.lens = lens
+        ctx.second_order = second_order
         return Vt
 
     @staticmethod
     def backward(ctx, Et):
         theta, gap_open, gap_extend, state, Vt = ctx.saved_tensors
-        E, GO, GX = AffineLocalFunctionBackward.apply(theta, gap_open, gap_extend, Et, state, Vt, ctx.lens, *ctx.needs_input_grad[:3])
-        return E, GO, GX, None
+        if ctx.second_order:
+            # (Vt detached: the adjoint pair carries the whole derivative, and this node is not to be visited again for it)
+            E, GO, GX = AffineLocalFunctionBackward2.apply(theta, gap_open, gap_extend, Et, state, Vt.detach(), ctx.lens,
+                                                           *ctx.needs_input_grad[:3])
+        else:
+            E, GO, GX = AffineLocalFunctionBackward.apply(theta, gap_open, gap_extend, Et, state, Vt, ctx.lens, *ctx.needs_input_grad[:3])
+        return E, GO, GX, None, None
 
 
 class HardAffineLocalFunctionBackward(torch.autograd.Function):
@@ -133,9 +191,14 @@ class AffineLocalDecoder(torch.nn.Module):
 
     forward(theta, gap_open, gap_extend, lengths=None) -> Vt (B,), differentiable ONCE: theta.grad = E, gap_open.grad = GO,
     gap_extend.grad = GX, all true gradients; GO and GX are computed only when their input needs a gradient.  Differentiating a
-    gradient raises NotImplementedError: the second order is not built.
+    gradient raises NotImplementedError (the second order is not built into the default object), unless second_order is set.
     decode(theta, gap_open, gap_extend, lengths=None) -> E (B, N, M) for Et = 1: E[b, i, j] is the posterior probability that cell
-    (i, j) lies on the alignment of pair b.  No autograd graph.
+    (i, j) lies on the alignment of pair b.  No autograd graph, unless second_order is set.
+    second_order=True (softmax only; with "hardmax": ValueError, the max-plus score is piecewise linear): forward() is
+    differentiable TWICE and decode() returns E with a graph when grad is enabled and an input requires it, so that a loss on the
+    alignment matrix -- loss(first, dec.decode(theta, gap_open, gap_extend, lengths), x_len, y_len, G).backward() -- trains theta,
+    gap_open and gap_extend: the gradients come from the adjoint pair (sdp_affine_local_adjoint_*), true ones for all three; only
+    the ones asked for are computed.  The third order is not built and raises.
     score(theta, gap_open, gap_extend, lengths=None) -> Vt (B,) through the value-only sweep: no state is allocated, no graph.
     theta finite; gap_open and gap_extend finite or -inf (a forbidden opening or extension: the matching gradient is exactly 0
     there).  lengths (B, 2): pair b is theta[b, :n_b, :m_b]; E, GO and GX are +0 outside it, and an empty pair has Vt = 0.
@@ -149,20 +212,25 @@ class AffineLocalDecoder(torch.nn.Module):
     optimal_score.  Any other string: ValueError.
     optimal_paths / optimal_alignments / optimal_score: the optimal alignment itself, on every decoder whatever its operator.
     sample_paths / sample_alignments: alignments drawn from the soft operator's posterior, on every decoder whatever its operator.
-    Not built: the second order, float64, `distributed`, `search_scores` (a two-tensor protocol)."""
+    The second order is opt-in (`second_order=True`); the third order, float64, `distributed`, `search_scores` and
+    `losses.decode_loss` (two-tensor protocols) are not built."""
 
-    def __init__(self, operator="softmax"):
+    def __init__(self, operator="softmax", second_order=False):
         super().__init__()
         if operator not in ("softmax", "hardmax"):
             raise ValueError(f"operator must be 'softmax' or 'hardmax', got {operator!r}")
+        if second_order and operator == "hardmax":
+            raise ValueError("second_order=True needs operator='softmax': the max-plus score of 'hardmax' is piecewise linear, its "
+                             "second derivative is zero wherever it exists")
         self.operator = operator
+        self.second_order = bool(second_order)
 
     def forward(self, theta, gap_open, gap_extend, lengths=None):
         _validate(theta, gap_open, gap_extend)
         theta, gap_open, gap_extend, lengths, transposed = _oriented(theta, gap_open, gap_extend, lengths)
         if self.operator == "hardmax":
             return HardAffineLocalFunction.apply(theta, gap_open, gap_extend, lengths, transposed)
-        return AffineLocalFunction.apply(theta, gap_open, gap_extend, lengths)
+        return AffineLocalFunction.apply(theta, gap_open, gap_extend, lengths, self.second_order)
 
     def decode(self, theta, gap_open, gap_extend, lengths=None):
         _validate(theta, gap_open, gap_extend)
@@ -173,6 +241,12 @@ class AffineLocalDecoder(torch.nn.Module):
                 _, state, ends = eng.hard_affine_local_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths, ymx=transposed)
                 E = eng.hard_affine_local_walk(state, ends, tuple(theta.shape), lengths, ymx=transposed, want_states=False,
                                                Et=torch.ones((), dtype=torch.float32, device=theta.device))[0]
+            return E.transpose(1, 2) if transposed else E
+        if self.second_order and torch.is_grad_enabled() and (theta.requires_grad or gap_open.requires_grad or gap_extend.requires_grad):
+            # E with a graph: the first-order pair outside autograd, then the node the adjoint pair hangs on (Et = 1)
+            Vt, state = eng.affine_local_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths)
+            one = torch.ones(theta.shape[0], dtype=torch.float32, device=theta.device)
+            E, _, _ = AffineLocalFunctionBackward2.apply(theta, gap_open, gap_extend, one, state, Vt, lengths, True, False, False)
             return E.transpose(1, 2) if transposed else E
         with torch.no_grad():
             Vt, state = eng.affine_local_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths)

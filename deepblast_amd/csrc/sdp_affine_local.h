@@ -39,6 +39,28 @@ __host__ __device__ inline size_t pair_cells(int N, int M) { return (size_t)stri
 // kernel ids sdp_kernel_name answers for (159 and 163 answer NULL)
 enum { ID_FWD = 160, ID_VAL = 161, ID_BWD = 162 };
 
+// ---- the second order (csrc/sdp_affine_local_adj.hip): the adjoint pair ----
+constexpr int ADJ_GROUP = 4;     // steps of the adjoint forward sweep's cotangent prefetch and of the adjoint backward sweep's stores
+constexpr int ADJ_PAIR = 2;      // steps of the adjoint sweeps' record prefetch (the backward one's: a record and a dot record per plane, 24 floats a step)
+// the adjoint forward sweep hands the three Vd of a strip's bottom row down: the ring, the budget and the waves of the first order
+// (sweep_lds_bytes, waves_for).  The adjoint backward sweep's ring is twice that: what the top row pushes up into each plane, of Eb
+// and of Ebd, unreduced
+__host__ __device__ inline size_t adjoint_lds_bytes(int waves, int M) { return (size_t)2 * PLANES * waves * row_pitch(M) * 4 + 2 * MAX_WAVES * 4; }
+// waves of the adjoint backward sweep: eight up to M = 789, seven up to 910, six up to 1073, five up to 1300, four up to 1642,
+// three up to the column limit 2048
+__host__ __device__ inline int adjoint_waves_for(int N, int M)
+{
+    int w = strips(N) < MAX_WAVES ? strips(N) : MAX_WAVES;
+    while (w > 1 && adjoint_lds_bytes(w, M) > (size_t)LDS_BUDGET) --w;
+    return w;
+}
+// the record no cell owns -- lane 1 at step 0 of chunk 0 of strip 0, plane x: column -1 of row 1 -- counted in float4 from the
+// pair's first record.  In the dot state it carries the normaliser from the adjoint forward sweep to the adjoint backward sweep
+constexpr int NORM_SLOT = 1;
+
+// kernel ids sdp_kernel_name answers for (166 and 169 answer NULL)
+enum { ID_ADJ_FWD = 167, ID_ADJ_BWD = 168 };
+
 }  // namespace sdp_affine_local
 
 extern "C" {
@@ -48,6 +70,10 @@ __global__ void sdp_affine_local_val_kernel(const float *theta, const float *O, 
                                             int N, int M, int waves);
 __global__ void sdp_affine_local_bwd_kernel(const float4 *state, const float *Vt, const float *Et, float *E, float *GO, float *GX,
                                             const int *lens, int N, int M, int waves);
+__global__ void sdp_affine_local_adj_fwd_kernel(const float4 *state, const float *Vt, const float *ZE, const float *ZGO, const float *ZGX,
+                                                float4 *stated, float *Vtd, const int *lens, int N, int M, int waves);
+__global__ void sdp_affine_local_adj_bwd_kernel(const float4 *state, const float4 *stated, const float *Vt, const float *Vtd, const float *Et,
+                                                float *Ed, float *GOd, float *GXd, const int *lens, int N, int M, int waves);
 }
 
 #endif  // SDP_AFFINE_LOCAL_H_

@@ -628,6 +628,17 @@ int raise_affine_local_limit(int device)
                               sdp_affine_local::LDS_BUDGET);
 }
 
+// its adjoint pair: the adjoint forward sweep keeps the first order's ring, the adjoint backward sweep twice that
+// (sdp_affine_local::adjoint_lds_bytes), both up to 160 KB
+int raise_affine_local_adjoint_limit(int device)
+{
+    static thread_local unsigned long long raised = 0;
+    return raise_strip_limits(raised, device,
+                              {{(const void *)sdp_affine_local_adj_fwd_kernel, "hipFuncSetAttribute(sdp_affine_local_adj_fwd_kernel)"},
+                               {(const void *)sdp_affine_local_adj_bwd_kernel, "hipFuncSetAttribute(sdp_affine_local_adj_bwd_kernel)"}},
+                              sdp_affine_local::LDS_BUDGET);
+}
+
 // the hard affine-gap local operator's sweeps keep three boundary rows per wave (sdp_hard_affine::sweep_lds_bytes), and its walk
 // three planes of a strip's pointer lines (sdp_hard_affine::walk_lds_bytes): up to 160 KB and 99 KB
 int raise_hard_affine_limit(int device)
@@ -795,6 +806,9 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_affine_local::ID_FWD: return "sdp_affine_local_fwd_kernel";
     case sdp_affine_local::ID_VAL: return "sdp_affine_local_val_kernel";
     case sdp_affine_local::ID_BWD: return "sdp_affine_local_bwd_kernel";
+    // its adjoint pair (csrc/sdp_affine_local_adj.hip)
+    case sdp_affine_local::ID_ADJ_FWD: return "sdp_affine_local_adj_fwd_kernel";
+    case sdp_affine_local::ID_ADJ_BWD: return "sdp_affine_local_adj_bwd_kernel";
     // sampling from its posterior (csrc/sdp_affine_local_sample.hip)
     case sdp_affine_local_sample::ID_TABLES: return "sdp_affine_local_tables_kernel";
     case sdp_affine_local_sample::ID_SAMPLE: return "sdp_affine_local_sample_kernel";
@@ -826,6 +840,7 @@ int sdp_init(int device)
     if (int rc = raise_soft_local_adjoint_limit(device)) return rc;
     if (int rc = raise_sparsemax_adjoint_limit(device)) return rc;
     if (int rc = raise_affine_local_limit(device)) return rc;
+    if (int rc = raise_affine_local_adjoint_limit(device)) return rc;
     return raise_hard_affine_limit(device);
 }
 
@@ -1690,6 +1705,40 @@ int sdp_affine_local_backward_f32(const void *state, const float *Vt, const floa
     const int W = sdp_affine_local::waves_for(N, M);
     return strip_launch(sdp_affine_local_bwd_kernel, "sdp_affine_local_bwd_kernel", B, W, sdp_affine_local::sweep_lds_bytes(W, M), stream,
                         static_cast<const float4 *>(state), Vt, Et, E, GO, GX, lens, N, M, W);
+}
+
+// ---- its second order (csrc/sdp_affine_local_adj.hip): the adjoint pair; the adjoint backward sweep has a wave count of its own ----
+size_t sdp_affine_local_adjoint_state_bytes(int B, int N, int M) { return sdp_affine_local_state_bytes(B, N, M); }
+
+int sdp_affine_local_adjoint_forward_f32(const void *state, const float *Vt, const float *ZE, const float *ZGO, const float *ZGX,
+                                         void *state_d, float *Vtd, int B, int N, int M, const int32_t *lens, int flags, int device,
+                                         void *stream)
+{
+    if (!state || !Vt || !state_d || !Vtd || (!ZE && !ZGO && !ZGX))
+        return fail(SDP_E_NULLPTR, "sdp_affine_local_adjoint_forward_f32: null pointer (state, Vt, state_d, Vtd; ZE, ZGO, ZGX may be NULL, "
+                                   "not all three)");
+    if (int rc = affine_local_args(B, N, M, flags)) return rc;
+    if (int rc = use_device(device)) return rc;
+    if (int rc = raise_affine_local_adjoint_limit(device)) return rc;
+    const int W = sdp_affine_local::waves_for(N, M);
+    return strip_launch(sdp_affine_local_adj_fwd_kernel, "sdp_affine_local_adj_fwd_kernel", B, W, sdp_affine_local::sweep_lds_bytes(W, M),
+                        stream, static_cast<const float4 *>(state), Vt, ZE, ZGO, ZGX, static_cast<float4 *>(state_d), Vtd, lens, N, M, W);
+}
+
+int sdp_affine_local_adjoint_backward_f32(const void *state, const void *state_d, const float *Vt, const float *Vtd, const float *Et,
+                                          float *Ed, float *GOd, float *GXd, int B, int N, int M, const int32_t *lens, int flags,
+                                          int device, void *stream)
+{
+    if (!state || !state_d || !Vt || !Vtd || !Et || !Ed)
+        return fail(SDP_E_NULLPTR, "sdp_affine_local_adjoint_backward_f32: null pointer (state, state_d, Vt, Vtd, Et, Ed; GOd and GXd may "
+                                   "be NULL)");
+    if (int rc = affine_local_args(B, N, M, flags)) return rc;
+    if (int rc = use_device(device)) return rc;
+    if (int rc = raise_affine_local_adjoint_limit(device)) return rc;
+    const int W = sdp_affine_local::adjoint_waves_for(N, M);
+    return strip_launch(sdp_affine_local_adj_bwd_kernel, "sdp_affine_local_adj_bwd_kernel", B, W, sdp_affine_local::adjoint_lds_bytes(W, M),
+                        stream, static_cast<const float4 *>(state), static_cast<const float4 *>(state_d), Vt, Vtd, Et, Ed, GOd, GXd, lens,
+                        N, M, W);
 }
 
 // ---- alignments sampled from its posterior (csrc/sdp_affine_local_sample.hip): the end-cell tables, then one walk per sample ----

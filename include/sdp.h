@@ -651,7 +651,8 @@ int sdp_sparsemax_adjoint_backward_f32(const void *state, const void *state_d, c
  * exactly 0 there, and nothing is NaN when every gap is forbidden).  E, GO and GX are +0 by bit pattern outside the pair's [:n, :m]
  * block (the backward kernel writes them: no extra launch); a pair with n < 1 or m < 1 has Vt = 0 and all gradients 0.  fp32 only.
  * No floating-point atomics: two calls on the same inputs give the same bits, and sdp_affine_local_forward_value_f32 gives the bits
- * of sdp_affine_local_forward_f32's Vt.  NOT built: the second order, float64.  Sampling from the posterior is
+ * of sdp_affine_local_forward_f32's Vt.  The second order is sdp_affine_local_adjoint_* below.  NOT built: the third order,
+ * float64.  Sampling from the posterior is
  * sdp_affine_local_end_tables_f32 / sdp_affine_local_sample_paths_f32 below; the hard (max-plus) member of the family is
  * sdp_hard_affine_local_* after them.
  *   state    sdp_affine_local_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: 48 bytes per cell -- one record
@@ -672,6 +673,43 @@ int sdp_affine_local_forward_value_f32(const float *theta, const float *gap_open
                                        const int32_t *lens, int flags, int device, void *stream);
 int sdp_affine_local_backward_f32(const void *state, const float *Vt, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
                                   const int32_t *lens, int flags, int device, void *stream);
+
+/* Its SECOND ORDER (csrc/sdp_affine_local_adj.hip): the adjoint pair, what sdp_soft_local_adjoint_* is to the soft
+ * local operator.  With cotangents ZE on E, ZGO on GO and ZGX on GX, p_s the cell before (i,j) for plane s -- (i-1,j), (i-1,j-1),
+ * (i,j-1) -- and g[s<-s'] = ZGX[i,j] for a gap plane s and s' = s, ZGO[i,j] for a gap plane s and s' != s, 0 for s = m:
+ *     u[s<-s'] = g[s<-s'] + Vd_s'[p_s]                        (a Vd outside the table is 0; the restart term of plane m has u = 0)
+ *     ub_s = sum_s' q[s<-s'] u[s<-s'];   Vd_s[i,j] = ZE[i,j] + ub_s;   qd[s<-s'] = q[s<-s'] (u[s<-s'] - ub_s)
+ *     Vtd  = sum over cells and planes of w_s Vd_s
+ *     Ebd_s[i,j] = Et w_s (Vd_s - Vtd) + (qd[x<-s] Eb_x + q[x<-s] Ebd_x)[i+1,j] + (qd[m<-s] Eb_m + q[m<-s] Ebd_m)[i+1,j+1]
+ *                                      + (qd[y<-s] Eb_y + q[y<-s] Ebd_y)[i,j+1]
+ *     Ed  = Ebd_x + Ebd_m + Ebd_y
+ *     GXd = Ebd_x q[x<-x] + Eb_x qd[x<-x] + Ebd_y q[y<-y] + Eb_y qd[y<-y]
+ *     GOd = Ebd_x (q[x<-m] + q[x<-y]) + Eb_x (qd[x<-m] + qd[x<-y]) + Ebd_y (q[y<-x] + q[y<-m]) + Eb_y (qd[y<-x] + qd[y<-m])
+ * (Ed, GOd, GXd, Vtd) are the gradients of <ZE,E> + <ZGO,GO> + <ZGX,GX> with respect to (theta, O, X, Et); Eb is re-formed by the
+ * first-order recurrence, E is not read.  A plane that is -inf has q = w = 0 and takes no part; a forbidden opening or extension
+ * gets GOd / GXd of bit pattern +0; nothing is NaN for finite theta and finite cotangents.  Outputs are +0 outside a pair's block, and a
+ * pair without a cell gives Vtd = 0.  No atomics: two calls give the same bits.
+ * THE NORMALISER OF w IS TAKEN FROM THE RECORDS, as sdp_soft_local_adjoint_* takes it: exp(-Vt) + sum w is 1 but for the rounding of
+ * Vt, an error common to every w; the adjoint forward sweep sums w, divides Vtd by the sum and leaves its logarithm in the dot record
+ * no cell owns (column -1 of row 1), and the adjoint backward sweep subtracts it from V_s - Vt.  In exact arithmetic it is 0.
+ *   state, Vt   what sdp_affine_local_forward_f32 wrote, with the same B, N, M, lens.
+ *   ZE, ZGO, ZGX   (B, N, M) or NULL (zeros), each on its own; all three NULL: SDP_E_NULLPTR.  A NULL gives the bits of a tensor of zeros.
+ *   state_d  sdp_affine_local_adjoint_state_bytes(B, N, M) == sdp_affine_local_state_bytes(B, N, M) bytes, DEVICE, caller-owned: the
+ *            dot records {qd[s<-x], qd[s<-m], qd[s<-y], Vd_s} in the layout of the records.  Only records of cells inside a pair's
+ *            block are written, and the normaliser's.
+ *   Vtd      (B,): written by the adjoint forward entry, READ by the adjoint backward entry.
+ *   Et       (B,): what sdp_affine_local_backward_f32 was given.
+ *   GOd, GXd (B, N, M) or NULL, each on its own.
+ * The adjoint forward sweep runs on the first order's ring and waves; the adjoint backward sweep's ring is twice that (the pushes of
+ * Eb and of Ebd into each plane), so it runs eight waves up to M = 789 and three at the column limit.  Codes, limits and the
+ * dynamic-LDS attribute as for the first-order entries; all arguments are checked before any device call. */
+size_t sdp_affine_local_adjoint_state_bytes(int B, int N, int M);
+int sdp_affine_local_adjoint_forward_f32(const void *state, const float *Vt, const float *ZE, const float *ZGO, const float *ZGX,
+                                         void *state_d, float *Vtd, int B, int N, int M, const int32_t *lens, int flags, int device,
+                                         void *stream);
+int sdp_affine_local_adjoint_backward_f32(const void *state, const void *state_d, const float *Vt, const float *Vtd, const float *Et,
+                                          float *Ed, float *GOd, float *GXd, int B, int N, int M, const int32_t *lens, int flags,
+                                          int device, void *stream);
 
 /* Alignments SAMPLED from its posterior (csrc/sdp_affine_local_sample.hip): what sdp_soft_local_sample_paths_f32 is
  * to the soft local operator.  (Added after SDP_VERSION 106 without a version change: look the symbols up.  sdp_kernel_name answers
