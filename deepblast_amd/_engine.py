@@ -830,6 +830,52 @@ class HipEngine:
                   opens, extends, ends, B, N, M, int(K), int(sample0), int(seed) & 0xffffffffffffffff, lens, 0)
         return states, counts, visits, opens, extends, ends
 
+    # ---- the affine-gap soft global operator (include/sdp.h: sdp_affine_global_*) ---------------
+    def affine_global_forward(self, theta, gap_open, gap_extend, lens=None, state_out=None):
+        """-> (Vt (B,), state): the affine-gap soft global sweep and its 48-byte records (opaque float32 tensor of
+        sdp_affine_global_state_bytes; the end weights travel in it).  state_out: a buffer of that size to write into instead of a
+        fresh one."""
+        dev = self.device_of(theta)
+        check_args(theta, torch.float32, theta=theta, gap_open=gap_open, gap_extend=gap_extend)
+        check_args(theta, None, tuple(theta.shape), gap_open=gap_open, gap_extend=gap_extend)
+        theta, gap_open, gap_extend = theta.contiguous(), gap_open.contiguous(), gap_extend.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        nfloats = max(self.lib.sdp_affine_global_state_bytes(B, N, M), 4) // 4
+        check_args(theta, torch.float32, (nfloats,), True, ValueError, state_out=state_out)
+        state = torch.empty(nfloats, dtype=torch.float32, device=theta.device) if state_out is None else state_out
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        self.call("sdp_affine_global_forward_f32", AFFINE_GLOBAL_KERNELS[180], dev, theta, gap_open, gap_extend, state, Vt, B, N, M, lens, 0)
+        return Vt, state
+
+    def affine_global_forward_value(self, theta, gap_open, gap_extend, lens=None):
+        """-> Vt (B,) alone: the same sweep with the records compiled out (the same bits); nothing else is allocated."""
+        dev = self.device_of(theta)
+        check_args(theta, torch.float32, theta=theta, gap_open=gap_open, gap_extend=gap_extend)
+        check_args(theta, None, tuple(theta.shape), gap_open=gap_open, gap_extend=gap_extend)
+        theta, gap_open, gap_extend = theta.contiguous(), gap_open.contiguous(), gap_extend.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        self.call("sdp_affine_global_forward_value_f32", AFFINE_GLOBAL_KERNELS[181], dev, theta, gap_open, gap_extend, Vt, B, N, M, lens, 0)
+        return Vt
+
+    def affine_global_backward(self, state, Et, shape, lens=None, want_GO=True, want_GX=True):
+        """The mirror sweep over the records of affine_global_forward -> (E (B,N,M), GO (B,N,M) or None, GX (B,N,M) or None):
+        Et . dVt/dtheta, Et . dVt/dgap_open and Et . dVt/dgap_extend, +0 outside each pair's block.  (No Vt: the end weights are in
+        `state`.)"""
+        dev = self.device_of(state)
+        B, N, M = shape
+        check_args(state, torch.float32, None, True, state=state)
+        check_args(state, Et=Et)
+        Et = Et.detach().to(torch.float32).expand(B).contiguous()
+        lens = self._lens(lens, B, state.device)
+        E = torch.empty((B, N, M), dtype=torch.float32, device=state.device)
+        GO = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if want_GO else None
+        GX = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if want_GX else None
+        self.call("sdp_affine_global_backward_f32", AFFINE_GLOBAL_KERNELS[182], dev, state, Et, E, GO, GX, B, N, M, lens, 0)
+        return E, GO, GX
+
     # ---- the hard affine-gap local operator (include/sdp.h: sdp_hard_affine_local_*) ------------
     def _hard_affine_variant(self, ymx, waves=True):
         """`variant` of the sdp_hard_affine_local_* entries; waves=False for the walk, which runs one wave per pair."""
@@ -990,6 +1036,8 @@ SOFT_LOCAL_SAMPLE_KERNELS = {134: "sdp_soft_local_tables_kernel", 135: "sdp_soft
 SPARSEMAX_KERNELS = {150: "sdp_sparsemax_fwd_kernel", 151: "sdp_sparsemax_val_kernel", 152: "sdp_sparsemax_bwd_kernel"}
 # the same of its adjoint pair (csrc/sdp_sparsemax_adj.hip)
 SPARSEMAX_ADJOINT_KERNELS = {154: "sdp_sparsemax_adj_fwd_kernel", 155: "sdp_sparsemax_adj_bwd_kernel"}
+# kernel id (csrc/sdp_affine_global.h) -> symbol of the affine-gap soft global operator's kernels
+AFFINE_GLOBAL_KERNELS = {180: "sdp_affine_global_fwd_kernel", 181: "sdp_affine_global_val_kernel", 182: "sdp_affine_global_bwd_kernel"}
 # kernel id (csrc/sdp_affine_local.h) -> symbol of the affine-gap soft local operator's kernels
 AFFINE_LOCAL_KERNELS = {160: "sdp_affine_local_fwd_kernel", 161: "sdp_affine_local_val_kernel", 162: "sdp_affine_local_bwd_kernel"}
 # of its adjoint pair (the same header)

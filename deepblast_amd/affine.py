@@ -27,6 +27,9 @@ theta, gap_open and gap_extend -- loss(first, dec.decode(theta, gap_open, gap_ex
 
 Out of scope, none of it built: the third order, float64, the `distributed` wrappers, `search_scores` and `losses.decode_loss`
 (their protocols have two tensors, this operator three).
+
+The GLOBAL form -- a path from cell (1,1) to cell (n,m), the Gotoh form of Needleman-Wunsch -- is AffineGlobalDecoder at the end of
+this file (include/sdp.h: sdp_affine_global_*): first order, softmax only.
 """
 import torch
 
@@ -345,3 +348,95 @@ class AffineLocalDecoder(torch.nn.Module):
         states, counts = states.cpu().numpy(), counts.cpu().numpy()
         return Vt, [[[tuple(int(v) for v in row) for row in states[b, k, :counts[b, k]]] for k in range(counts.shape[1])]
                     for b in range(counts.shape[0])]
+
+
+# ---- the affine-gap soft GLOBAL operator (include/sdp.h: sdp_affine_global_*) ----
+class AffineGlobalFunctionBackward(torch.autograd.Function):
+    """(E, GO, GX) of the global mirror sweep.  Differentiable in nothing: this is the node at which a second differentiation
+    stops, with a message that names the reason."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, Et, state, lens, want_E, want_GO, want_GX):
+        # (the three inputs are here for the graph alone: the gradients depend on them, and a second differentiation must arrive below)
+        E, GO, GX = _engine.get_engine().affine_global_backward(state, Et, tuple(theta.shape), lens, want_GO=want_GO, want_GX=want_GX)
+        return (E if want_E else None), GO, GX
+
+    @staticmethod
+    def backward(ctx, ZE, ZGO, ZGX):
+        raise NotImplementedError("the affine-gap soft global operator is first order only: its second order (an adjoint pair for "
+                                  "sdp_affine_global_*) is not built")
+
+
+class AffineGlobalFunction(torch.autograd.Function):
+    """Vt = affine_global(theta, gap_open, gap_extend); backward: theta.grad = E, gap_open.grad = GO, gap_extend.grad = GX, one
+    mirror sweep; GO and GX are computed only when their input needs a gradient.  Once differentiable: differentiating E, GO or
+    GX raises NotImplementedError (AffineGlobalFunctionBackward)."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, lens=None):
+        Vt, state = _engine.get_engine().affine_global_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lens)
+        ctx.save_for_backward(theta, gap_open, gap_extend, state)
+        ctx.lens = lens
+        return Vt
+
+    @staticmethod
+    def backward(ctx, Et):
+        theta, gap_open, gap_extend, state = ctx.saved_tensors
+        E, GO, GX = AffineGlobalFunctionBackward.apply(theta, gap_open, gap_extend, Et, state, ctx.lens, *ctx.needs_input_grad[:3])
+        return E, GO, GX, None
+
+
+class AffineGlobalDecoder(torch.nn.Module):
+    """Affine-gap GLOBAL alignment scores, their gradients and the posterior alignment matrix, on a ROCm device in float32: a
+    differentiable Needleman-Wunsch in which opening a gap and extending it are priced separately, the Gotoh global form
+    (include/sdp.h: sdp_affine_global_*).
+
+        Vm[1,1] = theta[1,1];  elsewhere  Vm[i,j] = theta[i,j] + log(exp Vx[i-1,j-1] + exp Vm[i-1,j-1] + exp Vy[i-1,j-1])
+        Vx[i,j] = theta[i,j] + log(exp(X[i,j] + Vx[i-1,j]) + exp(O[i,j] + Vm[i-1,j]) + exp(O[i,j] + Vy[i-1,j]))
+        Vy[i,j] = theta[i,j] + log(exp(O[i,j] + Vx[i,j-1]) + exp(O[i,j] + Vm[i,j-1]) + exp(X[i,j] + Vy[i,j-1]))
+        Vt      = log(exp Vx[n,m] + exp Vm[n,m] + exp Vy[n,m])
+
+    O = gap_open, X = gap_extend.  exp(Vt) is the sum over every path from cell (1,1) to cell (n,m) of exp(score): theta on every
+    cell of the path; on a cell entered through a gap step, X if the step before was the same kind of gap step and O otherwise.
+    A plane without a predecessor is -inf.  There is no temperature parameter: scale theta, gap_open and gap_extend.
+
+    Parity unpinned.  With gap_open == gap_extend == A this is the single-score Needleman-Wunsch with a -inf border; it is NOT the
+    reference's NeedlemanWunschDecoder (nor deepblast_amd.NeedlemanWunschDecoder, which follows it): that one keeps a ZERO border,
+    so a path may start anywhere on the top or left edge, and the two differ by more than 1 in Vt on ordinary inputs.  The kernels
+    are held to the float64 definition.
+
+    forward(theta, gap_open, gap_extend, lengths=None) -> Vt (B,), differentiable ONCE: theta.grad = E, gap_open.grad = GO,
+    gap_extend.grad = GX, all true gradients; GO and GX are computed only when their input needs a gradient.  Differentiating a
+    gradient raises NotImplementedError (the second order is not built).
+    decode(theta, gap_open, gap_extend, lengths=None) -> E (B, N, M) for Et = 1: E[b, i, j] is the posterior probability that cell
+    (i, j) lies on the alignment of pair b.  No autograd graph.
+    score(theta, gap_open, gap_extend, lengths=None) -> Vt (B,) through the value-only sweep: no state is allocated, no graph.
+    theta finite; gap_open and gap_extend finite or -inf (a forbidden opening or extension: the matching gradient is exactly +0
+    there).  Where no path exists -- n != m with every gap forbidden, or masks that cut every route -- Vt = -inf and the gradients
+    are +0; nothing is NaN.  lengths (B, 2): pair b is theta[b, :n_b, :m_b], aligned end to end; E, GO and GX are +0 outside it,
+    and an empty pair has Vt = 0.  Problems wider than the column limit (2048) are swept transposed -- the operator is symmetric
+    under transposition with x <-> y -- and the results come back in the caller's coordinates; both sides above the limit raise
+    ValueError.  Non-fp32 or non-tensor input: TypeError; a shape mismatch: ValueError.
+    Out of scope, none of it built: the hard-max member and its walk, sampling, the second order, float64, the `distributed`
+    wrappers, `search_scores`, `losses.decode_loss`, free end gaps, and the reference's zero border."""
+
+    def forward(self, theta, gap_open, gap_extend, lengths=None):
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, _ = _oriented(theta, gap_open, gap_extend, lengths)
+        return AffineGlobalFunction.apply(theta, gap_open, gap_extend, lengths)
+
+    def decode(self, theta, gap_open, gap_extend, lengths=None):
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, transposed = _oriented(theta, gap_open, gap_extend, lengths)
+        eng = _engine.get_engine()
+        with torch.no_grad():
+            _, state = eng.affine_global_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths)
+            E, _, _ = eng.affine_global_backward(state, torch.ones((), dtype=torch.float32, device=theta.device), tuple(theta.shape),
+                                                 lengths, want_GO=False, want_GX=False)
+        return E.transpose(1, 2) if transposed else E
+
+    def score(self, theta, gap_open, gap_extend, lengths=None):
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, _ = _oriented(theta, gap_open, gap_extend, lengths)
+        with torch.no_grad():
+            return _engine.get_engine().affine_global_forward_value(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths)

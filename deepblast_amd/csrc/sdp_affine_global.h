@@ -1,0 +1,56 @@
+// sdp_affine_global.h -- the affine-gap soft global operator's kernel family (csrc/sdp_affine_global.hip): launch geometry shared with the host side.
+#ifndef SDP_AFFINE_GLOBAL_H_
+#define SDP_AFFINE_GLOBAL_H_
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace sdp_affine_global {
+
+constexpr int STRIP = 64;        // rows of a strip: one per lane of the wave that sweeps it
+constexpr int CHUNK = 32;        // anti-diagonal steps between two barriers
+constexpr int HALF = 16;         // steps of the forward sweep's input prefetch: three inputs, half a chunk ahead
+constexpr int GROUP = 4;         // steps of the backward sweep's record prefetch (twelve floats a step) and of its E / GO / GX stores
+constexpr int PLANES = 3;        // x, m, y = 0, 1, 2: the step that entered the cell
+constexpr int RING = 4;          // words of a column of a boundary row: three mantissas and the cell's exponent
+constexpr int MAX_WAVES = 8;     // waves (strips in flight) of a workgroup
+constexpr int KEY = 256;         // progress word of a wave: strip * KEY + chunks done (chunks of a strip <= 66 < KEY)
+constexpr int LDS_BUDGET = 160 * 1024;   // all of a CU's LDS: every kernel of the family has its dynamic-LDS attribute raised
+constexpr int CELL_BYTES = 48;   // three records of a cell, one per plane s: {q[s<-x], q[s<-m], q[s<-y], w_s at the end cell / 0}
+constexpr int ZERO_LOG2 = 29;    // an all-zero cell carries the exponent -(1 << ZERO_LOG2), and a cell below it is flushed to one
+constexpr int SCORE_LOG2 = 24;   // a score below -(1 << SCORE_LOG2) / log2(e) = -1.16e7 is -inf: its exp has mantissa 0
+
+__host__ __device__ inline int strips(int N) { return (N + STRIP - 1) / STRIP; }
+// chunks of a strip of m columns: the last lane starts 63 steps after the first
+__host__ __device__ inline int chunks(int m) { return (m + STRIP - 1 + CHUNK - 1) / CHUNK; }
+__host__ __device__ inline int row_pitch(int M) { return M + STRIP; }   // words of one boundary row of one plane in LDS
+// the ring of boundary rows: four words per column -- the forward sweep hands the three mantissas and the exponent of a strip's
+// bottom row down; the backward sweep, on the same ring, what the top row pushes up into each plane -- plus the progress words
+__host__ __device__ inline size_t sweep_lds_bytes(int waves, int M) { return (size_t)RING * waves * row_pitch(M) * 4 + 2 * MAX_WAVES * 4; }
+// waves of a workgroup, all three kernels: one per strip in flight, as many as the ring fits LDS_BUDGET for -- eight up to
+// M = 1215, seven up to 1398, six up to 1642, five up to 1983, four up to the column limit 2048
+__host__ __device__ inline int waves_for(int N, int M)
+{
+    int w = strips(N) < MAX_WAVES ? strips(N) : MAX_WAVES;
+    while (w > 1 && sweep_lds_bytes(w, M) > (size_t)LDS_BUDGET) --w;
+    return w;
+}
+// cells of one pair's state: every step of every chunk of every strip holds three lines of 64 records (one line per plane)
+__host__ __device__ inline size_t pair_cells(int N, int M) { return (size_t)strips(N) * chunks(M) * CHUNK * STRIP; }
+
+// kernel ids sdp_kernel_name answers for (179 and 183 answer NULL)
+enum { ID_FWD = 180, ID_VAL = 181, ID_BWD = 182 };
+
+}  // namespace sdp_affine_global
+
+extern "C" {
+__global__ void sdp_affine_global_fwd_kernel(const float *theta, const float *O, const float *X, float4 *state, float *Vt, const int *lens,
+                                             int N, int M, int waves);
+__global__ void sdp_affine_global_val_kernel(const float *theta, const float *O, const float *X, float4 *state, float *Vt, const int *lens,
+                                             int N, int M, int waves);
+__global__ void sdp_affine_global_bwd_kernel(const float4 *state, const float *Et, float *E, float *GO, float *GX, const int *lens, int N,
+                                             int M, int waves);
+}
+
+#endif  // SDP_AFFINE_GLOBAL_H_

@@ -17,6 +17,7 @@
 #include "sdp_soft_local.h"
 #include "sdp_soft_local_sample.h"
 #include "sdp_sparsemax.h"
+#include "sdp_affine_global.h"
 #include "sdp_affine_local.h"
 #include "sdp_affine_local_sample.h"
 #include "sdp_hard_affine.h"
@@ -653,6 +654,18 @@ int raise_hard_affine_limit(int device)
                               sdp_hard_affine::LDS_BUDGET);
 }
 
+// the affine-gap soft global operator's three kernels keep four words per column and wave (sdp_affine_global::sweep_lds_bytes): up to
+// 160 KB, forward sweeps included
+int raise_affine_global_limit(int device)
+{
+    static thread_local unsigned long long raised = 0;
+    return raise_strip_limits(raised, device,
+                              {{(const void *)sdp_affine_global_fwd_kernel, "hipFuncSetAttribute(sdp_affine_global_fwd_kernel)"},
+                               {(const void *)sdp_affine_global_val_kernel, "hipFuncSetAttribute(sdp_affine_global_val_kernel)"},
+                               {(const void *)sdp_affine_global_bwd_kernel, "hipFuncSetAttribute(sdp_affine_global_bwd_kernel)"}},
+                              sdp_affine_global::LDS_BUDGET);
+}
+
 // ---- what the entries of the strip-schedule families share ----
 // waves of a workgroup: one per strip in flight, lowered to `forced` if 0 < forced, then until the family's ring fits its budget
 int strip_waves(int strips, int max_waves, int forced, int M, size_t (*lds_bytes)(int, int), int budget)
@@ -818,6 +831,10 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_hard_affine::ID_VAL: return "sdp_hard_affine_local_val_kernel";
     case sdp_hard_affine::ID_VAL_T: return "sdp_hard_affine_local_val_t_kernel";
     case sdp_hard_affine::ID_WALK: return "sdp_hard_affine_local_walk_kernel";
+    // the affine-gap soft global operator (csrc/sdp_affine_global.hip)
+    case sdp_affine_global::ID_FWD: return "sdp_affine_global_fwd_kernel";
+    case sdp_affine_global::ID_VAL: return "sdp_affine_global_val_kernel";
+    case sdp_affine_global::ID_BWD: return "sdp_affine_global_bwd_kernel";
     }
     return nullptr;
 }
@@ -841,7 +858,8 @@ int sdp_init(int device)
     if (int rc = raise_sparsemax_adjoint_limit(device)) return rc;
     if (int rc = raise_affine_local_limit(device)) return rc;
     if (int rc = raise_affine_local_adjoint_limit(device)) return rc;
-    return raise_hard_affine_limit(device);
+    if (int rc = raise_hard_affine_limit(device)) return rc;
+    return raise_affine_global_limit(device);
 }
 
 int sdp_device_status(int device, int32_t info[4])
@@ -1844,6 +1862,54 @@ int sdp_hard_affine_local_walk_f32(const void *state, const int32_t *ends, const
     return strip_launch(sdp_hard_affine_local_walk_kernel, "sdp_hard_affine_local_walk_kernel", B, 1, sdp_hard_affine::walk_lds_bytes(M),
                         stream, static_cast<const uint32_t *>(state), ends, Et, E, GO, GX, states, counts, lens, N, M,
                         sdp_traceback_capacity(N, M), ymx ? 1 : 0);
+}
+
+// ---- the affine-gap soft global operator (csrc/sdp_affine_global.hip): the Gotoh form of Needleman-Wunsch, first order ----
+// `flags` of the three entries: none is defined, any bit is refused
+static int affine_global_args(int B, int N, int M, int flags) { return flagless_args("sdp_affine_global", B, N, M, flags); }
+
+size_t sdp_affine_global_state_bytes(int B, int N, int M)
+{
+    if (B <= 0 || N <= 0 || M <= 0 || M > sdp::MAX_COLS) return 0;
+    return (size_t)B * sdp_affine_global::pair_cells(N, M) * sdp_affine_global::CELL_BYTES;
+}
+
+static int affine_global_forward(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int B, int N,
+                                 int M, const int32_t *lens, int flags, int device, void *stream, bool records)
+{
+    if (int rc = affine_global_args(B, N, M, flags)) return rc;
+    if (int rc = use_device(device)) return rc;
+    if (int rc = raise_affine_global_limit(device)) return rc;
+    const int W = sdp_affine_global::waves_for(N, M);
+    return strip_launch(records ? sdp_affine_global_fwd_kernel : sdp_affine_global_val_kernel,
+                        records ? "sdp_affine_global_fwd_kernel" : "sdp_affine_global_val_kernel", B, W, sdp_affine_global::sweep_lds_bytes(W, M),
+                        stream, theta, gap_open, gap_extend, static_cast<float4 *>(state), Vt, lens, N, M, W);
+}
+
+int sdp_affine_global_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int B, int N,
+                                  int M, const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!theta || !gap_open || !gap_extend || !state || !Vt) return fail(SDP_E_NULLPTR, "sdp_affine_global_forward_f32: null pointer");
+    return affine_global_forward(theta, gap_open, gap_extend, state, Vt, B, N, M, lens, flags, device, stream, true);
+}
+
+int sdp_affine_global_forward_value_f32(const float *theta, const float *gap_open, const float *gap_extend, float *Vt, int B, int N, int M,
+                                        const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!theta || !gap_open || !gap_extend || !Vt) return fail(SDP_E_NULLPTR, "sdp_affine_global_forward_value_f32: null pointer");
+    return affine_global_forward(theta, gap_open, gap_extend, nullptr, Vt, B, N, M, lens, flags, device, stream, false);
+}
+
+int sdp_affine_global_backward_f32(const void *state, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
+                                   const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!state || !Et || !E) return fail(SDP_E_NULLPTR, "sdp_affine_global_backward_f32: null pointer (state, Et, E; GO and GX may be NULL)");
+    if (int rc = affine_global_args(B, N, M, flags)) return rc;
+    if (int rc = use_device(device)) return rc;
+    if (int rc = raise_affine_global_limit(device)) return rc;
+    const int W = sdp_affine_global::waves_for(N, M);
+    return strip_launch(sdp_affine_global_bwd_kernel, "sdp_affine_global_bwd_kernel", B, W, sdp_affine_global::sweep_lds_bytes(W, M), stream,
+                        static_cast<const float4 *>(state), Et, E, GO, GX, lens, N, M, W);
 }
 
 // ---- the sparsemax operator (csrc/sdp_sparsemax.hip): the global recurrence under the sparse smoothed maximum, first order ----

@@ -828,6 +828,52 @@ int sdp_hard_affine_local_forward_value_f32(const float *theta, const float *gap
 int sdp_hard_affine_local_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, float *GO, float *GX, int32_t *states,
                                    int32_t *counts, int B, int N, int M, const int32_t *lens, int variant, int device, void *stream);
 
+/* The AFFINE-GAP SOFT GLOBAL operator (csrc/sdp_affine_global.hip): a differentiable Needleman-Wunsch with opening a
+ * gap and extending it priced separately -- the Gotoh global form.  (Added after SDP_VERSION 106 without a version change: look the
+ * symbols up.)  Notation of the affine-gap soft local operator above: (n, m) = lens[b] clamped or (N, M), cells 1-based, theta,
+ * gap_open (O) and gap_extend (X) 0-based (B, N, M).  A path STARTS AT CELL (1,1) AND ENDS AT CELL (n,m); it takes steps x
+ * (i-1,j)->(i,j), m (i-1,j-1)->(i,j) or y (i,j-1)->(i,j); its score is theta on every one of its cells, plus, on every cell entered
+ * through x or y, X[i,j] if the step before was the same kind of gap step and O[i,j] otherwise (the start cell, an m step and the
+ * OTHER gap kind all count as otherwise).  exp(Vt) = the sum over every such path of exp(score).  Three planes per cell, named by the
+ * step that entered the cell, x, m, y = 0, 1, 2; a plane value without a predecessor is -inf and its weights are 0:
+ *     Vm[1,1] = theta[1,1];   elsewhere  Vm[i,j] = theta[i,j] + log(exp Vx[i-1,j-1] + exp Vm[i-1,j-1] + exp Vy[i-1,j-1])
+ *     Vx[i,j] = theta[i,j] + log(exp(X[i,j] + Vx[i-1,j]) + exp(O[i,j] + Vm[i-1,j]) + exp(O[i,j] + Vy[i-1,j]))
+ *     Vy[i,j] = theta[i,j] + log(exp(O[i,j] + Vx[i,j-1]) + exp(O[i,j] + Vm[i,j-1]) + exp(X[i,j] + Vy[i,j-1]))
+ *     Vt      = log(exp Vx[n,m] + exp Vm[n,m] + exp Vy[n,m]);      w_s = exp(V_s[n,m] - Vt)      (the end cell only)
+ *     Eb_s[i,j] = [(i,j) = (n,m)] Et w_s + q[x<-s][i+1,j] Eb_x[i+1,j] + q[m<-s][i+1,j+1] Eb_m[i+1,j+1] + q[y<-s][i,j+1] Eb_y[i,j+1]
+ *     E, GO, GX from Eb and q exactly as in the local family: the TRUE gradients Et dVt/dtheta, Et dVt/dO, Et dVt/dX.
+ * With O == X == A this is the single-score Needleman-Wunsch with a -inf border (Vt, E, GO + GX = G).  It is NOT the operator of
+ * sdp_forward_f32 / the reference's NeedlemanWunschDecoder, whose border is zero (a path may start anywhere on the top or left
+ * edge): parity is unpinned, the kernels are held to the float64 definition.  Symmetric under transposition with x <-> y.
+ * theta finite; O and X finite or -inf (a forbidden opening or extension: the matching gradient is +0 there).  When no path exists
+ * -- n != m with every gap forbidden, or masks that cut every route -- Vt = -inf, E = GO = GX = +0, nothing is NaN.  E, GO and GX
+ * are +0 by bit pattern outside the pair's [:n, :m] block (the backward kernel writes them: no extra launch); a pair with n < 1 or
+ * m < 1 has Vt = 0 and all gradients 0.  fp32 only.  No floating-point atomics: two calls on the same inputs give the same bits,
+ * and sdp_affine_global_forward_value_f32 gives the bits of sdp_affine_global_forward_f32's Vt.
+ * Arithmetic: the sweep carries exp V scaled -- three fp32 mantissas on one integer exponent per cell -- and rebuilds Vt once per
+ * pair in float64.  Its envelope: a score below -2^24 / log2(e) = -1.16e7 counts as -inf; a plane more than 2^126 below the largest
+ * plane of its cell, and a cell whose weight falls below 2^(-2^29), are flushed to zero.
+ * NOT built: the hard-max member and its walk, sampling, the second order, float64, free end gaps, the reference's zero border.
+ *   state    sdp_affine_global_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: 48 bytes per cell -- one record
+ *            {q[s<-x], q[s<-m], q[s<-y], w_s} per plane s, w_s zero but in the end cell -- in a private layout; written by
+ *            sdp_affine_global_forward_f32, read by sdp_affine_global_backward_f32 with the same B, N, M, lens (which needs neither
+ *            theta, O, X nor Vt).  Only records of cells inside a pair's block are written, and the backward pass uses no others.
+ *   Vt       (B,): written by the forward entries.
+ *   GO, GX   (B, N, M) or NULL, each on its own.
+ *   flags    this family defines none: any bit is refused (SDP_E_VARIANT).
+ * One workgroup per pair, rows unbounded, M <= sdp_max_cols().  Every kernel keeps four words per column and wave in LDS (up to
+ * 160 KB: eight waves up to M = 1215, seven to 1398, six to 1642, five to 1983, four at the column limit), for which the entries
+ * raise the kernels' dynamic-LDS limit (sdp_init does it too, before a stream capture).  All arguments are checked before any
+ * device call, with the local family's codes and limits: SDP_E_NULLPTR, SDP_E_SHAPE, SDP_E_MAXCOLS, SDP_E_VARIANT, SDP_E_TOOBIG
+ * (N*M > 2^28, or B*N*M > 2^31 elements). */
+size_t sdp_affine_global_state_bytes(int B, int N, int M);
+int sdp_affine_global_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int B, int N,
+                                  int M, const int32_t *lens, int flags, int device, void *stream);
+int sdp_affine_global_forward_value_f32(const float *theta, const float *gap_open, const float *gap_extend, float *Vt, int B, int N, int M,
+                                        const int32_t *lens, int flags, int device, void *stream);
+int sdp_affine_global_backward_f32(const void *state, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
+                                   const int32_t *lens, int flags, int device, void *stream);
+
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept
  * for callers who are short of memory, not of time; deepblast_amd.losses uses the unfused kernels by default.
