@@ -892,36 +892,44 @@ class HipEngine:
         plane, (-1, -1, -1) where nothing is positive -- and its 2-bit pointers, three planes (opaque int32 tensor of
         sdp_hard_affine_local_state_bytes).  ymx: the tensors are a TRANSPOSED problem; ends come back in the coordinates and
         plane names handed over."""
+        return self._hard_affine_forward("local", HARD_AFFINE_LOCAL_KERNELS, 170, theta, gap_open, gap_extend, lens, ymx)
+
+    def _hard_affine_forward(self, member, kernels, first, theta, gap_open, gap_extend, lens, ymx):
+        """the pointer sweep of sdp_hard_affine_<member>_*; kernels[first], kernels[first + 1]: its two tie orders"""
         dev = self.device_of(theta)
         theta, gap_open, gap_extend = self._hard_affine_inputs(theta, gap_open, gap_extend)
         B, N, M = theta.shape
         lens = self._lens(lens, B, theta.device)
-        nbytes = self.lib.sdp_hard_affine_local_state_bytes(B, N, M)
+        nbytes = getattr(self.lib, f"sdp_hard_affine_{member}_state_bytes")(B, N, M)
         state = torch.empty(max(nbytes, 4) // 4, dtype=torch.int32, device=theta.device)
         Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
         ends = torch.empty((B, 3), dtype=torch.int32, device=theta.device)
-        self.call("sdp_hard_affine_local_forward_f32", HARD_AFFINE_LOCAL_KERNELS[171 if ymx else 170], dev, theta, gap_open, gap_extend,
+        self.call(f"sdp_hard_affine_{member}_forward_f32", kernels[first + (1 if ymx else 0)], dev, theta, gap_open, gap_extend,
                   state, Vt, ends, B, N, M, lens, self._hard_affine_variant(ymx))
         return Vt, state, ends
 
     def hard_affine_local_forward_value(self, theta, gap_open, gap_extend, lens=None, ymx=False, want_ends=True):
         """-> (Vt (B,), ends (B, 3) int32 or None): the same sweep with the pointers compiled out (the same bits)."""
+        return self._hard_affine_forward_value("local", HARD_AFFINE_LOCAL_KERNELS, 172, theta, gap_open, gap_extend, lens, ymx, want_ends)
+
+    def _hard_affine_forward_value(self, member, kernels, first, theta, gap_open, gap_extend, lens, ymx, want_ends):
         dev = self.device_of(theta)
         theta, gap_open, gap_extend = self._hard_affine_inputs(theta, gap_open, gap_extend)
         B, N, M = theta.shape
         lens = self._lens(lens, B, theta.device)
         Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
         ends = torch.empty((B, 3), dtype=torch.int32, device=theta.device) if want_ends else None
-        self.call("sdp_hard_affine_local_forward_value_f32", HARD_AFFINE_LOCAL_KERNELS[173 if ymx else 172], dev, theta, gap_open,
+        self.call(f"sdp_hard_affine_{member}_forward_value_f32", kernels[first + (1 if ymx else 0)], dev, theta, gap_open,
                   gap_extend, Vt, ends, B, N, M, lens, self._hard_affine_variant(ymx))
         return Vt, ends
 
     def hard_affine_local_walk(self, state, ends, shape, lens=None, Et=None, ymx=False, want_E=True, want_GO=False, want_GX=False,
-                               want_states=True, E_out=None, GO_out=None, GX_out=None, states_out=None):
+                               want_states=True, E_out=None, GO_out=None, GX_out=None, states_out=None, entry="sdp_hard_affine_local_walk_f32"):
         """The walk along the pointers of hard_affine_local_forward, from `ends` -> (E, GO, GX (B,N,M) or None each, states
         (B,cap,3) int32 or None, counts (B,) or None).  E: Et[b] on pair b's path, GO / GX: Et[b] on its gap cells entered from
         another plane / the same plane, +0 on every other cell of the plane; states / counts: the path alone (no padding), start
-        first; row cap - 1 of states: (number of path cells, i and j of its first cell).  *_out: buffers to write into."""
+        first; row cap - 1 of states: (number of path cells, i and j of its first cell).  *_out: buffers to write into.
+        entry: the C entry to go through (hard_affine_global_walk names its own; the kernel is the same)."""
         dev = self.device_of(state)
         B, N, M = shape
         lens = self._lens(lens, B, state.device)
@@ -943,9 +951,25 @@ class HipEngine:
             check_args(state, torch.int32, (B, cap, 3), True, ValueError, states_out=states_out)
             states = torch.empty((B, cap, 3), dtype=torch.int32, device=state.device) if states_out is None else states_out
             counts = torch.empty(B, dtype=torch.int32, device=state.device)
-        self.call("sdp_hard_affine_local_walk_f32", HARD_AFFINE_LOCAL_KERNELS[174], dev, state, ends, Et if any(wants) else None, *planes,
+        self.call(entry, HARD_AFFINE_LOCAL_KERNELS[174], dev, state, ends, Et if any(wants) else None, *planes,
                   states, counts, B, N, M, lens, self._hard_affine_variant(ymx, waves=False))
         return planes[0], planes[1], planes[2], states, counts
+
+    # ---- the hard affine-gap global operator (include/sdp.h: sdp_hard_affine_global_*): the local member's launches ----
+    def hard_affine_global_forward(self, theta, gap_open, gap_extend, lens=None, ymx=False):
+        """-> (Vt (B,), state, ends (B, 3) int32): the Gotoh max-plus sweep from cell (0, 0) to cell (n - 1, m - 1) -- Vt the first
+        maximum of the last cell's planes, -inf for a pair without a path, +0 for an empty pair; ends (n - 1, m - 1, plane),
+        (-1, -1, -1) where there is no path -- and its pointers in the local member's format.  ymx: as hard_affine_local_forward."""
+        return self._hard_affine_forward("global", HARD_AFFINE_GLOBAL_KERNELS, 185, theta, gap_open, gap_extend, lens, ymx)
+
+    def hard_affine_global_forward_value(self, theta, gap_open, gap_extend, lens=None, ymx=False, want_ends=True):
+        """-> (Vt (B,), ends (B, 3) int32 or None): the same sweep with the pointers compiled out (the same bits)."""
+        return self._hard_affine_forward_value("global", HARD_AFFINE_GLOBAL_KERNELS, 187, theta, gap_open, gap_extend, lens, ymx, want_ends)
+
+    def hard_affine_global_walk(self, state, ends, shape, lens=None, **kw):
+        """hard_affine_local_walk on the pointers of hard_affine_global_forward (the state format, ends and the stop at START are the
+        same), through sdp_hard_affine_global_walk_f32."""
+        return self.hard_affine_local_walk(state, ends, shape, lens, entry="sdp_hard_affine_global_walk_f32", **kw)
 
     # ---- alignments sampled from the posterior (include/sdp.h: sdp_sample_paths_*) -------------------
     def sample_paths(self, state, shape, variant, K, lens=None, seed=0, sample0=0, exact_state=False, transposed=False,
@@ -1048,6 +1072,9 @@ AFFINE_LOCAL_SAMPLE_KERNELS = {164: "sdp_affine_local_tables_kernel", 165: "sdp_
 HARD_AFFINE_LOCAL_KERNELS = {170: "sdp_hard_affine_local_fwd_kernel", 171: "sdp_hard_affine_local_fwd_t_kernel",
                              172: "sdp_hard_affine_local_val_kernel", 173: "sdp_hard_affine_local_val_t_kernel",
                              174: "sdp_hard_affine_local_walk_kernel"}
+# the sweeps of its global member (the same header); the walk is kernel 174
+HARD_AFFINE_GLOBAL_KERNELS = {185: "sdp_hard_affine_global_fwd_kernel", 186: "sdp_hard_affine_global_fwd_t_kernel",
+                              187: "sdp_hard_affine_global_val_kernel", 188: "sdp_hard_affine_global_val_t_kernel"}
 
 _SWEEPS = ("sdp_forward", "sdp_backward", "sdp_adjoint_forward", "sdp_adjoint_backward")
 # dtype -> (suffix of the four sweeps' entries, their launch labels (float32: where the library's plan is not asked),

@@ -29,7 +29,9 @@ Out of scope, none of it built: the third order, float64, the `distributed` wrap
 (their protocols have two tensors, this operator three).
 
 The GLOBAL form -- a path from cell (1,1) to cell (n,m), the Gotoh form of Needleman-Wunsch -- is AffineGlobalDecoder at the end of
-this file (include/sdp.h: sdp_affine_global_*): first order, softmax only.
+this file (include/sdp.h: sdp_affine_global_*): first order.  Its hard (max-plus) member is built as well
+(include/sdp.h: sdp_hard_affine_global_*): the optimal affine-gap Needleman-Wunsch (Gotoh) alignment --
+AffineGlobalDecoder.optimal_paths / optimal_alignments / optimal_score on every decoder, and AffineGlobalDecoder(operator="hardmax").
 """
 import torch
 
@@ -386,6 +388,45 @@ class AffineGlobalFunction(torch.autograd.Function):
         return E, GO, GX, None
 
 
+class HardAffineGlobalFunctionBackward(torch.autograd.Function):
+    """(E, GO, GX) of the walk along the optimal global path.  Differentiable in nothing: the max-plus score is piecewise linear,
+    and this is the node at which a second differentiation stops."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, Et, state, ends, lens, ymx, want_E, want_GO, want_GX):
+        # (the three inputs are here for the graph alone: a second differentiation must arrive below)
+        E, GO, GX, _, _ = _engine.get_engine().hard_affine_global_walk(state, ends, tuple(theta.shape), lens, Et=Et, ymx=ymx, want_E=want_E,
+                                                                       want_GO=want_GO, want_GX=want_GX, want_states=False)
+        return E, GO, GX
+
+    @staticmethod
+    def backward(ctx, ZE, ZGO, ZGX):
+        raise NotImplementedError("the hard affine-gap global operator is first order only: its second order is not built (the "
+                                  "max-plus score is piecewise linear)")
+
+
+class HardAffineGlobalFunction(torch.autograd.Function):
+    """Vt = the optimal affine-gap global alignment's score; backward: theta.grad = E, gap_open.grad = GO, gap_extend.grad = GX, the
+    indicator matrices of the optimal path times Et -- one walk; only the ones whose input needs a gradient.  Once differentiable.
+    ymx: the tensors are a transposed problem (ties as the problem before it was transposed)."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, lens=None, ymx=False):
+        Vt, state, ends = _engine.get_engine().hard_affine_global_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lens, ymx=ymx)
+        ctx.save_for_backward(theta, gap_open, gap_extend, state, ends)
+        ctx.lens, ctx.ymx = lens, ymx
+        return Vt
+
+    @staticmethod
+    def backward(ctx, Et):
+        theta, gap_open, gap_extend, state, ends = ctx.saved_tensors
+        want = ctx.needs_input_grad[:3]
+        if not any(want):
+            return None, None, None, None, None
+        E, GO, GX = HardAffineGlobalFunctionBackward.apply(theta, gap_open, gap_extend, Et, state, ends, ctx.lens, ctx.ymx, *want)
+        return E, GO, GX, None, None
+
+
 class AffineGlobalDecoder(torch.nn.Module):
     """Affine-gap GLOBAL alignment scores, their gradients and the posterior alignment matrix, on a ROCm device in float32: a
     differentiable Needleman-Wunsch in which opening a gap and extending it are priced separately, the Gotoh global form
@@ -417,18 +458,40 @@ class AffineGlobalDecoder(torch.nn.Module):
     and an empty pair has Vt = 0.  Problems wider than the column limit (2048) are swept transposed -- the operator is symmetric
     under transposition with x <-> y -- and the results come back in the caller's coordinates; both sides above the limit raise
     ValueError.  Non-fp32 or non-tensor input: TypeError; a shape mismatch: ValueError.
-    Out of scope, none of it built: the hard-max member and its walk, sampling, the second order, float64, the `distributed`
-    wrappers, `search_scores`, `losses.decode_loss`, free end gaps, and the reference's zero border."""
+    operator: "softmax" (the default: everything above) or "hardmax" -- the hard-max (max-plus) member of the family, the classical
+    Gotoh affine-gap Needleman-Wunsch (include/sdp.h: sdp_hard_affine_global_*): forward returns the optimal global
+    alignment's score, differentiable once, with the subgradients of perceptron or margin training (theta.grad = Et on the optimal
+    path, gap_open.grad / gap_extend.grad = Et on its gap cells that open / extend; only the ones asked for are computed); decode
+    returns the path's indicator matrix; score is optimal_score; a second differentiation raises NotImplementedError.  Adds and
+    compares only: the bits of the plain fp32 loop over cells.  Where no path exists Vt = -inf and the subgradients are +0.  Any
+    other string: ValueError.
+    optimal_paths / optimal_alignments / optimal_score: the optimal alignment itself, on every decoder whatever its operator.
+    Out of scope, none of it built: sampling, the second order, float64, the `distributed` wrappers, `search_scores`,
+    `losses.decode_loss`, free end gaps, and the reference's zero border."""
+
+    def __init__(self, operator="softmax"):
+        super().__init__()
+        if operator not in ("softmax", "hardmax"):
+            raise ValueError(f"operator must be 'softmax' or 'hardmax', got {operator!r}")
+        self.operator = operator
 
     def forward(self, theta, gap_open, gap_extend, lengths=None):
         _validate(theta, gap_open, gap_extend)
-        theta, gap_open, gap_extend, lengths, _ = _oriented(theta, gap_open, gap_extend, lengths)
+        theta, gap_open, gap_extend, lengths, transposed = _oriented(theta, gap_open, gap_extend, lengths)
+        if self.operator == "hardmax":
+            return HardAffineGlobalFunction.apply(theta, gap_open, gap_extend, lengths, transposed)
         return AffineGlobalFunction.apply(theta, gap_open, gap_extend, lengths)
 
     def decode(self, theta, gap_open, gap_extend, lengths=None):
         _validate(theta, gap_open, gap_extend)
         theta, gap_open, gap_extend, lengths, transposed = _oriented(theta, gap_open, gap_extend, lengths)
         eng = _engine.get_engine()
+        if self.operator == "hardmax":
+            with torch.no_grad():
+                _, state, ends = eng.hard_affine_global_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths, ymx=transposed)
+                E = eng.hard_affine_global_walk(state, ends, tuple(theta.shape), lengths, ymx=transposed, want_states=False,
+                                                Et=torch.ones((), dtype=torch.float32, device=theta.device))[0]
+            return E.transpose(1, 2) if transposed else E
         with torch.no_grad():
             _, state = eng.affine_global_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths)
             E, _, _ = eng.affine_global_backward(state, torch.ones((), dtype=torch.float32, device=theta.device), tuple(theta.shape),
@@ -436,7 +499,50 @@ class AffineGlobalDecoder(torch.nn.Module):
         return E.transpose(1, 2) if transposed else E
 
     def score(self, theta, gap_open, gap_extend, lengths=None):
+        if self.operator == "hardmax":
+            return self.optimal_score(theta, gap_open, gap_extend, lengths)
         _validate(theta, gap_open, gap_extend)
         theta, gap_open, gap_extend, lengths, _ = _oriented(theta, gap_open, gap_extend, lengths)
         with torch.no_grad():
             return _engine.get_engine().affine_global_forward_value(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths)
+
+    def optimal_paths(self, theta, gap_open, gap_extend, lengths=None):
+        """The optimal (max-plus) affine-gap global alignment of every pair under the scores given -> (Vt (B,), states (B, cap, 3)
+        int32, counts (B,) int32), device tensors without an autograd graph, in the format of AffineLocalDecoder.optimal_paths:
+        pair b's list is states[b, :counts[b]], rows (i, j, state), from cell (0, 0) to cell (n_b - 1, m_b - 1); empty
+        (counts[b] = 0) for an empty pair (Vt[b] = 0) and for a pair without a path (Vt[b] = -inf); states[b, cap - 1] is (number
+        of path cells, i, j of the first one), (0, -1, -1) for an empty list.  state: the plane of the cell -- 0 / 2 a cell entered
+        through a gap step (x / y), 1 through a diagonal step or the start.  Available whatever the operator.  One sweep that
+        stores 6 bits per cell, one walk per pair."""
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, transposed = _oriented(theta, gap_open, gap_extend, lengths)
+        eng = _engine.get_engine()
+        with torch.no_grad():
+            Vt, state, ends = eng.hard_affine_global_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths, ymx=transposed)
+            _, _, _, states, counts = eng.hard_affine_global_walk(state, ends, tuple(theta.shape), lengths, ymx=transposed, want_E=False)
+            if transposed:
+                scratch = states[:, -1]
+                states = states[..., [1, 0, 2]].contiguous()
+                states[:, -1] = scratch[:, [0, 2, 1]]     # (number of path cells, first i, first j): the count stays in front
+        return Vt, states, counts
+
+    def optimal_alignments(self, theta, gap_open, gap_extend, lengths=None):
+        """optimal_paths() as lists: (Vt, list of B lists of (i, j, state))."""
+        Vt, states, counts = self.optimal_paths(theta, gap_open, gap_extend, lengths)
+        states, counts = states.cpu().numpy(), counts.cpu().numpy()
+        return Vt, [[tuple(int(v) for v in row) for row in states[b, :counts[b]]] for b in range(len(counts))]
+
+    def optimal_score(self, theta, gap_open, gap_extend, lengths=None, return_ends=False):
+        """Vt (B,) of optimal_paths() through the value-only sweep: no pointers are stored, no graph.  return_ends: -> (Vt, ends
+        (B, 3) int32), the 0-based last cell (n_b - 1, m_b - 1) and the plane each pair's optimal alignment ends in, (-1, -1, -1)
+        where there is no path."""
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, transposed = _oriented(theta, gap_open, gap_extend, lengths)
+        with torch.no_grad():
+            Vt, ends = _engine.get_engine().hard_affine_global_forward_value(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths,
+                                                                             ymx=transposed, want_ends=bool(return_ends))
+            if not return_ends:
+                return Vt
+            if transposed:   # (j, i) and the other gap plane; no end stays (-1, -1, -1)
+                ends = torch.stack([ends[:, 1], ends[:, 0], torch.where(ends[:, 2] < 0, ends[:, 2], 2 - ends[:, 2])], dim=1).contiguous()
+        return Vt, ends

@@ -650,7 +650,11 @@ int raise_hard_affine_limit(int device)
                                {(const void *)sdp_hard_affine_local_fwd_t_kernel, "hipFuncSetAttribute(sdp_hard_affine_local_fwd_t_kernel)"},
                                {(const void *)sdp_hard_affine_local_val_kernel, "hipFuncSetAttribute(sdp_hard_affine_local_val_kernel)"},
                                {(const void *)sdp_hard_affine_local_val_t_kernel, "hipFuncSetAttribute(sdp_hard_affine_local_val_t_kernel)"},
-                               {(const void *)sdp_hard_affine_local_walk_kernel, "hipFuncSetAttribute(sdp_hard_affine_local_walk_kernel)"}},
+                               {(const void *)sdp_hard_affine_local_walk_kernel, "hipFuncSetAttribute(sdp_hard_affine_local_walk_kernel)"},
+                               {(const void *)sdp_hard_affine_global_fwd_kernel, "hipFuncSetAttribute(sdp_hard_affine_global_fwd_kernel)"},
+                               {(const void *)sdp_hard_affine_global_fwd_t_kernel, "hipFuncSetAttribute(sdp_hard_affine_global_fwd_t_kernel)"},
+                               {(const void *)sdp_hard_affine_global_val_kernel, "hipFuncSetAttribute(sdp_hard_affine_global_val_kernel)"},
+                               {(const void *)sdp_hard_affine_global_val_t_kernel, "hipFuncSetAttribute(sdp_hard_affine_global_val_t_kernel)"}},
                               sdp_hard_affine::LDS_BUDGET);
 }
 
@@ -831,6 +835,11 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_hard_affine::ID_VAL: return "sdp_hard_affine_local_val_kernel";
     case sdp_hard_affine::ID_VAL_T: return "sdp_hard_affine_local_val_t_kernel";
     case sdp_hard_affine::ID_WALK: return "sdp_hard_affine_local_walk_kernel";
+    // its global member's sweeps (the same file; the walk is the local member's)
+    case sdp_hard_affine::ID_GLOBAL_FWD: return "sdp_hard_affine_global_fwd_kernel";
+    case sdp_hard_affine::ID_GLOBAL_FWD_T: return "sdp_hard_affine_global_fwd_t_kernel";
+    case sdp_hard_affine::ID_GLOBAL_VAL: return "sdp_hard_affine_global_val_kernel";
+    case sdp_hard_affine::ID_GLOBAL_VAL_T: return "sdp_hard_affine_global_val_t_kernel";
     // the affine-gap soft global operator (csrc/sdp_affine_global.hip)
     case sdp_affine_global::ID_FWD: return "sdp_affine_global_fwd_kernel";
     case sdp_affine_global::ID_VAL: return "sdp_affine_global_val_kernel";
@@ -1806,7 +1815,7 @@ static int hard_affine_args(int variant, int B, int N, int M, bool &ymx, int &wa
     waves = take_waves(variant);
     variant &= ~SDP_HARD_TIES_YMX;
     if (int rc = check_shape(B, N, M, SDP_NW)) return rc;
-    if (variant != 0) return fail(SDP_E_VARIANT, "sdp_hard_affine_local_*: variant takes SDP_HARD_TIES_YMX and SDP_WAVES(w) only");
+    if (variant != 0) return fail(SDP_E_VARIANT, "sdp_hard_affine_{local,global}_*: variant takes SDP_HARD_TIES_YMX and SDP_WAVES(w) only");
     if ((size_t)B * (size_t)N * (size_t)M > ((size_t)1 << 31)) return fail(SDP_E_TOOBIG, "B*N*M exceeds 2^31 elements");
     return 0;
 }
@@ -1818,7 +1827,8 @@ size_t sdp_hard_affine_local_state_bytes(int B, int N, int M)
 }
 
 static int hard_affine_forward(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int32_t *ends,
-                               int B, int N, int M, const int32_t *lens, int variant, int device, void *stream, bool pointers)
+                               int B, int N, int M, const int32_t *lens, int variant, int device, void *stream, bool pointers,
+                               bool global = false)
 {
     bool ymx;
     int waves;
@@ -1828,9 +1838,14 @@ static int hard_affine_forward(const float *theta, const float *gap_open, const 
     const int W = sdp_hard_affine::waves_for(N, M, waves);
     auto kernel = pointers ? (ymx ? sdp_hard_affine_local_fwd_t_kernel : sdp_hard_affine_local_fwd_kernel)
                            : (ymx ? sdp_hard_affine_local_val_t_kernel : sdp_hard_affine_local_val_kernel);
-    return strip_launch(kernel, pointers ? "sdp_hard_affine_local_fwd_kernel" : "sdp_hard_affine_local_val_kernel", B, W,
-                        sdp_hard_affine::sweep_lds_bytes(W, M), stream, theta, gap_open, gap_extend, static_cast<uint32_t *>(state), Vt, ends,
-                        lens, N, M, W);
+    const char *name = pointers ? "sdp_hard_affine_local_fwd_kernel" : "sdp_hard_affine_local_val_kernel";
+    if (global) {
+        kernel = pointers ? (ymx ? sdp_hard_affine_global_fwd_t_kernel : sdp_hard_affine_global_fwd_kernel)
+                          : (ymx ? sdp_hard_affine_global_val_t_kernel : sdp_hard_affine_global_val_kernel);
+        name = pointers ? "sdp_hard_affine_global_fwd_kernel" : "sdp_hard_affine_global_val_kernel";
+    }
+    return strip_launch(kernel, name, B, W, sdp_hard_affine::sweep_lds_bytes(W, M), stream, theta, gap_open, gap_extend,
+                        static_cast<uint32_t *>(state), Vt, ends, lens, N, M, W);
 }
 
 int sdp_hard_affine_local_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt,
@@ -1862,6 +1877,31 @@ int sdp_hard_affine_local_walk_f32(const void *state, const int32_t *ends, const
     return strip_launch(sdp_hard_affine_local_walk_kernel, "sdp_hard_affine_local_walk_kernel", B, 1, sdp_hard_affine::walk_lds_bytes(M),
                         stream, static_cast<const uint32_t *>(state), ends, Et, E, GO, GX, states, counts, lens, N, M,
                         sdp_traceback_capacity(N, M), ymx ? 1 : 0);
+}
+
+// ---- the hard affine-gap global operator (csrc/sdp_hard_affine.hip, GLOBAL builds): the local member's checks, state and walk ----
+size_t sdp_hard_affine_global_state_bytes(int B, int N, int M) { return sdp_hard_affine_local_state_bytes(B, N, M); }
+
+int sdp_hard_affine_global_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt,
+                                       int32_t *ends, int B, int N, int M, const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!theta || !gap_open || !gap_extend || !state || !Vt || !ends)
+        return fail(SDP_E_NULLPTR, "sdp_hard_affine_global_forward_f32: null pointer");
+    return hard_affine_forward(theta, gap_open, gap_extend, state, Vt, ends, B, N, M, lens, variant, device, stream, true, true);
+}
+
+int sdp_hard_affine_global_forward_value_f32(const float *theta, const float *gap_open, const float *gap_extend, float *Vt, int32_t *ends,
+                                             int B, int N, int M, const int32_t *lens, int variant, int device, void *stream)
+{
+    if (!theta || !gap_open || !gap_extend || !Vt) return fail(SDP_E_NULLPTR, "sdp_hard_affine_global_forward_value_f32: null pointer");
+    return hard_affine_forward(theta, gap_open, gap_extend, nullptr, Vt, ends, B, N, M, lens, variant, device, stream, false, true);
+}
+
+// (the state format, `ends` and the stop at START are the local member's: one walk kernel serves both)
+int sdp_hard_affine_global_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, float *GO, float *GX, int32_t *states,
+                                    int32_t *counts, int B, int N, int M, const int32_t *lens, int variant, int device, void *stream)
+{
+    return sdp_hard_affine_local_walk_f32(state, ends, Et, E, GO, GX, states, counts, B, N, M, lens, variant, device, stream);
 }
 
 // ---- the affine-gap soft global operator (csrc/sdp_affine_global.hip): the Gotoh form of Needleman-Wunsch, first order ----

@@ -1,4 +1,4 @@
-// sdp_hard_affine.h -- the hard (max-plus) affine-gap local kernel family (csrc/sdp_hard_affine.hip): launch geometry shared with the host side.
+// sdp_hard_affine.h -- the hard (max-plus) affine-gap kernel family, local and global (csrc/sdp_hard_affine.hip): launch geometry shared with the host side.
 #ifndef SDP_HARD_AFFINE_H_
 #define SDP_HARD_AFFINE_H_
 
@@ -43,6 +43,8 @@ __host__ __device__ inline size_t pair_words(int N, int M) { return (size_t)stri
 
 // kernel ids sdp_kernel_name answers for (169 and 175 answer NULL)
 enum { ID_FWD = 170, ID_FWD_T = 171, ID_VAL = 172, ID_VAL_T = 173, ID_WALK = 174 };
+// the global member's sweeps (184 and 189 answer NULL); its walk is ID_WALK
+enum { ID_GLOBAL_FWD = 185, ID_GLOBAL_FWD_T = 186, ID_GLOBAL_VAL = 187, ID_GLOBAL_VAL_T = 188 };
 
 }  // namespace sdp_hard_affine
 
@@ -55,6 +57,14 @@ __global__ void sdp_hard_affine_local_val_kernel(const float *theta, const float
                                                  const int *lens, int N, int M, int waves);
 __global__ void sdp_hard_affine_local_val_t_kernel(const float *theta, const float *O, const float *X, uint32_t *state, float *Vt, int *ends,
                                                    const int *lens, int N, int M, int waves);
+__global__ void sdp_hard_affine_global_fwd_kernel(const float *theta, const float *O, const float *X, uint32_t *state, float *Vt, int *ends,
+                                                  const int *lens, int N, int M, int waves);
+__global__ void sdp_hard_affine_global_fwd_t_kernel(const float *theta, const float *O, const float *X, uint32_t *state, float *Vt, int *ends,
+                                                    const int *lens, int N, int M, int waves);
+__global__ void sdp_hard_affine_global_val_kernel(const float *theta, const float *O, const float *X, uint32_t *state, float *Vt, int *ends,
+                                                  const int *lens, int N, int M, int waves);
+__global__ void sdp_hard_affine_global_val_t_kernel(const float *theta, const float *O, const float *X, uint32_t *state, float *Vt, int *ends,
+                                                    const int *lens, int N, int M, int waves);
 __global__ void sdp_hard_affine_local_walk_kernel(const uint32_t *state, const int *ends, const float *Et, float *E, float *GO, float *GX,
                                                   int *states, int *counts, const int *lens, int N, int M, int cap, int ymx);
 }

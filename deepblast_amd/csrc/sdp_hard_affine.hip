@@ -10,7 +10,7 @@
 // Adds and compares only: every build gives the bits of the plain loop over cells.  It is the max-plus member of the affine
 // family (csrc/sdp_affine_local.hip) as sdp_hard_local_* is of the one-score family (csrc/sdp_hard.hip), and is put together from
 // those two: the strip schedule, three planes handed down through LDS and moved by DPP, inputs loaded half a chunk ahead are the
-// former's; the pointer lines, the running best, its join and the walk the latter's.  Five kernels:
+// former's; the pointer lines, the running best, its join and the walk the latter's.  Five kernels (and four of the global member):
 //
 //   sweeps    one workgroup per pair, one wave per strip of 64 rows (lane = row), swept along the anti-diagonals: at step s lane l
 //             is at column s - l, the three H[i-1,j] arrive from lane l - 1 by DPP, the three H[i-1,j-1] are what arrived one step
@@ -29,6 +29,11 @@
 // Tie order: the default scans are x, m, y.  The TRANSPOSED builds serve problems that are swept as (M, N) because M exceeds the
 // column limit: every scan is then y, m, x (START still first), the first maximum over cells is taken column-major, and the walk
 // names plane x y and plane y x -- so Vt, the end and the path do not depend on which way a problem was swept.
+//
+// The GLOBAL member (include/sdp.h: sdp_hard_affine_global_*) is the same sweep template with one more flag: START
+// at cell (1,1) alone and no zero floor, a path from (1,1) to (n,m), Vt the first maximum of the last cell's three planes, which
+// the lane of row n captures where its column is m -- there is no running best and no join.  Four more sweep kernels; the state
+// format, ends and the stop at START are the same, so the walk above serves both members.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -98,8 +103,10 @@ __device__ __forceinline__ bool better_end(float v1, int r1, int c1, float v0, i
 }
 
 // PTR: write the pointers (else: the value-only sweep); YMX: every scan y, m, x and the first maximum over cells column-major.
+// GLOBAL: the Gotoh form of Needleman-Wunsch -- START at cell (0, 0) alone and no zero floor, no running best:
+// the lane of row n - 1 keeps its three plane values at column m - 1, and Vt is their first maximum in scan order.
 // ends may be NULL.
-template <bool PTR, bool YMX>
+template <bool PTR, bool YMX, bool GLOBAL>
 __device__ __forceinline__ void hard_affine_forward(const float *theta, const float *O, const float *X, uint32_t *state, float *Vt, int *ends,
                                                     const int *lens, int N, int M, int W)
 {
@@ -138,6 +145,9 @@ __device__ __forceinline__ void hard_affine_forward(const float *theta, const fl
     // ... and of all the rows this lane has finished
     float bv = 0.f;
     int brw = -1, bcode = -4;
+    // GLOBAL: the three planes of cell (n - 1, m - 1), kept by lane (n - 1) % 64 of the wave that sweeps the pair's last strip
+    float ex = NINF, em = NINF, ey = NINF;
+    const int endlane = (n - 1) & (STRIP - 1);
 
     for (int tick = 0;; ++tick) {
         __syncthreads();
@@ -160,6 +170,8 @@ __device__ __forceinline__ void hard_affine_forward(const float *theta, const fl
             // steps t with col >= 0 and t < tlim are cells of the pair: rows >= n and columns >= m compute values nobody reads, and
             // they do not enter the best
             const int tlim = (row1 <= n ? m : 0) - colb;
+            // GLOBAL: the step of this chunk at which this lane is at the pair's last cell (in no chunk but one, in no lane but one)
+            const int tend = (s == S - 1 && lane == endlane) ? m - 1 - colb : -1;
             uint32_t bits[PLANES][CHUNK / PTR_STEPS] = {{0u, 0u}, {0u, 0u}, {0u, 0u}};
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -177,7 +189,8 @@ __device__ __forceinline__ void hard_affine_forward(const float *theta, const fl
                     // plane m: "start here" is a candidate, taken before theta and first in every scan
                     uint32_t km, kx, ky;
                     float mbest = first_max<YMX>(dx, dm, dy, km);
-                    const bool cont = mbest > 0.f;
+                    // (GLOBAL: the path starts at cell (0, 0) and nowhere else, and nothing is floored)
+                    const bool cont = GLOBAL ? !(s == 0 && lane == 0 && col == 0) : mbest > 0.f;
                     mbest = cont ? mbest : 0.f;
                     km = cont ? km : (uint32_t)START;
                     float nvm = th[tt] + mbest;
@@ -197,7 +210,10 @@ __device__ __forceinline__ void hard_affine_forward(const float *theta, const fl
                         // masks alive to the end of the chunk and spills some 500 scalar registers)
                         asm volatile("" : "+v"(bits[0][t / PTR_STEPS]), "+v"(bits[1][t / PTR_STEPS]), "+v"(bits[2][t / PTR_STEPS]));
                     }
-                    {   // the cell's planes join the row's best in scan order (a lane that has not started holds -inf: never a best)
+                    if (GLOBAL) {
+                        const bool last = t == tend;
+                        ex = last ? nvx : ex, em = last ? nvm : em, ey = last ? nvy : ey;
+                    } else {   // the cell's planes join the row's best in scan order (a lane that has not started holds -inf: never a best)
                         const bool cell = t < tlim;
                         const int code = 4 * col;
                         const float p0 = YMX ? nvy : nvx, p2 = YMX ? nvx : nvy;
@@ -233,13 +249,23 @@ __device__ __forceinline__ void hard_affine_forward(const float *theta, const fl
                     for (int p = 0; p < PLANES; ++p) dst[(q * PLANES + p) * STRIP] = bits[p][q];
             }
             if (ns != s) {   // the row is finished: it joins the lane's best, and the next row starts from nothing
-                if (better_end<YMX>(rv, row1 - 1, rcode >> 2, bv, brw, bcode >> 2)) bv = rv, brw = row1 - 1, bcode = rcode;
+                if (!GLOBAL && better_end<YMX>(rv, row1 - 1, rcode >> 2, bv, brw, bcode >> 2)) bv = rv, brw = row1 - 1, bcode = rcode;
                 rv = 0.f, rcode = -4;
                 vx = NINF, vm = NINF, vy = NINF, dx = NINF, dm = NINF, dy = NINF;
             }
             s = ns, c = nc;
         }
         if (lane == 0) kw[w] = s * KEY + c;
+    }
+    if (GLOBAL) {   // one lane holds the end cell: the first maximum of its planes in scan order, no end where all are -inf
+        if (w == lastw && lane == endlane) {
+            uint32_t k;
+            const float best = first_max<YMX>(ex, em, ey, k);
+            const bool any = best > NINF;
+            Vt[b] = best;
+            if (ends) ends[3 * b] = any ? n - 1 : -1, ends[3 * b + 1] = any ? m - 1 : -1, ends[3 * b + 2] = any ? (int)k : -1;
+        }
+        return;
     }
     // every strip is complete and every wave has left the loop at the same barrier: the boundary rows are free.  One reduction
     // over the wave by shuffles, one over the waves through LDS.
@@ -269,25 +295,51 @@ extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_local_fwd_kern
                                                                                    uint32_t *state, float *Vt, int *ends, const int *lens,
                                                                                    int N, int M, int waves)
 {
-    hard_affine_forward<true, false>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+    hard_affine_forward<true, false, false>(theta, O, X, state, Vt, ends, lens, N, M, waves);
 }
 extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_local_fwd_t_kernel(const float *theta, const float *O, const float *X,
                                                                                      uint32_t *state, float *Vt, int *ends, const int *lens,
                                                                                      int N, int M, int waves)
 {
-    hard_affine_forward<true, true>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+    hard_affine_forward<true, true, false>(theta, O, X, state, Vt, ends, lens, N, M, waves);
 }
 extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_local_val_kernel(const float *theta, const float *O, const float *X,
                                                                                    uint32_t *state, float *Vt, int *ends, const int *lens,
                                                                                    int N, int M, int waves)
 {
-    hard_affine_forward<false, false>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+    hard_affine_forward<false, false, false>(theta, O, X, state, Vt, ends, lens, N, M, waves);
 }
 extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_local_val_t_kernel(const float *theta, const float *O, const float *X,
                                                                                      uint32_t *state, float *Vt, int *ends, const int *lens,
                                                                                      int N, int M, int waves)
 {
-    hard_affine_forward<false, true>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+    hard_affine_forward<false, true, false>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+}
+
+// the global member's four sweeps: the same arguments, the same state, the same walk
+extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_global_fwd_kernel(const float *theta, const float *O, const float *X,
+                                                                                    uint32_t *state, float *Vt, int *ends, const int *lens,
+                                                                                    int N, int M, int waves)
+{
+    hard_affine_forward<true, false, true>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+}
+extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_global_fwd_t_kernel(const float *theta, const float *O, const float *X,
+                                                                                      uint32_t *state, float *Vt, int *ends, const int *lens,
+                                                                                      int N, int M, int waves)
+{
+    hard_affine_forward<true, true, true>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+}
+extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_global_val_kernel(const float *theta, const float *O, const float *X,
+                                                                                    uint32_t *state, float *Vt, int *ends, const int *lens,
+                                                                                    int N, int M, int waves)
+{
+    hard_affine_forward<false, false, true>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+}
+extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_global_val_t_kernel(const float *theta, const float *O, const float *X,
+                                                                                      uint32_t *state, float *Vt, int *ends, const int *lens,
+                                                                                      int N, int M, int waves)
+{
+    hard_affine_forward<false, true, true>(theta, O, X, state, Vt, ends, lens, N, M, waves);
 }
 
 namespace {

@@ -828,6 +828,34 @@ int sdp_hard_affine_local_forward_value_f32(const float *theta, const float *gap
 int sdp_hard_affine_local_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, float *GO, float *GX, int32_t *states,
                                    int32_t *counts, int B, int N, int M, const int32_t *lens, int variant, int device, void *stream);
 
+/* The HARD AFFINE-GAP GLOBAL operator (csrc/sdp_hard_affine.hip): the max-plus member of the affine-gap global family
+ * below -- the optimal affine-gap Needleman-Wunsch (Gotoh) alignment of every pair, from cell (1,1) to cell (n,m): its score, its
+ * end plane and its path.  (Added after SDP_VERSION 106 without a version change: look the symbols up.)  Adds and compares only:
+ * the results are the BITS of this loop, in the notation of the local operator above:
+ *
+ *     for i in 1..n, j in 1..m:
+ *         m plane: at cell (1,1): H[1,1,m] = t + (+0), P = 3 (START);  elsewhere  c = H[i-1,j-1,(x,m,y)], k = FIRST maximum
+ *                  (strict '>'), H[i,j,m] = t + c[k], P[i,j,m] = k
+ *         x plane, y plane: as in the local operator
+ *     Vt  = the FIRST maximum of H[n,m,(x,m,y)];  end = (n, m, that plane) if Vt > -inf, else none
+ *     path: as in the local operator, from end; it stops at cell (1,1), the only START
+ *
+ * There is NO zero floor.  theta is finite, O and X are finite or -inf; -inf + finite and -inf + -inf are -inf, +inf never arises and
+ * nothing is NaN.  Where all three candidates are -inf the pointer is the first of the scan; the walk never visits such a cell.  A
+ * pair without a path (n != m with every gap forbidden, or -inf masks that cut every route): Vt = -inf, ends = (-1, -1, -1), an
+ * empty list with counts 0 and scratch row (0, -1, -1), E, GO and GX +0.  An empty pair (n < 1 or m < 1): Vt = +0, no end, an empty
+ * list.  variant, state, ends, the walk's outputs, the limits and the error codes are the local operator's;
+ * SDP_HARD_TIES_YMX scans y, m, x everywhere, the end cell's planes included.  sdp_hard_affine_global_state_bytes is
+ * sdp_hard_affine_local_state_bytes and sdp_hard_affine_global_walk_f32 is sdp_hard_affine_local_walk_f32 (the state format, ends
+ * and the stop at START are the same): they are here so that the family is whole.  ends may be NULL in the value entry. */
+size_t sdp_hard_affine_global_state_bytes(int B, int N, int M);
+int sdp_hard_affine_global_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt,
+                                       int32_t *ends, int B, int N, int M, const int32_t *lens, int variant, int device, void *stream);
+int sdp_hard_affine_global_forward_value_f32(const float *theta, const float *gap_open, const float *gap_extend, float *Vt, int32_t *ends,
+                                             int B, int N, int M, const int32_t *lens, int variant, int device, void *stream);
+int sdp_hard_affine_global_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, float *GO, float *GX, int32_t *states,
+                                    int32_t *counts, int B, int N, int M, const int32_t *lens, int variant, int device, void *stream);
+
 /* The AFFINE-GAP SOFT GLOBAL operator (csrc/sdp_affine_global.hip): a differentiable Needleman-Wunsch with opening a
  * gap and extending it priced separately -- the Gotoh global form.  (Added after SDP_VERSION 106 without a version change: look the
  * symbols up.)  Notation of the affine-gap soft local operator above: (n, m) = lens[b] clamped or (N, M), cells 1-based, theta,
@@ -853,7 +881,7 @@ int sdp_hard_affine_local_walk_f32(const void *state, const int32_t *ends, const
  * Arithmetic: the sweep carries exp V scaled -- three fp32 mantissas on one integer exponent per cell -- and rebuilds Vt once per
  * pair in float64.  Its envelope: a score below -2^24 / log2(e) = -1.16e7 counts as -inf; a plane more than 2^126 below the largest
  * plane of its cell, and a cell whose weight falls below 2^(-2^29), are flushed to zero.
- * NOT built: the hard-max member and its walk, sampling, the second order, float64, free end gaps, the reference's zero border.
+ * NOT built (the hard-max member is sdp_hard_affine_global_* above): sampling, the second order, float64, free end gaps, the reference's zero border.
  *   state    sdp_affine_global_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: 48 bytes per cell -- one record
  *            {q[s<-x], q[s<-m], q[s<-y], w_s} per plane s, w_s zero but in the end cell -- in a private layout; written by
  *            sdp_affine_global_forward_f32, read by sdp_affine_global_backward_f32 with the same B, N, M, lens (which needs neither
