@@ -876,6 +876,36 @@ class HipEngine:
         self.call("sdp_affine_global_backward_f32", AFFINE_GLOBAL_KERNELS[182], dev, state, Et, E, GO, GX, B, N, M, lens, 0)
         return E, GO, GX
 
+    # ---- alignments sampled from its posterior (include/sdp.h: sdp_affine_global_sample_paths_f32) ----
+    def affine_global_sample_paths(self, state, shape, K, lens=None, seed=0, sample0=0, want_states=True, want_visits=False,
+                                   want_opens=False, want_extends=False, want_ends=False):
+        """K global alignments per pair drawn from the posterior, on the `state` of affine_global_forward (the end weights are in
+        it: no Vt, no tables) -> (states (B,K,cap,3) int32 or None, counts (B,K) int32 or None, visits, opens, extends (B,N,M)
+        int32 or None, ends (B,K,3) int32 or None), in the formats of affine_local_sample_paths: the list of sample (b, k) -- sample
+        number sample0 + k of pair b under `seed` whatever K is -- runs from cell (0, 0) to cell (n_b - 1, m_b - 1), rows (i, j,
+        plane), RIGHT-aligned in states[b, k]: rows cap-1-counts[b,k] .. cap-2, and row cap-1 holds (number of path cells, i, j of
+        the first one), (0, -1, -1) for an empty sample -- an empty pair, or a pair without a path; rows in front of the list are
+        unspecified.  ends: (n_b - 1, m_b - 1, the end plane), (-1, -1, -1) for an empty sample.  visits: how many of the K paths
+        pass through each cell; opens / extends: how many of them open / extend a gap into it."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        if not (want_states or want_visits or want_opens or want_extends or want_ends):
+            raise ValueError("affine_global_sample_paths: nothing asked for (want_states, want_visits, want_opens, want_extends, want_ends)")
+        check_args(state, torch.float32, None, True, state=state)
+        lens = self._lens(lens, B, state.device)
+        states = counts = ends = None
+        if want_states:
+            cap = self.lib.sdp_traceback_capacity(N, M)
+            states = torch.empty((B, int(K), cap, 3), dtype=torch.int32, device=state.device)
+            counts = torch.empty((B, int(K)), dtype=torch.int32, device=state.device)
+        visits, opens, extends = (torch.zeros((B, N, M), dtype=torch.int32, device=state.device) if want else None
+                                  for want in (want_visits, want_opens, want_extends))
+        if want_ends:
+            ends = torch.empty((B, int(K), 3), dtype=torch.int32, device=state.device)
+        self.call("sdp_affine_global_sample_paths_f32", AFFINE_GLOBAL_SAMPLE_KERNELS[190], dev, state, states, counts, visits, opens,
+                  extends, ends, B, N, M, int(K), int(sample0), int(seed) & 0xffffffffffffffff, lens, 0)
+        return states, counts, visits, opens, extends, ends
+
     # ---- the hard affine-gap local operator (include/sdp.h: sdp_hard_affine_local_*) ------------
     def _hard_affine_variant(self, ymx, waves=True):
         """`variant` of the sdp_hard_affine_local_* entries; waves=False for the walk, which runs one wave per pair."""
@@ -1062,6 +1092,8 @@ SPARSEMAX_KERNELS = {150: "sdp_sparsemax_fwd_kernel", 151: "sdp_sparsemax_val_ke
 SPARSEMAX_ADJOINT_KERNELS = {154: "sdp_sparsemax_adj_fwd_kernel", 155: "sdp_sparsemax_adj_bwd_kernel"}
 # kernel id (csrc/sdp_affine_global.h) -> symbol of the affine-gap soft global operator's kernels
 AFFINE_GLOBAL_KERNELS = {180: "sdp_affine_global_fwd_kernel", 181: "sdp_affine_global_val_kernel", 182: "sdp_affine_global_bwd_kernel"}
+# and of the kernel that samples from its posterior (csrc/sdp_affine_global_sample.h)
+AFFINE_GLOBAL_SAMPLE_KERNELS = {190: "sdp_affine_global_sample_kernel"}
 # kernel id (csrc/sdp_affine_local.h) -> symbol of the affine-gap soft local operator's kernels
 AFFINE_LOCAL_KERNELS = {160: "sdp_affine_local_fwd_kernel", 161: "sdp_affine_local_val_kernel", 162: "sdp_affine_local_bwd_kernel"}
 # of its adjoint pair (the same header)

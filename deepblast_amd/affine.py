@@ -32,6 +32,8 @@ The GLOBAL form -- a path from cell (1,1) to cell (n,m), the Gotoh form of Needl
 this file (include/sdp.h: sdp_affine_global_*): first order.  Its hard (max-plus) member is built as well
 (include/sdp.h: sdp_hard_affine_global_*): the optimal affine-gap Needleman-Wunsch (Gotoh) alignment --
 AffineGlobalDecoder.optimal_paths / optimal_alignments / optimal_score on every decoder, and AffineGlobalDecoder(operator="hardmax").
+Sampling from the global posterior is built too (include/sdp.h: sdp_affine_global_sample_paths_f32):
+AffineGlobalDecoder.sample_paths / sample_alignments, on every decoder.
 """
 import torch
 
@@ -466,7 +468,10 @@ class AffineGlobalDecoder(torch.nn.Module):
     compares only: the bits of the plain fp32 loop over cells.  Where no path exists Vt = -inf and the subgradients are +0.  Any
     other string: ValueError.
     optimal_paths / optimal_alignments / optimal_score: the optimal alignment itself, on every decoder whatever its operator.
-    Out of scope, none of it built: sampling, the second order, float64, the `distributed` wrappers, `search_scores`,
+    sample_paths / sample_alignments: alignments drawn from the soft operator's posterior, on every decoder whatever its operator
+    (include/sdp.h: sdp_affine_global_sample_paths_f32); only sampling a problem that is swept transposed is out
+    of scope.
+    Out of scope, none of it built: the second order, float64, the `distributed` wrappers, `search_scores`,
     `losses.decode_loss`, free end gaps, and the reference's zero border."""
 
     def __init__(self, operator="softmax"):
@@ -546,3 +551,45 @@ class AffineGlobalDecoder(torch.nn.Module):
             if transposed:   # (j, i) and the other gap plane; no end stays (-1, -1, -1)
                 ends = torch.stack([ends[:, 1], ends[:, 0], torch.where(ends[:, 2] < 0, ends[:, 2], 2 - ends[:, 2])], dim=1).contiguous()
         return Vt, ends
+
+    def sample_paths(self, theta, gap_open, gap_extend, num_samples, lengths=None, seed=0, sample0=0, return_visits=False,
+                     return_gaps=False, return_ends=False):
+        """Global alignments drawn from the POSTERIOR the soft operator defines -- a path from cell (0, 0) to cell (n_b - 1,
+        m_b - 1) with probability exp(score - Vt); decode() of the softmax decoder returns its marginals, optimal_paths() its
+        mode -- from one forward sweep and one walk per sample (include/sdp.h: sdp_affine_global_sample_paths_f32; no tables: the
+        end cell is fixed and the sweep leaves the end weights in the state; no backward sweep).  Available whatever the operator.
+        -> (Vt (B,), states (B, K, cap, 3) int32, counts (B, K) int32[, visits (B, N, M) int32][, opens, extends (B, N, M)
+        int32][, ends (B, K, 3) int32]), K = num_samples, device tensors without an autograd graph, in the formats of
+        AffineLocalDecoder.sample_paths: sample k of pair b is states[b, k, :counts[b, k]], rows (i, j, plane), start first (rows
+        between the list and the last one are unspecified); states[b, k, cap - 1] is (number of path cells, i, j of the first
+        one), (0, -1, -1) for an empty sample, which has counts = 0: every sample of an empty pair (Vt = 0) and of a pair without
+        a path (Vt = -inf).  The start cell carries plane m (1).  visits: how many of the K paths pass through each cell; opens /
+        extends (return_gaps): how many of them enter it through a gap step that opens / extends a gap -- over K they estimate E,
+        GO and GX for Et = 1.  ends: (n_b - 1, m_b - 1, the plane the path ends in), (-1, -1, -1) for an empty sample.
+        The draws are reproducible: sample k is sample number sample0 + k of pair b under `seed` (a counter-based generator: 64
+        samples at sample0 = 0 are 32 at 0 followed by 32 at 32).
+        Problems wider than the column limit are swept transposed by forward() and decode(); sampling them is NOT built (the draw
+        must not depend on the sweep direction): ValueError."""
+        _validate(theta, gap_open, gap_extend)
+        K = int(num_samples)
+        if K < 1:
+            raise ValueError(f"num_samples must be positive, got {num_samples}")
+        eng = _engine.get_engine()
+        if theta.shape[2] > eng.max_cols():
+            raise ValueError(f"sample_paths is out of scope for problems swept transposed (M = {theta.shape[2]} exceeds the column "
+                             f"limit {eng.max_cols()}): sampling on a transposed state is not built")
+        with torch.no_grad():
+            Vt, state = eng.affine_global_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths)
+            states, counts, visits, opens, extends, ends = eng.affine_global_sample_paths(
+                state, tuple(theta.shape), K, lengths, seed=seed, sample0=sample0, want_visits=bool(return_visits),
+                want_opens=bool(return_gaps), want_extends=bool(return_gaps), want_ends=bool(return_ends))
+            states = left_aligned(states, counts)
+        return ((Vt, states, counts) + ((visits,) if return_visits else ()) + ((opens, extends) if return_gaps else ())
+                + ((ends,) if return_ends else ()))
+
+    def sample_alignments(self, theta, gap_open, gap_extend, num_samples, lengths=None, seed=0, sample0=0):
+        """sample_paths() as lists: (Vt, list of B lists of K lists of (i, j, plane)); an empty sample is an empty list."""
+        Vt, states, counts = self.sample_paths(theta, gap_open, gap_extend, num_samples, lengths, seed, sample0)
+        states, counts = states.cpu().numpy(), counts.cpu().numpy()
+        return Vt, [[[tuple(int(v) for v in row) for row in states[b, k, :counts[b, k]]] for k in range(counts.shape[1])]
+                    for b in range(counts.shape[0])]

@@ -18,6 +18,7 @@
 #include "sdp_soft_local_sample.h"
 #include "sdp_sparsemax.h"
 #include "sdp_affine_global.h"
+#include "sdp_affine_global_sample.h"
 #include "sdp_affine_local.h"
 #include "sdp_affine_local_sample.h"
 #include "sdp_hard_affine.h"
@@ -844,6 +845,8 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_affine_global::ID_FWD: return "sdp_affine_global_fwd_kernel";
     case sdp_affine_global::ID_VAL: return "sdp_affine_global_val_kernel";
     case sdp_affine_global::ID_BWD: return "sdp_affine_global_bwd_kernel";
+    // sampling from its posterior (csrc/sdp_affine_global_sample.hip)
+    case sdp_affine_global_sample::ID_SAMPLE: return "sdp_affine_global_sample_kernel";
     }
     return nullptr;
 }
@@ -1950,6 +1953,30 @@ int sdp_affine_global_backward_f32(const void *state, const float *Et, float *E,
     const int W = sdp_affine_global::waves_for(N, M);
     return strip_launch(sdp_affine_global_bwd_kernel, "sdp_affine_global_bwd_kernel", B, W, sdp_affine_global::sweep_lds_bytes(W, M), stream,
                         static_cast<const float4 *>(state), Et, E, GO, GX, lens, N, M, W);
+}
+
+// ---- alignments sampled from its posterior (csrc/sdp_affine_global_sample.hip): one walk per sample, from the end cell (n,m) ----
+static_assert(sdp_affine_global_sample::LANES == sdp_affine_local_sample::LANES, "the two samplers launch the same workgroups");
+int sdp_affine_global_sample_paths_f32(const void *state, int32_t *states, int32_t *counts, int32_t *visits, int32_t *opens,
+                                       int32_t *extends, int32_t *ends, int B, int N, int M, int K, int sample0, uint64_t seed,
+                                       const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!state || (states && !counts) || (!states && !counts && !visits && !opens && !extends && !ends))
+        return fail(SDP_E_NULLPTR, "sdp_affine_global_sample_paths_f32: null pointer (state; states with counts, or visits, or opens, "
+                                   "or extends, or ends)");
+    if (int rc = affine_global_args(B, N, M, flags)) return rc;
+    if (K < 1 || sample0 < 0 || (long long)sample0 + K > 0x7fffffffLL)
+        return fail(SDP_E_SHAPE, "sdp_affine_global_sample_paths_f32: K must be positive, sample0 non-negative and sample0 + K below 2^31");
+    const int cap = sdp_traceback_capacity(N, M);
+    const size_t lim = 0x7fffffffu, waves = (size_t)B * ((K + sdp_affine_global_sample::LANES - 1) / sdp_affine_global_sample::LANES);
+    if ((states && (size_t)B * K * cap * 3 > lim) || (size_t)B * K * 3 > lim || waves > lim)
+        return fail(SDP_E_TOOBIG, "sdp_affine_global_sample_paths_f32: an output exceeds 2^31 elements");
+    if (int rc = use_device(device)) return rc;
+    sdp_affine_global_sample::Params g = {};
+    g.state = static_cast<const float4 *>(state);
+    g.states = states, g.counts = counts, g.visits = visits, g.opens = opens, g.extends = extends, g.ends = ends, g.lens = lens;
+    g.seed = seed, g.B = B, g.N = N, g.M = M, g.K = K, g.sample0 = sample0, g.cap = cap;
+    return strip_launch(sdp_affine_global_sample_kernel, "sdp_affine_global_sample_kernel", (unsigned)waves, SAMPLE_WAVES, 0, stream, g);
 }
 
 // ---- the sparsemax operator (csrc/sdp_sparsemax.hip): the global recurrence under the sparse smoothed maximum, first order ----

@@ -880,8 +880,11 @@ int sdp_hard_affine_global_walk_f32(const void *state, const int32_t *ends, cons
  * and sdp_affine_global_forward_value_f32 gives the bits of sdp_affine_global_forward_f32's Vt.
  * Arithmetic: the sweep carries exp V scaled -- three fp32 mantissas on one integer exponent per cell -- and rebuilds Vt once per
  * pair in float64.  Its envelope: a score below -2^24 / log2(e) = -1.16e7 counts as -inf; a plane more than 2^126 below the largest
- * plane of its cell, and a cell whose weight falls below 2^(-2^29), are flushed to zero.
- * NOT built (the hard-max member is sdp_hard_affine_global_* above): sampling, the second order, float64, free end gaps, the reference's zero border.
+ * plane of its cell, and a cell whose weight falls below 2^(-2^29), are flushed to zero; so is, of O[i,j] and X[i,j], the one that
+ * lies more than about 2^149 (103 in the scores' own units) below the other: exp(theta + O) and exp(theta + X) of a cell share one
+ * exponent, and such an opening (or extension) counts as forbidden.
+ * NOT built (the hard-max member is sdp_hard_affine_global_* above, sampling sdp_affine_global_sample_paths_f32 below): the second
+ * order, float64, free end gaps, the reference's zero border.
  *   state    sdp_affine_global_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: 48 bytes per cell -- one record
  *            {q[s<-x], q[s<-m], q[s<-y], w_s} per plane s, w_s zero but in the end cell -- in a private layout; written by
  *            sdp_affine_global_forward_f32, read by sdp_affine_global_backward_f32 with the same B, N, M, lens (which needs neither
@@ -901,6 +904,52 @@ int sdp_affine_global_forward_value_f32(const float *theta, const float *gap_ope
                                         const int32_t *lens, int flags, int device, void *stream);
 int sdp_affine_global_backward_f32(const void *state, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
                                    const int32_t *lens, int flags, int device, void *stream);
+
+/* Alignments SAMPLED from its posterior (csrc/sdp_affine_global_sample.hip): what sdp_affine_local_sample_paths_f32 is
+ * to the local operator.  (Added after SDP_VERSION 106 without a version change: look the symbol up.  sdp_kernel_name answers 190
+ * for its kernel; 189 and 191 answer NULL.)  A path from cell (1,1) to cell (n,m) has probability exp(score - Vt); E, GO and GX for
+ * Et = 1 are the marginals of "the path passes through the cell", "opens a gap into it" and "extends a gap into it".  The end cell
+ * is fixed, and sdp_affine_global_forward_f32 has left the end weights w_s in the state: there are NO tables and the entry takes no
+ * Vt.  Planes x, m, y = 0, 1, 2.  (n, m) = lens[b] clamped to [0, N] x [0, M], or (N, M); for n < 1 or m < 1 every sample is EMPTY.
+ * Cells 0-based from here on; U(seed, pair, sample, t) the generator of sdp_sample_paths_* (sdp_sample_uniform is its host twin);
+ * the sample number of sample k is sample0 + k.  t is numbered as in the local sampler: U(.., 0) and U(.., 1) are not used.
+ * END PLANE, t = 2: wx, wm, wy = the fourth words of the records of planes x, m, y of cell (n-1, m-1);
+ * p = U(.., 2) * ((wx + wy) + wm), in this order of fp32 adds, and
+ *     p < wx                   plane x
+ *     else p < wx + wy         plane y
+ *     else                     the last of m, y, x whose weight is non-zero: m if wm > 0, else y if wy > 0, else x if wx > 0
+ *     else (all three are 0)   the pair has NO PATH: the sample is EMPTY
+ * (Unlike the local operator's, plane m of the end cell may have weight 0: a 1 x 2 pair ends in plane y.)
+ * WALK, t = 3, 4, ...: at (i, j, s).  At cell (0, 0) the walk ENDS: the cell is recorded as plane m, NO uniform is consumed and no
+ * record is read there.  Elsewhere, with that plane's record {q[s<-x], q[s<-m], q[s<-y], .} and u = U(.., t), t one more than at
+ * the cell before: the predecessor CELL is (i-1, j) for s = x, (i-1, j-1) for s = m, (i, j-1) for s = y; the predecessor's PLANE is
+ *     u < q[s<-x]                                  x
+ *     else u < q[s<-x] + q[s<-y]  (one fp32 add)   y
+ *     else                                         the last of m, y, x whose weight is non-zero: m if q[s<-m] > 0, else y if
+ *                                                  q[s<-y] > 0, else x
+ * in EVERY plane: no plane stops by weight -- the weights of a plane that a path reaches sum to 1 up to rounding.  So a
+ * predecessor of weight exactly 0 -- a forbidden opening or extension, anything outside the block, a plane no path reaches -- is
+ * never chosen: by induction the walk never stands in an unreachable plane, never opens or extends a forbidden gap, and leaves the
+ * block only through (0, 0).  (The kernel still ends a walk at the block's edge: a buffer that is not a state is not read out of
+ * bounds.)  Every step lowers i or j: at most n + m - 1 cells.  NaN weights: unspecified.
+ * OUTPUTS, each nullable; if nothing is asked for, SDP_E_NULLPTR -- the formats of sdp_affine_local_sample_paths_f32:
+ *   states   (B, K, cap, 3) int32, cap = sdp_traceback_capacity(N, M), and counts (B, K) (required with states): the path, start
+ *            first, RIGHT-aligned -- rows cap-1-counts[b,k] .. cap-2, rows (i, j, plane: how the cell was entered, m for the
+ *            start); row cap-1 holds (number of path cells, i, j of the first cell), (0, -1, -1) for an empty sample; rows in
+ *            front of the list are not written.
+ *   ends     (B, K, 3) int32: (n-1, m-1, the end plane), (-1, -1, -1) for an empty sample.
+ *   visits, opens, extends   (B, N, M) int32, incremented by no-return integer atomic adds -- the caller zeroes them; the result is
+ *            deterministic.  visits: + 1 per path cell; opens: + 1 on a path cell in plane x or y whose predecessor on the path is
+ *            in a different plane; extends: + 1 where it is in the same plane.  Over K they estimate E, GO and GX for Et = 1.
+ * The same call twice gives the same tensors, and K = 64 at sample0 = 0 equals 32 at 0 joined with 32 at 32.
+ *   state    what sdp_affine_global_forward_f32 wrote, with the same B, N, M, lens.
+ *   flags    none is defined: any bit is refused (SDP_E_VARIANT).
+ * K >= 1 and sample0 >= 0 (and sample0 + K < 2^31), else SDP_E_SHAPE; an output of more than 2^31 - 1 elements: SDP_E_TOOBIG; M
+ * above sdp_max_cols(): SDP_E_MAXCOLS.  All arguments are checked before any device call.  One wave per 64 samples of a pair, no
+ * LDS.  A problem that was swept TRANSPOSED is out of scope, as in the other samplers. */
+int sdp_affine_global_sample_paths_f32(const void *state, int32_t *states, int32_t *counts, int32_t *visits, int32_t *opens,
+                                       int32_t *extends, int32_t *ends, int B, int N, int M, int K, int sample0, uint64_t seed,
+                                       const int32_t *lens, int flags, int device, void *stream);
 
 /* EXPERIMENTAL -- parity-equal to the unfused sequence, but SLOWER than it (B=256, 512 x 512: 2.02 vs 1.62 ms per training
  * step; the seed's divisions sit on the sweep's dependency chain and cost more than the 268 MB tensor they save).  Kept
