@@ -876,6 +876,45 @@ class HipEngine:
         self.call("sdp_affine_global_backward_f32", AFFINE_GLOBAL_KERNELS[182], dev, state, Et, E, GO, GX, B, N, M, lens, 0)
         return E, GO, GX
 
+    def affine_global_adjoint_forward(self, state, ZE, ZGO, ZGX, shape, lens=None, state_d_out=None):
+        """The adjoint forward sweep over the records of affine_global_forward -> (Vtd (B,), state_d): ZE, ZGO, ZGX (B,N,M) the
+        cotangents of E, GO and GX, each may be None (zeros) but not all three; state_d the dot records (opaque float32 tensor of
+        sdp_affine_global_adjoint_state_bytes; state_d_out: a buffer of that size to write into instead of a fresh one).  (No Vt:
+        the end weights are in `state`.)"""
+        dev = self.device_of(state)
+        B, N, M = shape
+        if ZE is None and ZGO is None and ZGX is None:
+            raise ValueError("affine_global_adjoint_forward: ZE, ZGO and ZGX are all None")
+        check_args(state, torch.float32, None, True, state=state)
+        check_args(state, torch.float32, (B, N, M), ZE=ZE, ZGO=ZGO, ZGX=ZGX)
+        ZE, ZGO, ZGX = (None if z is None else z.detach().contiguous() for z in (ZE, ZGO, ZGX))
+        lens = self._lens(lens, B, state.device)
+        nfloats = max(self.lib.sdp_affine_global_adjoint_state_bytes(B, N, M), 4) // 4
+        check_args(state, torch.float32, (nfloats,), True, ValueError, state_d_out=state_d_out)
+        state_d = torch.empty(nfloats, dtype=torch.float32, device=state.device) if state_d_out is None else state_d_out
+        Vtd = torch.empty(B, dtype=torch.float32, device=state.device)
+        self.call("sdp_affine_global_adjoint_forward_f32", AFFINE_GLOBAL_ADJOINT_KERNELS[193], dev, state, ZE, ZGO, ZGX, state_d, Vtd,
+                  B, N, M, lens, 0)
+        return Vtd, state_d
+
+    def affine_global_adjoint_backward(self, state, state_d, Vtd, Et, shape, lens=None, want_GO=True, want_GX=True):
+        """The adjoint mirror sweep -> (Ed (B,N,M), GOd (B,N,M) or None, GXd (B,N,M) or None): the gradients of <ZE,E> + <ZGO,GO> +
+        <ZGX,GX> with respect to theta, gap_open and gap_extend, +0 outside each pair's block.  state: of affine_global_forward;
+        state_d, Vtd: of affine_global_adjoint_forward; Et: what affine_global_backward was given."""
+        dev = self.device_of(state)
+        B, N, M = shape
+        check_args(state, torch.float32, (B,), True, Vtd=Vtd)
+        check_args(state, torch.float32, None, True, state_d=state_d)
+        check_args(state, Et=Et)
+        Et = Et.detach().to(torch.float32).expand(B).contiguous()
+        lens = self._lens(lens, B, state.device)
+        Ed = torch.empty((B, N, M), dtype=torch.float32, device=state.device)
+        GOd = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if want_GO else None
+        GXd = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if want_GX else None
+        self.call("sdp_affine_global_adjoint_backward_f32", AFFINE_GLOBAL_ADJOINT_KERNELS[194], dev, state, state_d, Vtd, Et, Ed, GOd, GXd,
+                  B, N, M, lens, 0)
+        return Ed, GOd, GXd
+
     # ---- alignments sampled from its posterior (include/sdp.h: sdp_affine_global_sample_paths_f32) ----
     def affine_global_sample_paths(self, state, shape, K, lens=None, seed=0, sample0=0, want_states=True, want_visits=False,
                                    want_opens=False, want_extends=False, want_ends=False):
@@ -1092,6 +1131,8 @@ SPARSEMAX_KERNELS = {150: "sdp_sparsemax_fwd_kernel", 151: "sdp_sparsemax_val_ke
 SPARSEMAX_ADJOINT_KERNELS = {154: "sdp_sparsemax_adj_fwd_kernel", 155: "sdp_sparsemax_adj_bwd_kernel"}
 # kernel id (csrc/sdp_affine_global.h) -> symbol of the affine-gap soft global operator's kernels
 AFFINE_GLOBAL_KERNELS = {180: "sdp_affine_global_fwd_kernel", 181: "sdp_affine_global_val_kernel", 182: "sdp_affine_global_bwd_kernel"}
+# of its adjoint pair (the same header)
+AFFINE_GLOBAL_ADJOINT_KERNELS = {193: "sdp_affine_global_adj_fwd_kernel", 194: "sdp_affine_global_adj_bwd_kernel"}
 # and of the kernel that samples from its posterior (csrc/sdp_affine_global_sample.h)
 AFFINE_GLOBAL_SAMPLE_KERNELS = {190: "sdp_affine_global_sample_kernel"}
 # kernel id (csrc/sdp_affine_local.h) -> symbol of the affine-gap soft local operator's kernels

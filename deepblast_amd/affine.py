@@ -29,7 +29,9 @@ Out of scope, none of it built: the third order, float64, the `distributed` wrap
 (their protocols have two tensors, this operator three).
 
 The GLOBAL form -- a path from cell (1,1) to cell (n,m), the Gotoh form of Needleman-Wunsch -- is AffineGlobalDecoder at the end of
-this file (include/sdp.h: sdp_affine_global_*): first order.  Its hard (max-plus) member is built as well
+this file (include/sdp.h: sdp_affine_global_*).  Its second order is opt-in as well (`second_order=True`; include/sdp.h:
+sdp_affine_global_adjoint_*), so that a loss on the alignment matrix trains through whole-sequence end-to-end
+alignment; the third order is not built.  Its hard (max-plus) member is built as well
 (include/sdp.h: sdp_hard_affine_global_*): the optimal affine-gap Needleman-Wunsch (Gotoh) alignment --
 AffineGlobalDecoder.optimal_paths / optimal_alignments / optimal_score on every decoder, and AffineGlobalDecoder(operator="hardmax").
 Sampling from the global posterior is built too (include/sdp.h: sdp_affine_global_sample_paths_f32):
@@ -371,23 +373,72 @@ class AffineGlobalFunctionBackward(torch.autograd.Function):
                                   "sdp_affine_global_*) is not built")
 
 
+class AffineGlobalAdjoint(torch.autograd.Function):
+    """(Ed, GOd, GXd, Vtd) of the global adjoint pair (include/sdp.h: sdp_affine_global_adjoint_*): the gradients of <ZE, E> +
+    <ZGO, GO> + <ZGX, GX> with respect to theta, gap_open, gap_extend and Et.  Differentiable in nothing: the third order is not
+    built, and this is the node that says so."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, Et, ZE, ZGO, ZGX, state, lens, want_GO, want_GX):
+        # (the inputs and the cotangents are here for the graph: a third differentiation must arrive below)
+        eng = _engine.get_engine()
+        shape = tuple(theta.shape)
+        Vtd, state_d = eng.affine_global_adjoint_forward(state, ZE, ZGO, ZGX, shape, lens)
+        Ed, GOd, GXd = eng.affine_global_adjoint_backward(state, state_d, Vtd, Et, shape, lens, want_GO=want_GO, want_GX=want_GX)
+        return Ed, GOd, GXd, Vtd
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError("the affine-gap soft global operator is second order only: its third order (the derivative of the "
+                                  "adjoint pair sdp_affine_global_adjoint_*) is not built")
+
+
+class AffineGlobalFunctionBackward2(torch.autograd.Function):
+    """AffineGlobalFunctionBackward for AffineGlobalDecoder(second_order=True): the same (E, GO, GX), differentiable once more
+    through the adjoint pair.  backward(ZE, ZGO, ZGX) -> the gradients of <ZE, E> + <ZGO, GO> + <ZGX, GX>: Ed for theta, GOd for
+    gap_open, GXd for gap_extend, Vtd for Et; only the outputs whose input needs a gradient are asked for."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, Et, state, lens, want_E, want_GO, want_GX):
+        E, GO, GX = _engine.get_engine().affine_global_backward(state, Et, tuple(theta.shape), lens, want_GO=want_GO, want_GX=want_GX)
+        ctx.save_for_backward(theta, gap_open, gap_extend, Et, state)
+        ctx.lens = lens
+        ctx.set_materialize_grads(False)
+        return (E if want_E else None), GO, GX
+
+    @staticmethod
+    def backward(ctx, ZE, ZGO, ZGX):
+        theta, gap_open, gap_extend, Et, state = ctx.saved_tensors
+        none = (None,) * 5
+        if ZE is None and ZGO is None and ZGX is None:
+            return (None, None, None, None) + none
+        need = ctx.needs_input_grad
+        Ed, GOd, GXd, Vtd = AffineGlobalAdjoint.apply(theta, gap_open, gap_extend, Et, ZE, ZGO, ZGX, state, ctx.lens, need[1], need[2])
+        if Vtd.shape != Et.shape:       # Et was broadcast over the batch
+            Vtd = Vtd.sum_to_size(Et.shape)
+        return (Ed if need[0] else None, GOd, GXd, Vtd if need[3] else None) + none
+
+
 class AffineGlobalFunction(torch.autograd.Function):
     """Vt = affine_global(theta, gap_open, gap_extend); backward: theta.grad = E, gap_open.grad = GO, gap_extend.grad = GX, one
     mirror sweep; GO and GX are computed only when their input needs a gradient.  Once differentiable: differentiating E, GO or
-    GX raises NotImplementedError (AffineGlobalFunctionBackward)."""
+    GX raises NotImplementedError (AffineGlobalFunctionBackward) -- unless second_order is set: they are then differentiable
+    through the adjoint pair (AffineGlobalFunctionBackward2), and the third order raises."""
 
     @staticmethod
-    def forward(ctx, theta, gap_open, gap_extend, lens=None):
+    def forward(ctx, theta, gap_open, gap_extend, lens=None, second_order=False):
         Vt, state = _engine.get_engine().affine_global_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lens)
         ctx.save_for_backward(theta, gap_open, gap_extend, state)
         ctx.lens = lens
+        ctx.second_order = second_order
         return Vt
 
     @staticmethod
     def backward(ctx, Et):
         theta, gap_open, gap_extend, state = ctx.saved_tensors
-        E, GO, GX = AffineGlobalFunctionBackward.apply(theta, gap_open, gap_extend, Et, state, ctx.lens, *ctx.needs_input_grad[:3])
-        return E, GO, GX, None
+        fn = AffineGlobalFunctionBackward2 if ctx.second_order else AffineGlobalFunctionBackward
+        E, GO, GX = fn.apply(theta, gap_open, gap_extend, Et, state, ctx.lens, *ctx.needs_input_grad[:3])
+        return E, GO, GX, None, None
 
 
 class HardAffineGlobalFunctionBackward(torch.autograd.Function):
@@ -450,9 +501,15 @@ class AffineGlobalDecoder(torch.nn.Module):
 
     forward(theta, gap_open, gap_extend, lengths=None) -> Vt (B,), differentiable ONCE: theta.grad = E, gap_open.grad = GO,
     gap_extend.grad = GX, all true gradients; GO and GX are computed only when their input needs a gradient.  Differentiating a
-    gradient raises NotImplementedError (the second order is not built).
+    gradient raises NotImplementedError (the second order is not built into the default object), unless second_order is set.
     decode(theta, gap_open, gap_extend, lengths=None) -> E (B, N, M) for Et = 1: E[b, i, j] is the posterior probability that cell
-    (i, j) lies on the alignment of pair b.  No autograd graph.
+    (i, j) lies on the alignment of pair b.  No autograd graph, unless second_order is set.
+    second_order=True (softmax only; with "hardmax": ValueError, the max-plus score is piecewise linear): forward() is
+    differentiable TWICE and decode() returns E with a graph when grad is enabled and an input requires it, so that a loss on the
+    alignment matrix -- loss(first, dec.decode(theta, gap_open, gap_extend, lengths), x_len, y_len, G).backward() -- trains theta,
+    gap_open and gap_extend through whole-sequence alignment: the gradients come from the adjoint pair
+    (sdp_affine_global_adjoint_*), true ones for all three; only the ones asked for are computed.  Finite
+    cotangents whose running sums along a path stay below 2^21.  The third order is not built and raises.
     score(theta, gap_open, gap_extend, lengths=None) -> Vt (B,) through the value-only sweep: no state is allocated, no graph.
     theta finite; gap_open and gap_extend finite or -inf (a forbidden opening or extension: the matching gradient is exactly +0
     there).  Where no path exists -- n != m with every gap forbidden, or masks that cut every route -- Vt = -inf and the gradients
@@ -471,21 +528,25 @@ class AffineGlobalDecoder(torch.nn.Module):
     sample_paths / sample_alignments: alignments drawn from the soft operator's posterior, on every decoder whatever its operator
     (include/sdp.h: sdp_affine_global_sample_paths_f32); only sampling a problem that is swept transposed is out
     of scope.
-    Out of scope, none of it built: the second order, float64, the `distributed` wrappers, `search_scores`,
-    `losses.decode_loss`, free end gaps, and the reference's zero border."""
+    The second order is opt-in (`second_order=True`).  Out of scope, none of it built: the third order, float64, the
+    `distributed` wrappers, `search_scores`, `losses.decode_loss`, free end gaps, and the reference's zero border."""
 
-    def __init__(self, operator="softmax"):
+    def __init__(self, operator="softmax", second_order=False):
         super().__init__()
         if operator not in ("softmax", "hardmax"):
             raise ValueError(f"operator must be 'softmax' or 'hardmax', got {operator!r}")
+        if second_order and operator == "hardmax":
+            raise ValueError("second_order=True needs operator='softmax': the max-plus score of 'hardmax' is piecewise linear, its "
+                             "second derivative is zero wherever it exists")
         self.operator = operator
+        self.second_order = bool(second_order)
 
     def forward(self, theta, gap_open, gap_extend, lengths=None):
         _validate(theta, gap_open, gap_extend)
         theta, gap_open, gap_extend, lengths, transposed = _oriented(theta, gap_open, gap_extend, lengths)
         if self.operator == "hardmax":
             return HardAffineGlobalFunction.apply(theta, gap_open, gap_extend, lengths, transposed)
-        return AffineGlobalFunction.apply(theta, gap_open, gap_extend, lengths)
+        return AffineGlobalFunction.apply(theta, gap_open, gap_extend, lengths, self.second_order)
 
     def decode(self, theta, gap_open, gap_extend, lengths=None):
         _validate(theta, gap_open, gap_extend)
@@ -496,6 +557,12 @@ class AffineGlobalDecoder(torch.nn.Module):
                 _, state, ends = eng.hard_affine_global_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths, ymx=transposed)
                 E = eng.hard_affine_global_walk(state, ends, tuple(theta.shape), lengths, ymx=transposed, want_states=False,
                                                 Et=torch.ones((), dtype=torch.float32, device=theta.device))[0]
+            return E.transpose(1, 2) if transposed else E
+        if self.second_order and torch.is_grad_enabled() and (theta.requires_grad or gap_open.requires_grad or gap_extend.requires_grad):
+            # E with a graph: the forward sweep outside autograd, then the node the adjoint pair hangs on (Et = 1)
+            _, state = eng.affine_global_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths)
+            one = torch.ones(theta.shape[0], dtype=torch.float32, device=theta.device)
+            E, _, _ = AffineGlobalFunctionBackward2.apply(theta, gap_open, gap_extend, one, state, lengths, True, False, False)
             return E.transpose(1, 2) if transposed else E
         with torch.no_grad():
             _, state = eng.affine_global_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), lengths)

@@ -20,7 +20,7 @@ SRC = [KERNELS, os.path.join(HERE, "csrc", "sdp_aux.hip"), os.path.join(HERE, "c
        os.path.join(HERE, "csrc", "sdp_soft_local_adj.hip"), os.path.join(HERE, "csrc", "sdp_soft_local_sample.hip"),
        os.path.join(HERE, "csrc", "sdp_sparsemax.hip"), os.path.join(HERE, "csrc", "sdp_sparsemax_adj.hip"),
        os.path.join(HERE, "csrc", "sdp_affine_local.hip"), os.path.join(HERE, "csrc", "sdp_affine_local_adj.hip"), os.path.join(HERE, "csrc", "sdp_affine_local_sample.hip"),
-       os.path.join(HERE, "csrc", "sdp_hard_affine.hip"), os.path.join(HERE, "csrc", "sdp_affine_global.hip"),
+       os.path.join(HERE, "csrc", "sdp_hard_affine.hip"), os.path.join(HERE, "csrc", "sdp_affine_global.hip"), os.path.join(HERE, "csrc", "sdp_affine_global_adj.hip"),
        os.path.join(HERE, "csrc", "sdp_affine_global_sample.hip"),
        os.path.join(HERE, "csrc", "sdp_api.hip")]
 HDR = [os.path.join(HERE, "csrc", "sdp_kernels.h"), os.path.join(HERE, "csrc", "sdp_device.h"), os.path.join(HERE, "csrc", "sdp_builds.def"), os.path.join(HERE, "csrc", "sdp_hard.h"),

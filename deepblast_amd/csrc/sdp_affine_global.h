@@ -42,6 +42,26 @@ __host__ __device__ inline size_t pair_cells(int N, int M) { return (size_t)stri
 // kernel ids sdp_kernel_name answers for (179 and 183 answer NULL)
 enum { ID_FWD = 180, ID_VAL = 181, ID_BWD = 182 };
 
+// ---- the second order (csrc/sdp_affine_global_adj.hip): the adjoint pair ----
+constexpr int ADJ_GROUP = 4;     // steps of the adjoint forward sweep's cotangent prefetch and of the adjoint backward sweep's stores
+constexpr int ADJ_PAIR = 2;      // steps of the adjoint sweeps' record prefetch (the backward one's: a record and a dot record per plane, 24 floats a step)
+constexpr int ADJ_BASE_LOG2 = 10;   // G: a cell's tangents are Vd_s = base 2^-G + delta_s, one integer base per cell; |Vd| < 2^(31 - G)
+// the adjoint forward sweep hands the three deltas and the base of a strip's bottom row down, four words per column: the ring, the
+// budget and the waves of the first order (sweep_lds_bytes, waves_for).  The adjoint backward sweep's ring is six words per column:
+// what the top row pushes up into each plane, of Eb and of Ebd, unreduced
+__host__ __device__ inline size_t adjoint_lds_bytes(int waves, int M) { return (size_t)2 * PLANES * waves * row_pitch(M) * 4 + 2 * MAX_WAVES * 4; }
+// waves of the adjoint backward sweep: eight up to M = 789, seven up to 910, six up to 1073, five up to 1300, four up to 1642,
+// three up to the column limit 2048
+__host__ __device__ inline int adjoint_waves_for(int N, int M)
+{
+    int w = strips(N) < MAX_WAVES ? strips(N) : MAX_WAVES;
+    while (w > 1 && adjoint_lds_bytes(w, M) > (size_t)LDS_BUDGET) --w;
+    return w;
+}
+
+// kernel ids sdp_kernel_name answers for (192 and 195 answer NULL)
+enum { ID_ADJ_FWD = 193, ID_ADJ_BWD = 194 };
+
 }  // namespace sdp_affine_global
 
 extern "C" {
@@ -51,6 +71,10 @@ __global__ void sdp_affine_global_val_kernel(const float *theta, const float *O,
                                              int N, int M, int waves);
 __global__ void sdp_affine_global_bwd_kernel(const float4 *state, const float *Et, float *E, float *GO, float *GX, const int *lens, int N,
                                              int M, int waves);
+__global__ void sdp_affine_global_adj_fwd_kernel(const float4 *state, const float *ZE, const float *ZGO, const float *ZGX, float4 *stated,
+                                                 float *Vtd, const int *lens, int N, int M, int waves);
+__global__ void sdp_affine_global_adj_bwd_kernel(const float4 *state, const float4 *stated, const float *Et, float *Ed, float *GOd,
+                                                 float *GXd, const int *lens, int N, int M, int waves);
 }
 
 #endif  // SDP_AFFINE_GLOBAL_H_

@@ -671,6 +671,17 @@ int raise_affine_global_limit(int device)
                               sdp_affine_global::LDS_BUDGET);
 }
 
+// its adjoint pair: the adjoint forward sweep keeps the first order's ring, the adjoint backward sweep six words per column
+// (sdp_affine_global::adjoint_lds_bytes), both up to 160 KB
+int raise_affine_global_adjoint_limit(int device)
+{
+    static thread_local unsigned long long raised = 0;
+    return raise_strip_limits(raised, device,
+                              {{(const void *)sdp_affine_global_adj_fwd_kernel, "hipFuncSetAttribute(sdp_affine_global_adj_fwd_kernel)"},
+                               {(const void *)sdp_affine_global_adj_bwd_kernel, "hipFuncSetAttribute(sdp_affine_global_adj_bwd_kernel)"}},
+                              sdp_affine_global::LDS_BUDGET);
+}
+
 // ---- what the entries of the strip-schedule families share ----
 // waves of a workgroup: one per strip in flight, lowered to `forced` if 0 < forced, then until the family's ring fits its budget
 int strip_waves(int strips, int max_waves, int forced, int M, size_t (*lds_bytes)(int, int), int budget)
@@ -847,6 +858,9 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_affine_global::ID_BWD: return "sdp_affine_global_bwd_kernel";
     // sampling from its posterior (csrc/sdp_affine_global_sample.hip)
     case sdp_affine_global_sample::ID_SAMPLE: return "sdp_affine_global_sample_kernel";
+    // the affine-gap soft global operator's adjoint pair (csrc/sdp_affine_global_adj.hip)
+    case sdp_affine_global::ID_ADJ_FWD: return "sdp_affine_global_adj_fwd_kernel";
+    case sdp_affine_global::ID_ADJ_BWD: return "sdp_affine_global_adj_bwd_kernel";
     }
     return nullptr;
 }
@@ -871,7 +885,8 @@ int sdp_init(int device)
     if (int rc = raise_affine_local_limit(device)) return rc;
     if (int rc = raise_affine_local_adjoint_limit(device)) return rc;
     if (int rc = raise_hard_affine_limit(device)) return rc;
-    return raise_affine_global_limit(device);
+    if (int rc = raise_affine_global_limit(device)) return rc;
+    return raise_affine_global_adjoint_limit(device);
 }
 
 int sdp_device_status(int device, int32_t info[4])
@@ -1953,6 +1968,40 @@ int sdp_affine_global_backward_f32(const void *state, const float *Et, float *E,
     const int W = sdp_affine_global::waves_for(N, M);
     return strip_launch(sdp_affine_global_bwd_kernel, "sdp_affine_global_bwd_kernel", B, W, sdp_affine_global::sweep_lds_bytes(W, M), stream,
                         static_cast<const float4 *>(state), Et, E, GO, GX, lens, N, M, W);
+}
+
+// ---- its second order (csrc/sdp_affine_global_adj.hip): the adjoint pair; the adjoint backward sweep has a wave count of its own ----
+size_t sdp_affine_global_adjoint_state_bytes(int B, int N, int M) { return sdp_affine_global_state_bytes(B, N, M); }
+
+int sdp_affine_global_adjoint_forward_f32(const void *state, const float *ZE, const float *ZGO, const float *ZGX, void *state_d, float *Vtd,
+                                          int B, int N, int M, const int32_t *lens, int flags, int device, void *stream)
+{
+    if (!state || !state_d || !Vtd || (!ZE && !ZGO && !ZGX))
+        return fail(SDP_E_NULLPTR, "sdp_affine_global_adjoint_forward_f32: null pointer (state, state_d, Vtd; ZE, ZGO, ZGX may be NULL, not "
+                                   "all three)");
+    if (int rc = affine_global_args(B, N, M, flags)) return rc;
+    if (int rc = use_device(device)) return rc;
+    if (int rc = raise_affine_global_adjoint_limit(device)) return rc;
+    const int W = sdp_affine_global::waves_for(N, M);
+    return strip_launch(sdp_affine_global_adj_fwd_kernel, "sdp_affine_global_adj_fwd_kernel", B, W, sdp_affine_global::sweep_lds_bytes(W, M),
+                        stream, static_cast<const float4 *>(state), ZE, ZGO, ZGX, static_cast<float4 *>(state_d), Vtd, lens, N, M, W);
+}
+
+// (Vtd holds the place it has in the local entry and is RESERVED: it is not read and may be NULL -- the sweep seeds from the
+// differences d_s - sum w d of the end cell's dot records, which lose nothing to the size of Vtd)
+int sdp_affine_global_adjoint_backward_f32(const void *state, const void *state_d, const float *Vtd, const float *Et, float *Ed, float *GOd,
+                                           float *GXd, int B, int N, int M, const int32_t *lens, int flags, int device, void *stream)
+{
+    (void)Vtd;
+    if (!state || !state_d || !Et || !Ed)
+        return fail(SDP_E_NULLPTR, "sdp_affine_global_adjoint_backward_f32: null pointer (state, state_d, Et, Ed; Vtd, GOd and GXd may be "
+                                   "NULL)");
+    if (int rc = affine_global_args(B, N, M, flags)) return rc;
+    if (int rc = use_device(device)) return rc;
+    if (int rc = raise_affine_global_adjoint_limit(device)) return rc;
+    const int W = sdp_affine_global::adjoint_waves_for(N, M);
+    return strip_launch(sdp_affine_global_adj_bwd_kernel, "sdp_affine_global_adj_bwd_kernel", B, W, sdp_affine_global::adjoint_lds_bytes(W, M),
+                        stream, static_cast<const float4 *>(state), static_cast<const float4 *>(state_d), Et, Ed, GOd, GXd, lens, N, M, W);
 }
 
 // ---- alignments sampled from its posterior (csrc/sdp_affine_global_sample.hip): one walk per sample, from the end cell (n,m) ----

@@ -883,8 +883,8 @@ int sdp_hard_affine_global_walk_f32(const void *state, const int32_t *ends, cons
  * plane of its cell, and a cell whose weight falls below 2^(-2^29), are flushed to zero; so is, of O[i,j] and X[i,j], the one that
  * lies more than about 2^149 (103 in the scores' own units) below the other: exp(theta + O) and exp(theta + X) of a cell share one
  * exponent, and such an opening (or extension) counts as forbidden.
- * NOT built (the hard-max member is sdp_hard_affine_global_* above, sampling sdp_affine_global_sample_paths_f32 below): the second
- * order, float64, free end gaps, the reference's zero border.
+ * The second order is sdp_affine_global_adjoint_* below.  NOT built (the hard-max member is sdp_hard_affine_global_* above, sampling
+ * sdp_affine_global_sample_paths_f32 below): the third order, float64, free end gaps, the reference's zero border.
  *   state    sdp_affine_global_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: 48 bytes per cell -- one record
  *            {q[s<-x], q[s<-m], q[s<-y], w_s} per plane s, w_s zero but in the end cell -- in a private layout; written by
  *            sdp_affine_global_forward_f32, read by sdp_affine_global_backward_f32 with the same B, N, M, lens (which needs neither
@@ -904,6 +904,46 @@ int sdp_affine_global_forward_value_f32(const float *theta, const float *gap_ope
                                         const int32_t *lens, int flags, int device, void *stream);
 int sdp_affine_global_backward_f32(const void *state, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
                                    const int32_t *lens, int flags, int device, void *stream);
+
+/* Its SECOND ORDER (csrc/sdp_affine_global_adj.hip): the adjoint pair, what sdp_affine_local_adjoint_* is to the local
+ * operator, with the global operator's start and end.  (Added after SDP_VERSION 106 without a version change: look the symbols up.
+ * sdp_kernel_name answers 193 and 194 for its kernels; 192 and 195 answer NULL.)  With cotangents ZE on E, ZGO on GO and ZGX on GX,
+ * p_s the cell before (i,j) for plane s -- (i-1,j), (i-1,j-1), (i,j-1) -- and g[s<-s'] = ZGX[i,j] for a gap plane s and s' = s,
+ * ZGO[i,j] for a gap plane s and s' != s, 0 for s = m:
+ *     u[s<-s'] = g[s<-s'] + Vd_s'[p_s]                        (a Vd outside the table is 0, the cell above-left of (1,1) included)
+ *     ub_s = sum_s' q[s<-s'] u[s<-s'];   Vd_s[i,j] = ZE[i,j] + ub_s;   qd[s<-s'] = q[s<-s'] (u[s<-s'] - ub_s)
+ *     Vtd  = sum_s w_s Vd_s[n,m]                               (w_s: the end weights, in the records of cell (n,m) only)
+ *     Ebd_s[i,j] = [(i,j) = (n,m)] Et w_s (Vd_s - Vtd) + (qd[x<-s] Eb_x + q[x<-s] Ebd_x)[i+1,j] + (qd[m<-s] Eb_m + q[m<-s] Ebd_m)[i+1,j+1]
+ *                                      + (qd[y<-s] Eb_y + q[y<-s] Ebd_y)[i,j+1]
+ *     Ed, GOd, GXd from Eb, Ebd, q, qd exactly as sdp_affine_local_adjoint_* forms them.
+ * (Ed, GOd, GXd, Vtd) are the gradients of <ZE,E> + <ZGO,GO> + <ZGX,GX> with respect to (theta, O, X, Et); Eb is re-formed by the
+ * first-order recurrence, E is not read.  A plane without a predecessor has q = 0 and its Vd is never used; a forbidden opening or
+ * extension gets GOd / GXd of bit pattern +0; a pair without a path has every q and w equal to 0 and gives Vtd = 0 and Ed = GOd =
+ * GXd = +0 by bit pattern, and so does a pair with n < 1 or m < 1.  Outputs are +0 outside a pair's block.  No atomics: two calls
+ * give the same bits.
+ * ARITHMETIC: on a global path Vd is a sum of cotangents along thousands of steps, while qd and the seed use only differences of
+ * Vd between the planes of one cell.  A cell therefore carries three fp32 offsets d_s on one shared integer base c, Vd_s = c 2^-10
+ * + d_s, as the first order carries exp V on a shared exponent; Vtd is rebuilt once per pair in float64; the seed of Ebd is
+ * Et w_s (d_s - sum w d).  The envelope: finite cotangents, and |Vd| < 2^21.
+ *   state    what sdp_affine_global_forward_f32 wrote, with the same B, N, M, lens.  (No Vt: the end weights are in the state.)
+ *   ZE, ZGO, ZGX   (B, N, M) or NULL (zeros), each on its own; all three NULL: SDP_E_NULLPTR.  A NULL gives the bits of a tensor of zeros.
+ *   state_d  sdp_affine_global_adjoint_state_bytes(B, N, M) == sdp_affine_global_state_bytes(B, N, M) bytes, DEVICE, caller-owned: the
+ *            dot records {qd[s<-x], qd[s<-m], qd[s<-y], d_s} in the layout of the records.  Only records of cells inside a pair's
+ *            block are written.
+ *   Vtd      (B,): written by the adjoint forward entry.  In the adjoint backward entry the argument holds the place it has in the
+ *            local entry and is RESERVED: it is not read and may be NULL (the seed is formed from the offsets of the end cell's dot
+ *            records).
+ *   Et       (B,): what sdp_affine_global_backward_f32 was given.
+ *   GOd, GXd (B, N, M) or NULL, each on its own.
+ * The adjoint forward sweep runs on the first order's ring and waves (four words per column: three offsets and the base); the
+ * adjoint backward sweep's ring has six (the pushes of Eb and of Ebd into each plane), so it runs eight waves up to M = 789, seven
+ * to 910, six to 1073, five to 1300, four to 1642 and three at the column limit.  Codes, limits and the dynamic-LDS attribute as
+ * for the first-order entries; all arguments are checked before any device call.  NOT built: the third order, float64. */
+size_t sdp_affine_global_adjoint_state_bytes(int B, int N, int M);
+int sdp_affine_global_adjoint_forward_f32(const void *state, const float *ZE, const float *ZGO, const float *ZGX, void *state_d, float *Vtd,
+                                          int B, int N, int M, const int32_t *lens, int flags, int device, void *stream);
+int sdp_affine_global_adjoint_backward_f32(const void *state, const void *state_d, const float *Vtd, const float *Et, float *Ed, float *GOd,
+                                           float *GXd, int B, int N, int M, const int32_t *lens, int flags, int device, void *stream);
 
 /* Alignments SAMPLED from its posterior (csrc/sdp_affine_global_sample.hip): what sdp_affine_local_sample_paths_f32 is
  * to the local operator.  (Added after SDP_VERSION 106 without a version change: look the symbol up.  sdp_kernel_name answers 190
