@@ -876,6 +876,63 @@ class HipEngine:
         self.call("sdp_affine_global_backward_f32", AFFINE_GLOBAL_KERNELS[182], dev, state, Et, E, GO, GX, B, N, M, lens, 0)
         return E, GO, GX
 
+    # ---- its free-end-gap member (include/sdp.h: sdp_affine_semiglobal_*) ---------------
+    @staticmethod
+    def _free_ends(free_ends):
+        free_ends = int(free_ends)
+        if free_ends & ~3:
+            raise ValueError(f"free_ends must be 0 .. 3 (bit 0: x, bit 1: y), got {free_ends}")
+        return free_ends
+
+    def affine_semiglobal_forward(self, theta, gap_open, gap_extend, free_ends, lens=None, state_out=None):
+        """-> (Vt (B,), state): affine_global_forward with free end gaps -- free_ends bit 0: x (rows may hang over), bit 1: y
+        (columns); 0: the global operator's bits.  state: opaque float32 tensor of sdp_affine_semiglobal_state_bytes (the global
+        records and a tail of end-cell exponents; the end weights travel in it)."""
+        dev = self.device_of(theta)
+        free_ends = self._free_ends(free_ends)
+        check_args(theta, torch.float32, theta=theta, gap_open=gap_open, gap_extend=gap_extend)
+        check_args(theta, None, tuple(theta.shape), gap_open=gap_open, gap_extend=gap_extend)
+        theta, gap_open, gap_extend = theta.contiguous(), gap_open.contiguous(), gap_extend.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        nfloats = max(self.lib.sdp_affine_semiglobal_state_bytes(B, N, M), 4) // 4
+        check_args(theta, torch.float32, (nfloats,), True, ValueError, state_out=state_out)
+        state = torch.empty(nfloats, dtype=torch.float32, device=theta.device) if state_out is None else state_out
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        self.call("sdp_affine_semiglobal_forward_f32", AFFINE_SEMIGLOBAL_KERNELS[200], dev, theta, gap_open, gap_extend, state, Vt, B, N, M,
+                  lens, free_ends, 0)
+        return Vt, state
+
+    def affine_semiglobal_forward_value(self, theta, gap_open, gap_extend, free_ends, lens=None):
+        """-> Vt (B,) alone: the same sweep with the records and the tail compiled out (the same bits); nothing else is allocated."""
+        dev = self.device_of(theta)
+        free_ends = self._free_ends(free_ends)
+        check_args(theta, torch.float32, theta=theta, gap_open=gap_open, gap_extend=gap_extend)
+        check_args(theta, None, tuple(theta.shape), gap_open=gap_open, gap_extend=gap_extend)
+        theta, gap_open, gap_extend = theta.contiguous(), gap_open.contiguous(), gap_extend.contiguous()
+        B, N, M = theta.shape
+        lens = self._lens(lens, B, theta.device)
+        Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
+        self.call("sdp_affine_semiglobal_forward_value_f32", AFFINE_SEMIGLOBAL_KERNELS[201], dev, theta, gap_open, gap_extend, Vt, B, N, M,
+                  lens, free_ends, 0)
+        return Vt
+
+    def affine_semiglobal_backward(self, state, Et, shape, free_ends, lens=None, want_GO=True, want_GX=True):
+        """The mirror sweep over the records of affine_semiglobal_forward (the same free_ends) -> (E (B,N,M), GO (B,N,M) or None,
+        GX (B,N,M) or None), +0 outside each pair's block.  (No Vt: the end weights are in `state`.)"""
+        dev = self.device_of(state)
+        free_ends = self._free_ends(free_ends)
+        B, N, M = shape
+        check_args(state, torch.float32, None, True, state=state)
+        check_args(state, Et=Et)
+        Et = Et.detach().to(torch.float32).expand(B).contiguous()
+        lens = self._lens(lens, B, state.device)
+        E = torch.empty((B, N, M), dtype=torch.float32, device=state.device)
+        GO = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if want_GO else None
+        GX = torch.empty((B, N, M), dtype=torch.float32, device=state.device) if want_GX else None
+        self.call("sdp_affine_semiglobal_backward_f32", AFFINE_SEMIGLOBAL_KERNELS[202], dev, state, Et, E, GO, GX, B, N, M, lens, free_ends, 0)
+        return E, GO, GX
+
     def affine_global_adjoint_forward(self, state, ZE, ZGO, ZGX, shape, lens=None, state_d_out=None):
         """The adjoint forward sweep over the records of affine_global_forward -> (Vtd (B,), state_d): ZE, ZGO, ZGX (B,N,M) the
         cotangents of E, GO and GX, each may be None (zeros) but not all three; state_d the dot records (opaque float32 tensor of
@@ -1131,8 +1188,11 @@ SPARSEMAX_KERNELS = {150: "sdp_sparsemax_fwd_kernel", 151: "sdp_sparsemax_val_ke
 SPARSEMAX_ADJOINT_KERNELS = {154: "sdp_sparsemax_adj_fwd_kernel", 155: "sdp_sparsemax_adj_bwd_kernel"}
 # kernel id (csrc/sdp_affine_global.h) -> symbol of the affine-gap soft global operator's kernels
 AFFINE_GLOBAL_KERNELS = {180: "sdp_affine_global_fwd_kernel", 181: "sdp_affine_global_val_kernel", 182: "sdp_affine_global_bwd_kernel"}
+# of its free-end-gap member (the same header; csrc/sdp_affine_semiglobal.hip)
+AFFINE_SEMIGLOBAL_KERNELS = {200: "sdp_affine_semiglobal_fwd_kernel", 201: "sdp_affine_semiglobal_val_kernel",
+                             202: "sdp_affine_semiglobal_bwd_kernel"}
 # of its adjoint pair (the same header)
-AFFINE_GLOBAL_ADJOINT_KERNELS = {193: "sdp_affine_global_adj_fwd_kernel", 194: "sdp_affine_global_adj_bwd_kernel"}
+AFFINE_GLOBAL_ADJOINT_KERNELS ={193: "sdp_affine_global_adj_fwd_kernel", 194: "sdp_affine_global_adj_bwd_kernel"}
 # and of the kernel that samples from its posterior (csrc/sdp_affine_global_sample.h)
 AFFINE_GLOBAL_SAMPLE_KERNELS = {190: "sdp_affine_global_sample_kernel"}
 # kernel id (csrc/sdp_affine_local.h) -> symbol of the affine-gap soft local operator's kernels

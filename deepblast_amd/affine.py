@@ -36,6 +36,10 @@ alignment; the third order is not built.  Its hard (max-plus) member is built as
 AffineGlobalDecoder.optimal_paths / optimal_alignments / optimal_score on every decoder, and AffineGlobalDecoder(operator="hardmax").
 Sampling from the global posterior is built too (include/sdp.h: sdp_affine_global_sample_paths_f32):
 AffineGlobalDecoder.sample_paths / sample_alignments, on every decoder.
+
+The SEMI-GLOBAL form -- the global operator with free end gaps: a whole query inside a longer target, or two sequences that overlap
+at their ends -- is AffineSemiGlobalDecoder(free="y" | "x" | "both") at the end of this file (include/sdp.h:
+sdp_affine_semiglobal_*): softmax and first order only.
 """
 import torch
 
@@ -529,7 +533,8 @@ class AffineGlobalDecoder(torch.nn.Module):
     (include/sdp.h: sdp_affine_global_sample_paths_f32); only sampling a problem that is swept transposed is out
     of scope.
     The second order is opt-in (`second_order=True`).  Out of scope, none of it built: the third order, float64, the
-    `distributed` wrappers, `search_scores`, `losses.decode_loss`, free end gaps, and the reference's zero border."""
+    `distributed` wrappers, `search_scores`, `losses.decode_loss`, and the reference's zero border.  This decoder has no
+    free end gaps: those are AffineSemiGlobalDecoder (below; first order)."""
 
     def __init__(self, operator="softmax", second_order=False):
         super().__init__()
@@ -660,3 +665,142 @@ class AffineGlobalDecoder(torch.nn.Module):
         states, counts = states.cpu().numpy(), counts.cpu().numpy()
         return Vt, [[[tuple(int(v) for v in row) for row in states[b, k, :counts[b, k]]] for k in range(counts.shape[1])]
                     for b in range(counts.shape[0])]
+
+
+# ---- the affine-gap soft SEMI-GLOBAL operator: free end gaps (include/sdp.h: sdp_affine_semiglobal_*) ----
+FREE_X, FREE_Y = 1, 2          # the bits of `free_ends`: rows may hang over / columns may hang over
+_FREE_ENDS = {"x": FREE_X, "y": FREE_Y, "both": FREE_X | FREE_Y}
+
+
+def _swapped(free_ends):
+    """`free_ends` of the transposed problem: x <-> y"""
+    return ((free_ends & FREE_X) << 1) | ((free_ends & FREE_Y) >> 1)
+
+
+class AffineSemiGlobalFunctionBackward(torch.autograd.Function):
+    """(E, GO, GX) of the semi-global mirror sweep.  Differentiable in nothing: this is the node at which a second differentiation
+    stops, with a message that names the reason."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, Et, state, lens, free_ends, want_E, want_GO, want_GX):
+        # (the three inputs are here for the graph alone: the gradients depend on them, and a second differentiation must arrive below)
+        E, GO, GX = _engine.get_engine().affine_semiglobal_backward(state, Et, tuple(theta.shape), free_ends, lens, want_GO=want_GO,
+                                                                    want_GX=want_GX)
+        return (E if want_E else None), GO, GX
+
+    @staticmethod
+    def backward(ctx, ZE, ZGO, ZGX):
+        raise NotImplementedError("the affine-gap soft semi-global operator is first order only: its second order (an adjoint pair "
+                                  "for sdp_affine_semiglobal_*) is not built")
+
+
+class AffineSemiGlobalFunction(torch.autograd.Function):
+    """Vt = affine_semiglobal(theta, gap_open, gap_extend) under `free_ends` (bit 0: x, bit 1: y); backward: theta.grad = E,
+    gap_open.grad = GO, gap_extend.grad = GX, one mirror sweep; GO and GX are computed only when their input needs a gradient.
+    Once differentiable: differentiating E, GO or GX raises NotImplementedError (AffineSemiGlobalFunctionBackward)."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, lens=None, free_ends=FREE_Y):
+        Vt, state = _engine.get_engine().affine_semiglobal_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), free_ends, lens)
+        ctx.save_for_backward(theta, gap_open, gap_extend, state)
+        ctx.lens, ctx.free_ends = lens, free_ends
+        return Vt
+
+    @staticmethod
+    def backward(ctx, Et):
+        theta, gap_open, gap_extend, state = ctx.saved_tensors
+        E, GO, GX = AffineSemiGlobalFunctionBackward.apply(theta, gap_open, gap_extend, Et, state, ctx.lens, ctx.free_ends,
+                                                           *ctx.needs_input_grad[:3])
+        return E, GO, GX, None, None
+
+
+class AffineSemiGlobalDecoder(torch.nn.Module):
+    """Affine-gap SEMI-GLOBAL alignment scores, their gradients and the posterior alignment matrix, on a ROCm device in float32:
+    AffineGlobalDecoder's operator with FREE END GAPS (include/sdp.h: sdp_affine_semiglobal_*).  The planes and the
+    recurrences of Vx, Vm, Vy are AffineGlobalDecoder's; what changes is where a path may start and end:
+
+        free="y"     the columns of y that hang over either end of x cost nothing: a path starts in any cell of row 1 and ends in
+                     any cell of row n -- the whole of x aligned INSIDE a longer y (a domain against a full-length protein);
+        free="x"     the same for rows: a path starts in any cell of column 1 and ends in any cell of column m;
+        free="both"  both: overlap alignment, two sequences that overlap at their ends.
+
+    A path starts with a match step into its start cell (never with a gap step), and Vt is the log of the sum of exp(score) over
+    every such path: Vt = log sum over the end cells and the planes of exp V_s[i,j].  Any other `free` raises ValueError; for no
+    free end there is AffineGlobalDecoder.  Parity unpinned: the kernels are held to the float64 definition.
+
+    forward(theta, gap_open, gap_extend, lengths=None) -> Vt (B,), differentiable ONCE: theta.grad = E, gap_open.grad = GO,
+    gap_extend.grad = GX, all true gradients; GO and GX are computed only when their input needs a gradient.  Differentiating a
+    gradient raises NotImplementedError.
+    decode(theta, gap_open, gap_extend, lengths=None) -> E (B, N, M) for Et = 1, the posterior probability that a cell lies on the
+    alignment; no autograd graph.
+    score(theta, gap_open, gap_extend, lengths=None) -> Vt (B,) through the value-only sweep: no state is allocated, no graph.
+    Inputs, lengths, forbidden gaps (-inf in gap_open / gap_extend: the matching gradient is exactly +0), the pair without a path
+    (Vt = -inf, gradients +0; with free="y" and every gap forbidden: n > m), the empty pair (Vt = 0) and the errors raised are
+    AffineGlobalDecoder's.  Problems wider than the column limit (2048) are swept transposed, with x and y of `free` swapped, and
+    the results come back in the caller's coordinates.
+    Not built, each raises NotImplementedError rather than answer for the closed border: operator="hardmax", second_order=True,
+    optimal_paths / optimal_alignments / optimal_score, sample_paths / sample_alignments.  Out of scope as well: float64, the
+    `distributed` wrappers, `search_scores`, `losses.decode_loss`, a one-score form, and the reference's zero border."""
+
+    def __init__(self, free="y", operator="softmax", second_order=False):
+        super().__init__()
+        if free not in _FREE_ENDS:
+            raise ValueError(f"free must be 'y', 'x' or 'both', got {free!r} (for no free end there is AffineGlobalDecoder)")
+        if operator == "hardmax":
+            raise NotImplementedError("the hard-max member of the affine-gap semi-global family (optimal alignments with free end "
+                                      "gaps) is not built")
+        if operator != "softmax":
+            raise ValueError(f"operator must be 'softmax', got {operator!r}")
+        if second_order:
+            raise NotImplementedError("the second order of the affine-gap soft semi-global operator (an adjoint pair for "
+                                      "sdp_affine_semiglobal_*) is not built")
+        self.free = free
+        self.free_ends = _FREE_ENDS[free]
+        self.operator = operator
+        self.second_order = False
+
+    def _oriented(self, theta, gap_open, gap_extend, lengths):
+        """_oriented, and `free_ends` as the sweep sees it: x <-> y when the problem is swept transposed"""
+        theta, gap_open, gap_extend, lengths, transposed = _oriented(theta, gap_open, gap_extend, lengths)
+        return theta, gap_open, gap_extend, lengths, transposed, (_swapped(self.free_ends) if transposed else self.free_ends)
+
+    def forward(self, theta, gap_open, gap_extend, lengths=None):
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, _, free_ends = self._oriented(theta, gap_open, gap_extend, lengths)
+        return AffineSemiGlobalFunction.apply(theta, gap_open, gap_extend, lengths, free_ends)
+
+    def decode(self, theta, gap_open, gap_extend, lengths=None):
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, transposed, free_ends = self._oriented(theta, gap_open, gap_extend, lengths)
+        eng = _engine.get_engine()
+        with torch.no_grad():
+            _, state = eng.affine_semiglobal_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), free_ends, lengths)
+            E, _, _ = eng.affine_semiglobal_backward(state, torch.ones((), dtype=torch.float32, device=theta.device), tuple(theta.shape),
+                                                     free_ends, lengths, want_GO=False, want_GX=False)
+        return E.transpose(1, 2) if transposed else E
+
+    def score(self, theta, gap_open, gap_extend, lengths=None):
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, _, free_ends = self._oriented(theta, gap_open, gap_extend, lengths)
+        with torch.no_grad():
+            return _engine.get_engine().affine_semiglobal_forward_value(theta.detach(), gap_open.detach(), gap_extend.detach(), free_ends,
+                                                                        lengths)
+
+    def _not_built(self, what):
+        raise NotImplementedError(f"{what} is not built for the affine-gap semi-global operator (free end gaps): the max-plus member "
+                                  "and its walk, and sampling, exist for AffineGlobalDecoder and AffineLocalDecoder only")
+
+    def optimal_paths(self, *args, **kwargs):
+        self._not_built("optimal_paths")
+
+    def optimal_alignments(self, *args, **kwargs):
+        self._not_built("optimal_alignments")
+
+    def optimal_score(self, *args, **kwargs):
+        self._not_built("optimal_score")
+
+    def sample_paths(self, *args, **kwargs):
+        self._not_built("sample_paths")
+
+    def sample_alignments(self, *args, **kwargs):
+        self._not_built("sample_alignments")

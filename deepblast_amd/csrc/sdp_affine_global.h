@@ -62,6 +62,15 @@ __host__ __device__ inline int adjoint_waves_for(int N, int M)
 // kernel ids sdp_kernel_name answers for (192 and 195 answer NULL)
 enum { ID_ADJ_FWD = 193, ID_ADJ_BWD = 194 };
 
+// ---- free end gaps (csrc/sdp_affine_semiglobal.hip): the first order's geometry, ring and waves; the state grows by a tail ----
+constexpr int FREE_ENDS_MASK = 3;   // the bits of `free_ends`: 1 = x (rows may hang over), 2 = y (columns may hang over)
+// words of one pair's tail behind the records of all pairs: the exponents of the end cells, one per row (column m) and one per
+// column (row n)
+__host__ __device__ inline size_t end_tail_words(int N, int M) { return (size_t)N + (size_t)M; }
+
+// kernel ids sdp_kernel_name answers for (199 and 203 answer NULL)
+enum { ID_SEMI_FWD = 200, ID_SEMI_VAL = 201, ID_SEMI_BWD = 202 };
+
 }  // namespace sdp_affine_global
 
 extern "C" {
@@ -75,6 +84,12 @@ __global__ void sdp_affine_global_adj_fwd_kernel(const float4 *state, const floa
                                                  float *Vtd, const int *lens, int N, int M, int waves);
 __global__ void sdp_affine_global_adj_bwd_kernel(const float4 *state, const float4 *stated, const float *Et, float *Ed, float *GOd,
                                                  float *GXd, const int *lens, int N, int M, int waves);
+__global__ void sdp_affine_semiglobal_fwd_kernel(const float *theta, const float *O, const float *X, float4 *state, float *Vt,
+                                                 const int *lens, int N, int M, int waves, int free_ends);
+__global__ void sdp_affine_semiglobal_val_kernel(const float *theta, const float *O, const float *X, float4 *state, float *Vt,
+                                                 const int *lens, int N, int M, int waves, int free_ends);
+__global__ void sdp_affine_semiglobal_bwd_kernel(const float4 *state, const float *Et, float *E, float *GO, float *GX, const int *lens,
+                                                 int N, int M, int waves, int free_ends);
 }
 
 #endif  // SDP_AFFINE_GLOBAL_H_

@@ -671,6 +671,17 @@ int raise_affine_global_limit(int device)
                               sdp_affine_global::LDS_BUDGET);
 }
 
+// the family's free-end-gap member (csrc/sdp_affine_semiglobal.hip): the same ring, the same budget
+int raise_affine_semiglobal_limit(int device)
+{
+    static thread_local unsigned long long raised = 0;
+    return raise_strip_limits(raised, device,
+                              {{(const void *)sdp_affine_semiglobal_fwd_kernel, "hipFuncSetAttribute(sdp_affine_semiglobal_fwd_kernel)"},
+                               {(const void *)sdp_affine_semiglobal_val_kernel, "hipFuncSetAttribute(sdp_affine_semiglobal_val_kernel)"},
+                               {(const void *)sdp_affine_semiglobal_bwd_kernel, "hipFuncSetAttribute(sdp_affine_semiglobal_bwd_kernel)"}},
+                              sdp_affine_global::LDS_BUDGET);
+}
+
 // its adjoint pair: the adjoint forward sweep keeps the first order's ring, the adjoint backward sweep six words per column
 // (sdp_affine_global::adjoint_lds_bytes), both up to 160 KB
 int raise_affine_global_adjoint_limit(int device)
@@ -861,6 +872,10 @@ const char *sdp_kernel_name(int kernel_id)
     // the affine-gap soft global operator's adjoint pair (csrc/sdp_affine_global_adj.hip)
     case sdp_affine_global::ID_ADJ_FWD: return "sdp_affine_global_adj_fwd_kernel";
     case sdp_affine_global::ID_ADJ_BWD: return "sdp_affine_global_adj_bwd_kernel";
+    // the affine-gap soft semi-global operator: free end gaps (csrc/sdp_affine_semiglobal.hip)
+    case sdp_affine_global::ID_SEMI_FWD: return "sdp_affine_semiglobal_fwd_kernel";
+    case sdp_affine_global::ID_SEMI_VAL: return "sdp_affine_semiglobal_val_kernel";
+    case sdp_affine_global::ID_SEMI_BWD: return "sdp_affine_semiglobal_bwd_kernel";
     }
     return nullptr;
 }
@@ -886,6 +901,7 @@ int sdp_init(int device)
     if (int rc = raise_affine_local_adjoint_limit(device)) return rc;
     if (int rc = raise_hard_affine_limit(device)) return rc;
     if (int rc = raise_affine_global_limit(device)) return rc;
+    if (int rc = raise_affine_semiglobal_limit(device)) return rc;
     return raise_affine_global_adjoint_limit(device);
 }
 
@@ -1968,6 +1984,65 @@ int sdp_affine_global_backward_f32(const void *state, const float *Et, float *E,
     const int W = sdp_affine_global::waves_for(N, M);
     return strip_launch(sdp_affine_global_bwd_kernel, "sdp_affine_global_bwd_kernel", B, W, sdp_affine_global::sweep_lds_bytes(W, M), stream,
                         static_cast<const float4 *>(state), Et, E, GO, GX, lens, N, M, W);
+}
+
+// ---- its free-end-gap member (csrc/sdp_affine_semiglobal.hip): the same launches with one more kernel argument, `free_ends` ----
+// `flags`: none is defined, any bit is refused; `free_ends`: bit 0 = x, bit 1 = y, any other bit is refused.  free_ends = 0 is the
+// global operator: its kernels are launched (the tail of the state is then not used)
+static int affine_semiglobal_args(int B, int N, int M, int free_ends, int flags)
+{
+    if (int rc = flagless_args("sdp_affine_semiglobal", B, N, M, flags)) return rc;
+    if (free_ends & ~sdp_affine_global::FREE_ENDS_MASK)
+        return fail(SDP_E_VARIANT, "sdp_affine_semiglobal_*: free_ends must be 0 .. 3 (bit 0: x, bit 1: y)");
+    return 0;
+}
+
+size_t sdp_affine_semiglobal_state_bytes(int B, int N, int M)
+{
+    const size_t records = sdp_affine_global_state_bytes(B, N, M);
+    return records ? records + (size_t)B * sdp_affine_global::end_tail_words(N, M) * sizeof(int32_t) : 0;
+}
+
+static int affine_semiglobal_forward(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int B, int N,
+                                     int M, const int32_t *lens, int free_ends, int flags, int device, void *stream, bool records)
+{
+    if (int rc = affine_semiglobal_args(B, N, M, free_ends, flags)) return rc;
+    if (free_ends == 0) return affine_global_forward(theta, gap_open, gap_extend, state, Vt, B, N, M, lens, flags, device, stream, records);
+    if (int rc = use_device(device)) return rc;
+    if (int rc = raise_affine_semiglobal_limit(device)) return rc;
+    const int W = sdp_affine_global::waves_for(N, M);
+    return strip_launch(records ? sdp_affine_semiglobal_fwd_kernel : sdp_affine_semiglobal_val_kernel,
+                        records ? "sdp_affine_semiglobal_fwd_kernel" : "sdp_affine_semiglobal_val_kernel", B, W,
+                        sdp_affine_global::sweep_lds_bytes(W, M), stream, theta, gap_open, gap_extend, static_cast<float4 *>(state), Vt, lens, N, M,
+                        W, free_ends);
+}
+
+int sdp_affine_semiglobal_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int B,
+                                      int N, int M, const int32_t *lens, int free_ends, int flags, int device, void *stream)
+{
+    if (!theta || !gap_open || !gap_extend || !state || !Vt) return fail(SDP_E_NULLPTR, "sdp_affine_semiglobal_forward_f32: null pointer");
+    return affine_semiglobal_forward(theta, gap_open, gap_extend, state, Vt, B, N, M, lens, free_ends, flags, device, stream, true);
+}
+
+int sdp_affine_semiglobal_forward_value_f32(const float *theta, const float *gap_open, const float *gap_extend, float *Vt, int B, int N,
+                                            int M, const int32_t *lens, int free_ends, int flags, int device, void *stream)
+{
+    if (!theta || !gap_open || !gap_extend || !Vt) return fail(SDP_E_NULLPTR, "sdp_affine_semiglobal_forward_value_f32: null pointer");
+    return affine_semiglobal_forward(theta, gap_open, gap_extend, nullptr, Vt, B, N, M, lens, free_ends, flags, device, stream, false);
+}
+
+int sdp_affine_semiglobal_backward_f32(const void *state, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
+                                       const int32_t *lens, int free_ends, int flags, int device, void *stream)
+{
+    if (!state || !Et || !E)
+        return fail(SDP_E_NULLPTR, "sdp_affine_semiglobal_backward_f32: null pointer (state, Et, E; GO and GX may be NULL)");
+    if (int rc = affine_semiglobal_args(B, N, M, free_ends, flags)) return rc;
+    if (free_ends == 0) return sdp_affine_global_backward_f32(state, Et, E, GO, GX, B, N, M, lens, flags, device, stream);
+    if (int rc = use_device(device)) return rc;
+    if (int rc = raise_affine_semiglobal_limit(device)) return rc;
+    const int W = sdp_affine_global::waves_for(N, M);
+    return strip_launch(sdp_affine_semiglobal_bwd_kernel, "sdp_affine_semiglobal_bwd_kernel", B, W, sdp_affine_global::sweep_lds_bytes(W, M),
+                        stream, static_cast<const float4 *>(state), Et, E, GO, GX, lens, N, M, W, free_ends);
 }
 
 // ---- its second order (csrc/sdp_affine_global_adj.hip): the adjoint pair; the adjoint backward sweep has a wave count of its own ----

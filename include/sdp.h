@@ -884,7 +884,8 @@ int sdp_hard_affine_global_walk_f32(const void *state, const int32_t *ends, cons
  * lies more than about 2^149 (103 in the scores' own units) below the other: exp(theta + O) and exp(theta + X) of a cell share one
  * exponent, and such an opening (or extension) counts as forbidden.
  * The second order is sdp_affine_global_adjoint_* below.  NOT built (the hard-max member is sdp_hard_affine_global_* above, sampling
- * sdp_affine_global_sample_paths_f32 below): the third order, float64, free end gaps, the reference's zero border.
+ * sdp_affine_global_sample_paths_f32 below): the third order, float64, the reference's zero border.  These entries have no
+ * free end gaps: those are sdp_affine_semiglobal_* below.
  *   state    sdp_affine_global_state_bytes(B, N, M) bytes (0 on a bad shape), DEVICE, caller-owned: 48 bytes per cell -- one record
  *            {q[s<-x], q[s<-m], q[s<-y], w_s} per plane s, w_s zero but in the end cell -- in a private layout; written by
  *            sdp_affine_global_forward_f32, read by sdp_affine_global_backward_f32 with the same B, N, M, lens (which needs neither
@@ -904,6 +905,37 @@ int sdp_affine_global_forward_value_f32(const float *theta, const float *gap_ope
                                         const int32_t *lens, int flags, int device, void *stream);
 int sdp_affine_global_backward_f32(const void *state, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
                                    const int32_t *lens, int flags, int device, void *stream);
+
+/* The AFFINE-GAP SOFT SEMI-GLOBAL operator (csrc/sdp_affine_semiglobal.hip): the operator above with FREE END GAPS,
+ * first order.  (Added after SDP_VERSION 106 without a version change: look the symbols up.  sdp_kernel_name answers 200, 201 and
+ * 202 for its kernels; 199 and 203 answer NULL.)  Planes, recurrences, q, E, GO, GX, inputs, envelope and conventions are those of
+ * sdp_affine_global_*; two things change, under the two bits of `free_ends`:
+ *     bit 1 (2), y: the columns of y that hang over either end of x cost nothing -- a path may START in any cell of row 1 and END
+ *                   in any cell of row n (a whole query x aligned inside a longer target y);
+ *     bit 0 (1), x: the same for rows -- a path may start in any cell of column 1 and end in any cell of column m.
+ *     start   a start cell is entered in plane m alone, Vm[i,j] gets the term theta[i,j]: START (exp V = 1) stands above-left of
+ *             it and is seen by the diagonal step only -- no path begins with a gap step.  Above-left of (1,1) always, of (1,j)
+ *             for every j <= m under y, of (i,1) for every i <= n under x.
+ *     end     Vt = log sum over (i,j) in Ends, s of exp V_s[i,j];  Ends = {(n,m)}, plus {(n,j)} under y, plus {(i,m)} under x (the
+ *             corner once);  Eb_s[i,j] += Et exp(V_s[i,j] - Vt) at every end cell.
+ * Both bits: overlap alignment.  free_ends = 0 is legal and is the global operator: the bits of sdp_affine_global_*.  Transposition
+ * swaps the two bits and the planes x and y.  A pair without a path (every gap forbidden, free_ends = 2, n > m) has Vt = -inf and
+ * +0 gradients; an empty pair has Vt = 0.  No floating-point atomics: the end cells are summed in a fixed order (float64 mantissa,
+ * integer exponent), two calls give the same bits, and the value entry gives the bits of the forward entry's Vt.
+ *   state      sdp_affine_semiglobal_state_bytes(B, N, M) bytes (0 on a bad shape): sdp_affine_global_state_bytes(B, N, M) plus a tail
+ *              of (N + M) int32 per pair, the exponents of the end cells; the records' w_s is nonzero in every end cell.  Written by
+ *              the forward entry, read by the backward entry with the same B, N, M, lens and free_ends.
+ *   free_ends  bit 0 = x, bit 1 = y; any other bit: SDP_E_VARIANT.
+ *   flags      this family defines none: any bit is refused (SDP_E_VARIANT).
+ * Launch geometry, LDS, argument checks, codes and limits are those of sdp_affine_global_*.  NOT built: the hard-max member and its
+ * walk, sampling, the second order, float64, a one-score form, the reference's zero border. */
+size_t sdp_affine_semiglobal_state_bytes(int B, int N, int M);
+int sdp_affine_semiglobal_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int B,
+                                      int N, int M, const int32_t *lens, int free_ends, int flags, int device, void *stream);
+int sdp_affine_semiglobal_forward_value_f32(const float *theta, const float *gap_open, const float *gap_extend, float *Vt, int B, int N,
+                                            int M, const int32_t *lens, int free_ends, int flags, int device, void *stream);
+int sdp_affine_semiglobal_backward_f32(const void *state, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
+                                       const int32_t *lens, int free_ends, int flags, int device, void *stream);
 
 /* Its SECOND ORDER (csrc/sdp_affine_global_adj.hip): the adjoint pair, what sdp_affine_local_adjoint_* is to the local
  * operator, with the global operator's start and end.  (Added after SDP_VERSION 106 without a version change: look the symbols up.
