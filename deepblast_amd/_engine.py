@@ -1020,8 +1020,9 @@ class HipEngine:
         plane names handed over."""
         return self._hard_affine_forward("local", HARD_AFFINE_LOCAL_KERNELS, 170, theta, gap_open, gap_extend, lens, ymx)
 
-    def _hard_affine_forward(self, member, kernels, first, theta, gap_open, gap_extend, lens, ymx):
-        """the pointer sweep of sdp_hard_affine_<member>_*; kernels[first], kernels[first + 1]: its two tie orders"""
+    def _hard_affine_forward(self, member, kernels, first, theta, gap_open, gap_extend, lens, ymx, extra=()):
+        """the pointer sweep of sdp_hard_affine_<member>_*; kernels[first], kernels[first + 1]: its two tie orders; extra: the
+        entry's arguments between lens and variant (the semi-global member's free_ends)"""
         dev = self.device_of(theta)
         theta, gap_open, gap_extend = self._hard_affine_inputs(theta, gap_open, gap_extend)
         B, N, M = theta.shape
@@ -1031,14 +1032,14 @@ class HipEngine:
         Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
         ends = torch.empty((B, 3), dtype=torch.int32, device=theta.device)
         self.call(f"sdp_hard_affine_{member}_forward_f32", kernels[first + (1 if ymx else 0)], dev, theta, gap_open, gap_extend,
-                  state, Vt, ends, B, N, M, lens, self._hard_affine_variant(ymx))
+                  state, Vt, ends, B, N, M, lens, *extra, self._hard_affine_variant(ymx))
         return Vt, state, ends
 
     def hard_affine_local_forward_value(self, theta, gap_open, gap_extend, lens=None, ymx=False, want_ends=True):
         """-> (Vt (B,), ends (B, 3) int32 or None): the same sweep with the pointers compiled out (the same bits)."""
         return self._hard_affine_forward_value("local", HARD_AFFINE_LOCAL_KERNELS, 172, theta, gap_open, gap_extend, lens, ymx, want_ends)
 
-    def _hard_affine_forward_value(self, member, kernels, first, theta, gap_open, gap_extend, lens, ymx, want_ends):
+    def _hard_affine_forward_value(self, member, kernels, first, theta, gap_open, gap_extend, lens, ymx, want_ends, extra=()):
         dev = self.device_of(theta)
         theta, gap_open, gap_extend = self._hard_affine_inputs(theta, gap_open, gap_extend)
         B, N, M = theta.shape
@@ -1046,7 +1047,7 @@ class HipEngine:
         Vt = torch.empty(B, dtype=torch.float32, device=theta.device)
         ends = torch.empty((B, 3), dtype=torch.int32, device=theta.device) if want_ends else None
         self.call(f"sdp_hard_affine_{member}_forward_value_f32", kernels[first + (1 if ymx else 0)], dev, theta, gap_open,
-                  gap_extend, Vt, ends, B, N, M, lens, self._hard_affine_variant(ymx))
+                  gap_extend, Vt, ends, B, N, M, lens, *extra, self._hard_affine_variant(ymx))
         return Vt, ends
 
     def hard_affine_local_walk(self, state, ends, shape, lens=None, Et=None, ymx=False, want_E=True, want_GO=False, want_GX=False,
@@ -1096,6 +1097,36 @@ class HipEngine:
         """hard_affine_local_walk on the pointers of hard_affine_global_forward (the state format, ends and the stop at START are the
         same), through sdp_hard_affine_global_walk_f32."""
         return self.hard_affine_local_walk(state, ends, shape, lens, entry="sdp_hard_affine_global_walk_f32", **kw)
+
+    # ---- the hard affine-gap semi-global operator (include/sdp.h: sdp_hard_affine_semiglobal_*): free end gaps ----
+    def _hard_affine_semiglobal(self, free_ends, first):
+        """-> (free_ends checked, the kernel table and the id of the first of the two tie orders a launch under it takes:
+        free_ends = 0 is the global member and launches its kernels)"""
+        free_ends = self._free_ends(free_ends)
+        if free_ends == 0:
+            return free_ends, HARD_AFFINE_GLOBAL_KERNELS, first - 20
+        return free_ends, HARD_AFFINE_SEMIGLOBAL_KERNELS, first
+
+    def hard_affine_semiglobal_forward(self, theta, gap_open, gap_extend, free_ends, lens=None, ymx=False):
+        """-> (Vt (B,), state, ends (B, 3) int32): hard_affine_global_forward with free end gaps -- free_ends bit 0: x (rows may hang
+        over: a path starts in column 0 and ends in column m - 1), bit 1: y (columns: row 0 and row n - 1); 0: the global member's
+        bits.  Vt the first maximum over the end cells and their planes, -inf for a pair without a path, +0 for an empty pair; ends
+        its 0-based cell and plane, (-1, -1, -1) where there is no path; the pointers in the local member's format.  ymx: the
+        tensors are a TRANSPOSED problem and free_ends its swapped bits; ends come back in the coordinates and plane names handed
+        over."""
+        free_ends, kernels, first = self._hard_affine_semiglobal(free_ends, 205)
+        return self._hard_affine_forward("semiglobal", kernels, first, theta, gap_open, gap_extend, lens, ymx, extra=(free_ends,))
+
+    def hard_affine_semiglobal_forward_value(self, theta, gap_open, gap_extend, free_ends, lens=None, ymx=False, want_ends=True):
+        """-> (Vt (B,), ends (B, 3) int32 or None): the same sweep with the pointers compiled out (the same bits)."""
+        free_ends, kernels, first = self._hard_affine_semiglobal(free_ends, 207)
+        return self._hard_affine_forward_value("semiglobal", kernels, first, theta, gap_open, gap_extend, lens, ymx, want_ends,
+                                               extra=(free_ends,))
+
+    def hard_affine_semiglobal_walk(self, state, ends, shape, lens=None, **kw):
+        """hard_affine_local_walk on the pointers of hard_affine_semiglobal_forward (the state format, ends and the stop at START
+        are the same: the walk stops in the start cell wherever that is), through sdp_hard_affine_semiglobal_walk_f32."""
+        return self.hard_affine_local_walk(state, ends, shape, lens, entry="sdp_hard_affine_semiglobal_walk_f32", **kw)
 
     # ---- alignments sampled from the posterior (include/sdp.h: sdp_sample_paths_*) -------------------
     def sample_paths(self, state, shape, variant, K, lens=None, seed=0, sample0=0, exact_state=False, transposed=False,
@@ -1208,6 +1239,9 @@ HARD_AFFINE_LOCAL_KERNELS = {170: "sdp_hard_affine_local_fwd_kernel", 171: "sdp_
 # the sweeps of its global member (the same header); the walk is kernel 174
 HARD_AFFINE_GLOBAL_KERNELS = {185: "sdp_hard_affine_global_fwd_kernel", 186: "sdp_hard_affine_global_fwd_t_kernel",
                               187: "sdp_hard_affine_global_val_kernel", 188: "sdp_hard_affine_global_val_t_kernel"}
+# and of its semi-global member, free end gaps (the same header); the walk is kernel 174
+HARD_AFFINE_SEMIGLOBAL_KERNELS = {205: "sdp_hard_affine_semiglobal_fwd_kernel", 206: "sdp_hard_affine_semiglobal_fwd_t_kernel",
+                                  207: "sdp_hard_affine_semiglobal_val_kernel", 208: "sdp_hard_affine_semiglobal_val_t_kernel"}
 
 _SWEEPS = ("sdp_forward", "sdp_backward", "sdp_adjoint_forward", "sdp_adjoint_backward")
 # dtype -> (suffix of the four sweeps' entries, their launch labels (float32: where the library's plan is not asked),

@@ -162,6 +162,16 @@ SIGNATURES = {
     "sdp_hard_affine_global_walk_f32": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_i32p,
                                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int,
                                                        ctypes.c_void_p]),
+    "sdp_hard_affine_semiglobal_state_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "sdp_hard_affine_semiglobal_forward_f32": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _c_f32p, _c_i32p, ctypes.c_int,
+                                                              ctypes.c_int, ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                              ctypes.c_void_p]),
+    "sdp_hard_affine_semiglobal_forward_value_f32": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_i32p, ctypes.c_int, ctypes.c_int,
+                                                                    ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                                    ctypes.c_void_p]),
+    "sdp_hard_affine_semiglobal_walk_f32": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_i32p,
+                                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int,
+                                                           ctypes.c_void_p]),
     "sdp_affine_global_state_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "sdp_affine_global_forward_f32": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _c_f32p, ctypes.c_int, ctypes.c_int,
                                                      ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),

@@ -39,7 +39,9 @@ AffineGlobalDecoder.sample_paths / sample_alignments, on every decoder.
 
 The SEMI-GLOBAL form -- the global operator with free end gaps: a whole query inside a longer target, or two sequences that overlap
 at their ends -- is AffineSemiGlobalDecoder(free="y" | "x" | "both") at the end of this file (include/sdp.h:
-sdp_affine_semiglobal_*): softmax and first order only.
+sdp_affine_semiglobal_*): softmax and first order only.  Its hard (max-plus) member -- the optimal alignment with
+free end gaps, its score, end, path and subgradients -- is a class of its own, HardAffineSemiGlobalDecoder(free=...), below it
+(include/sdp.h: sdp_hard_affine_semiglobal_*).
 """
 import torch
 
@@ -738,8 +740,10 @@ class AffineSemiGlobalDecoder(torch.nn.Module):
     (Vt = -inf, gradients +0; with free="y" and every gap forbidden: n > m), the empty pair (Vt = 0) and the errors raised are
     AffineGlobalDecoder's.  Problems wider than the column limit (2048) are swept transposed, with x and y of `free` swapped, and
     the results come back in the caller's coordinates.
-    Not built, each raises NotImplementedError rather than answer for the closed border: operator="hardmax", second_order=True,
-    optimal_paths / optimal_alignments / optimal_score, sample_paths / sample_alignments.  Out of scope as well: float64, the
+    Not built INTO THIS CLASS, each raises NotImplementedError rather than answer for the closed border: operator="hardmax",
+    second_order=True, optimal_paths / optimal_alignments / optimal_score, sample_paths / sample_alignments.  The hard-max member
+    and the optimal_* methods are HardAffineSemiGlobalDecoder(free=...) below; sampling and the second order exist for no
+    semi-global class.  Out of scope as well: float64, the
     `distributed` wrappers, `search_scores`, `losses.decode_loss`, a one-score form, and the reference's zero border."""
 
     def __init__(self, free="y", operator="softmax", second_order=False):
@@ -748,7 +752,7 @@ class AffineSemiGlobalDecoder(torch.nn.Module):
             raise ValueError(f"free must be 'y', 'x' or 'both', got {free!r} (for no free end there is AffineGlobalDecoder)")
         if operator == "hardmax":
             raise NotImplementedError("the hard-max member of the affine-gap semi-global family (optimal alignments with free end "
-                                      "gaps) is not built")
+                                      "gaps) is not built into AffineSemiGlobalDecoder: it is HardAffineSemiGlobalDecoder(free=...)")
         if operator != "softmax":
             raise ValueError(f"operator must be 'softmax', got {operator!r}")
         if second_order:
@@ -787,8 +791,9 @@ class AffineSemiGlobalDecoder(torch.nn.Module):
                                                                         lengths)
 
     def _not_built(self, what):
-        raise NotImplementedError(f"{what} is not built for the affine-gap semi-global operator (free end gaps): the max-plus member "
-                                  "and its walk, and sampling, exist for AffineGlobalDecoder and AffineLocalDecoder only")
+        raise NotImplementedError(f"{what} is not built for the affine-gap soft semi-global operator (free end gaps): the max-plus "
+                                  "member and its walk are HardAffineSemiGlobalDecoder(free=...), sampling exists for "
+                                  "AffineGlobalDecoder and AffineLocalDecoder only")
 
     def optimal_paths(self, *args, **kwargs):
         self._not_built("optimal_paths")
@@ -804,3 +809,157 @@ class AffineSemiGlobalDecoder(torch.nn.Module):
 
     def sample_alignments(self, *args, **kwargs):
         self._not_built("sample_alignments")
+
+
+# ---- the HARD affine-gap semi-global operator: optimal alignments with free end gaps (include/sdp.h: sdp_hard_affine_semiglobal_*;
+# DESIGN.md 3.32) ----
+class HardAffineSemiGlobalFunctionBackward(torch.autograd.Function):
+    """(E, GO, GX) of the walk along the optimal semi-global path.  Differentiable in nothing: the max-plus score is piecewise
+    linear, and this is the node at which a second differentiation stops."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, Et, state, ends, lens, ymx, want_E, want_GO, want_GX):
+        # (the three inputs are here for the graph alone: a second differentiation must arrive below)
+        E, GO, GX, _, _ = _engine.get_engine().hard_affine_semiglobal_walk(state, ends, tuple(theta.shape), lens, Et=Et, ymx=ymx,
+                                                                           want_E=want_E, want_GO=want_GO, want_GX=want_GX,
+                                                                           want_states=False)
+        return E, GO, GX
+
+    @staticmethod
+    def backward(ctx, ZE, ZGO, ZGX):
+        raise NotImplementedError("the hard affine-gap semi-global operator is first order only: its second order is not built (the "
+                                  "max-plus score is piecewise linear)")
+
+
+class HardAffineSemiGlobalFunction(torch.autograd.Function):
+    """Vt = the optimal affine-gap alignment's score under `free_ends` (bit 0: x, bit 1: y, as the sweep sees them); backward:
+    theta.grad = E, gap_open.grad = GO, gap_extend.grad = GX, the indicator matrices of the optimal path times Et -- one walk; only
+    the ones whose input needs a gradient.  Once differentiable.  ymx: the tensors are a transposed problem (ties as the problem
+    before it was transposed)."""
+
+    @staticmethod
+    def forward(ctx, theta, gap_open, gap_extend, lens=None, free_ends=FREE_Y, ymx=False):
+        Vt, state, ends = _engine.get_engine().hard_affine_semiglobal_forward(theta.detach(), gap_open.detach(), gap_extend.detach(),
+                                                                              free_ends, lens, ymx=ymx)
+        ctx.save_for_backward(theta, gap_open, gap_extend, state, ends)
+        ctx.lens, ctx.ymx = lens, ymx
+        return Vt
+
+    @staticmethod
+    def backward(ctx, Et):
+        theta, gap_open, gap_extend, state, ends = ctx.saved_tensors
+        want = ctx.needs_input_grad[:3]
+        if not any(want):
+            return None, None, None, None, None, None
+        E, GO, GX = HardAffineSemiGlobalFunctionBackward.apply(theta, gap_open, gap_extend, Et, state, ends, ctx.lens, ctx.ymx, *want)
+        return E, GO, GX, None, None, None
+
+
+class HardAffineSemiGlobalDecoder(torch.nn.Module):
+    """The OPTIMAL affine-gap alignment with FREE END GAPS, on a ROCm device in float32: the classical Gotoh semi-global aligner, the
+    hard-max (max-plus) member of AffineSemiGlobalDecoder's family (include/sdp.h: sdp_hard_affine_semiglobal_*).
+    The planes and the recurrences are AffineGlobalDecoder(operator="hardmax")'s, without a zero floor; what changes is where a path
+    may start and end:
+
+        free="y"     a path starts in any cell of row 1 and ends in any cell of row n: the whole of x aligned INSIDE a longer y (a
+                     domain against a full-length protein) -- the start and end columns say where;
+        free="x"     the same for rows: a path starts in any cell of column 1 and ends in any cell of column m;
+        free="both"  both: overlap alignment, two sequences that overlap at their ends.
+
+    A path starts with a match step into its start cell.  Vt is the largest plane value over the end cells, the end the FIRST
+    (cell, plane) that holds it -- cells row-major, planes x, m, y; equal values tie at any finite value, and the optimum may be
+    negative.  Adds and compares only: the bits of the plain fp32 loop over cells.  Any other `free` raises ValueError; for no
+    free end there is AffineGlobalDecoder(operator="hardmax").
+
+    forward(theta, gap_open, gap_extend, lengths=None) -> Vt (B,), the optimal score, differentiable ONCE with the subgradients of
+    perceptron or margin training: theta.grad = Et on the optimal path, gap_open.grad / gap_extend.grad = Et on its gap cells that
+    open / extend -- one walk, only the ones asked for are computed.  A second differentiation raises NotImplementedError.
+    decode(...) -> the path's indicator matrix (B, N, M); no graph.
+    score(...) is optimal_score(...).
+    optimal_paths / optimal_alignments / optimal_score(return_ends=): AffineGlobalDecoder's formats.  A list runs from the start
+    cell to the end cell; states[b, cap - 1] is (number of path cells, i, j of the START cell): where the query begins in the
+    target; ends is the 0-based end cell and its plane.
+    theta finite; gap_open and gap_extend finite or -inf (forbidden).  Where no path exists -- free="y", n > m and every gap
+    forbidden, or masks that cut every route -- Vt = -inf, the list is empty (counts 0, scratch row (0, -1, -1), ends (-1, -1, -1))
+    and the subgradients are +0.  lengths (B, 2): pair b is theta[b, :n_b, :m_b]; an empty pair has Vt = 0 and an empty list.
+    Problems wider than the column limit (2048) are swept transposed, with x and y of `free` swapped and the tie order flagged, and
+    (i, j), ends, the planes and the scratch row come back in the caller's coordinates: Vt, the end and the path do not depend on
+    the way a problem was swept.  Both sides above the limit raise ValueError.  Non-fp32 or non-tensor input: TypeError; a shape
+    mismatch: ValueError.
+    Not built: sampling and the second order of the semi-global family, float64, the `distributed` wrappers, `search_scores`,
+    `losses.decode_loss`, a one-score form, the reference's zero border."""
+
+    def __init__(self, free="y"):
+        super().__init__()
+        if free not in _FREE_ENDS:
+            raise ValueError(f"free must be 'y', 'x' or 'both', got {free!r} (for no free end there is "
+                             "AffineGlobalDecoder(operator='hardmax'))")
+        self.free = free
+        self.free_ends = _FREE_ENDS[free]
+        self.operator = "hardmax"
+        self.second_order = False
+
+    def _oriented(self, theta, gap_open, gap_extend, lengths):
+        """_oriented, and `free_ends` as the sweep sees it: x <-> y when the problem is swept transposed"""
+        theta, gap_open, gap_extend, lengths, transposed = _oriented(theta, gap_open, gap_extend, lengths)
+        return theta, gap_open, gap_extend, lengths, transposed, (_swapped(self.free_ends) if transposed else self.free_ends)
+
+    def forward(self, theta, gap_open, gap_extend, lengths=None):
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, transposed, free_ends = self._oriented(theta, gap_open, gap_extend, lengths)
+        return HardAffineSemiGlobalFunction.apply(theta, gap_open, gap_extend, lengths, free_ends, transposed)
+
+    def decode(self, theta, gap_open, gap_extend, lengths=None):
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, transposed, free_ends = self._oriented(theta, gap_open, gap_extend, lengths)
+        eng = _engine.get_engine()
+        with torch.no_grad():
+            _, state, ends = eng.hard_affine_semiglobal_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), free_ends, lengths,
+                                                                ymx=transposed)
+            E = eng.hard_affine_semiglobal_walk(state, ends, tuple(theta.shape), lengths, ymx=transposed, want_states=False,
+                                                Et=torch.ones((), dtype=torch.float32, device=theta.device))[0]
+        return E.transpose(1, 2) if transposed else E
+
+    def score(self, theta, gap_open, gap_extend, lengths=None):
+        return self.optimal_score(theta, gap_open, gap_extend, lengths)
+
+    def optimal_paths(self, theta, gap_open, gap_extend, lengths=None):
+        """The optimal affine-gap alignment with free end gaps of every pair -> (Vt (B,), states (B, cap, 3) int32, counts (B,)
+        int32), device tensors without an autograd graph, in the format of AffineGlobalDecoder.optimal_paths: pair b's list is
+        states[b, :counts[b]], rows (i, j, state), from the start cell to the end cell; empty (counts[b] = 0) for an empty pair
+        (Vt[b] = 0) and for a pair without a path (Vt[b] = -inf); states[b, cap - 1] is (number of path cells, i, j of the start
+        cell), (0, -1, -1) for an empty list.  One sweep that stores 6 bits per cell, one walk per pair."""
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, transposed, free_ends = self._oriented(theta, gap_open, gap_extend, lengths)
+        eng = _engine.get_engine()
+        with torch.no_grad():
+            Vt, state, ends = eng.hard_affine_semiglobal_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), free_ends, lengths,
+                                                                 ymx=transposed)
+            _, _, _, states, counts = eng.hard_affine_semiglobal_walk(state, ends, tuple(theta.shape), lengths, ymx=transposed, want_E=False)
+            if transposed:
+                scratch = states[:, -1]
+                states = states[..., [1, 0, 2]].contiguous()
+                states[:, -1] = scratch[:, [0, 2, 1]]     # (number of path cells, first i, first j): the count stays in front
+        return Vt, states, counts
+
+    def optimal_alignments(self, theta, gap_open, gap_extend, lengths=None):
+        """optimal_paths() as lists: (Vt, list of B lists of (i, j, state))."""
+        Vt, states, counts = self.optimal_paths(theta, gap_open, gap_extend, lengths)
+        states, counts = states.cpu().numpy(), counts.cpu().numpy()
+        return Vt, [[tuple(int(v) for v in row) for row in states[b, :counts[b]]] for b in range(len(counts))]
+
+    def optimal_score(self, theta, gap_open, gap_extend, lengths=None, return_ends=False):
+        """Vt (B,) of optimal_paths() through the value-only sweep: no pointers are stored, no graph.  return_ends: -> (Vt, ends
+        (B, 3) int32), the 0-based end cell and the plane each pair's optimal alignment ends in, (-1, -1, -1) where there is no
+        path."""
+        _validate(theta, gap_open, gap_extend)
+        theta, gap_open, gap_extend, lengths, transposed, free_ends = self._oriented(theta, gap_open, gap_extend, lengths)
+        with torch.no_grad():
+            Vt, ends = _engine.get_engine().hard_affine_semiglobal_forward_value(theta.detach(), gap_open.detach(), gap_extend.detach(),
+                                                                                 free_ends, lengths, ymx=transposed,
+                                                                                 want_ends=bool(return_ends))
+            if not return_ends:
+                return Vt
+            if transposed:   # (j, i) and the other gap plane; no end stays (-1, -1, -1)
+                ends = torch.stack([ends[:, 1], ends[:, 0], torch.where(ends[:, 2] < 0, ends[:, 2], 2 - ends[:, 2])], dim=1).contiguous()
+        return Vt, ends

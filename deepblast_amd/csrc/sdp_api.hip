@@ -655,7 +655,11 @@ int raise_hard_affine_limit(int device)
                                {(const void *)sdp_hard_affine_global_fwd_kernel, "hipFuncSetAttribute(sdp_hard_affine_global_fwd_kernel)"},
                                {(const void *)sdp_hard_affine_global_fwd_t_kernel, "hipFuncSetAttribute(sdp_hard_affine_global_fwd_t_kernel)"},
                                {(const void *)sdp_hard_affine_global_val_kernel, "hipFuncSetAttribute(sdp_hard_affine_global_val_kernel)"},
-                               {(const void *)sdp_hard_affine_global_val_t_kernel, "hipFuncSetAttribute(sdp_hard_affine_global_val_t_kernel)"}},
+                               {(const void *)sdp_hard_affine_global_val_t_kernel, "hipFuncSetAttribute(sdp_hard_affine_global_val_t_kernel)"},
+                               {(const void *)sdp_hard_affine_semiglobal_fwd_kernel, "hipFuncSetAttribute(sdp_hard_affine_semiglobal_fwd_kernel)"},
+                               {(const void *)sdp_hard_affine_semiglobal_fwd_t_kernel, "hipFuncSetAttribute(sdp_hard_affine_semiglobal_fwd_t_kernel)"},
+                               {(const void *)sdp_hard_affine_semiglobal_val_kernel, "hipFuncSetAttribute(sdp_hard_affine_semiglobal_val_kernel)"},
+                               {(const void *)sdp_hard_affine_semiglobal_val_t_kernel, "hipFuncSetAttribute(sdp_hard_affine_semiglobal_val_t_kernel)"}},
                               sdp_hard_affine::LDS_BUDGET);
 }
 
@@ -863,6 +867,11 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_hard_affine::ID_GLOBAL_FWD_T: return "sdp_hard_affine_global_fwd_t_kernel";
     case sdp_hard_affine::ID_GLOBAL_VAL: return "sdp_hard_affine_global_val_kernel";
     case sdp_hard_affine::ID_GLOBAL_VAL_T: return "sdp_hard_affine_global_val_t_kernel";
+    // its semi-global member's sweeps (free end gaps)
+    case sdp_hard_affine::ID_SEMIGLOBAL_FWD: return "sdp_hard_affine_semiglobal_fwd_kernel";
+    case sdp_hard_affine::ID_SEMIGLOBAL_FWD_T: return "sdp_hard_affine_semiglobal_fwd_t_kernel";
+    case sdp_hard_affine::ID_SEMIGLOBAL_VAL: return "sdp_hard_affine_semiglobal_val_kernel";
+    case sdp_hard_affine::ID_SEMIGLOBAL_VAL_T: return "sdp_hard_affine_semiglobal_val_t_kernel";
     // the affine-gap soft global operator (csrc/sdp_affine_global.hip)
     case sdp_affine_global::ID_FWD: return "sdp_affine_global_fwd_kernel";
     case sdp_affine_global::ID_VAL: return "sdp_affine_global_val_kernel";
@@ -1934,6 +1943,56 @@ int sdp_hard_affine_global_forward_value_f32(const float *theta, const float *ga
 // (the state format, `ends` and the stop at START are the local member's: one walk kernel serves both)
 int sdp_hard_affine_global_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, float *GO, float *GX, int32_t *states,
                                     int32_t *counts, int B, int N, int M, const int32_t *lens, int variant, int device, void *stream)
+{
+    return sdp_hard_affine_local_walk_f32(state, ends, Et, E, GO, GX, states, counts, B, N, M, lens, variant, device, stream);
+}
+
+// ---- the hard affine-gap semi-global operator (csrc/sdp_hard_affine.hip, SEMI builds): the global member with free end gaps ----
+size_t sdp_hard_affine_semiglobal_state_bytes(int B, int N, int M) { return sdp_hard_affine_local_state_bytes(B, N, M); }
+
+// free_ends: bit 0 = x, bit 1 = y (sdp_hard_affine::FREE_X, FREE_Y), any other bit is refused; 0 is the global member and launches its kernels, as the soft family does
+static int hard_affine_semiglobal_forward(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt,
+                                          int32_t *ends, int B, int N, int M, const int32_t *lens, int free_ends, int variant, int device,
+                                          void *stream, bool pointers)
+{
+    bool ymx;
+    int waves;
+    if (int rc = hard_affine_args(variant, B, N, M, ymx, waves)) return rc;
+    if (free_ends & ~sdp_hard_affine::FREE_ENDS_MASK)
+        return fail(SDP_E_VARIANT, "sdp_hard_affine_semiglobal_*: free_ends must be 0 .. 3 (bit 0: x, bit 1: y)");
+    if (free_ends == 0) return hard_affine_forward(theta, gap_open, gap_extend, state, Vt, ends, B, N, M, lens, variant, device, stream, pointers, true);
+    if (int rc = use_device(device)) return rc;
+    if (int rc = raise_hard_affine_limit(device)) return rc;
+    const int W = sdp_hard_affine::waves_for(N, M, waves);
+    auto kernel = pointers ? (ymx ? sdp_hard_affine_semiglobal_fwd_t_kernel : sdp_hard_affine_semiglobal_fwd_kernel)
+                           : (ymx ? sdp_hard_affine_semiglobal_val_t_kernel : sdp_hard_affine_semiglobal_val_kernel);
+    const char *name = pointers ? "sdp_hard_affine_semiglobal_fwd_kernel" : "sdp_hard_affine_semiglobal_val_kernel";
+    return strip_launch(kernel, name, B, W, sdp_hard_affine::sweep_lds_bytes(W, M), stream, theta, gap_open, gap_extend,
+                        static_cast<uint32_t *>(state), Vt, ends, lens, N, M, W, free_ends);
+}
+
+int sdp_hard_affine_semiglobal_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt,
+                                           int32_t *ends, int B, int N, int M, const int32_t *lens, int free_ends, int variant, int device,
+                                           void *stream)
+{
+    if (!theta || !gap_open || !gap_extend || !state || !Vt || !ends)
+        return fail(SDP_E_NULLPTR, "sdp_hard_affine_semiglobal_forward_f32: null pointer");
+    return hard_affine_semiglobal_forward(theta, gap_open, gap_extend, state, Vt, ends, B, N, M, lens, free_ends, variant, device, stream, true);
+}
+
+int sdp_hard_affine_semiglobal_forward_value_f32(const float *theta, const float *gap_open, const float *gap_extend, float *Vt, int32_t *ends,
+                                                 int B, int N, int M, const int32_t *lens, int free_ends, int variant, int device,
+                                                 void *stream)
+{
+    if (!theta || !gap_open || !gap_extend || !Vt) return fail(SDP_E_NULLPTR, "sdp_hard_affine_semiglobal_forward_value_f32: null pointer");
+    return hard_affine_semiglobal_forward(theta, gap_open, gap_extend, nullptr, Vt, ends, B, N, M, lens, free_ends, variant, device, stream,
+                                          false);
+}
+
+// (the local member's walk once more, so that the family is whole: it stops at START wherever that is)
+int sdp_hard_affine_semiglobal_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, float *GO, float *GX,
+                                        int32_t *states, int32_t *counts, int B, int N, int M, const int32_t *lens, int variant, int device,
+                                        void *stream)
 {
     return sdp_hard_affine_local_walk_f32(state, ends, Et, E, GO, GX, states, counts, B, N, M, lens, variant, device, stream);
 }

@@ -1,4 +1,4 @@
-// sdp_hard_affine.h -- the hard (max-plus) affine-gap kernel family, local and global (csrc/sdp_hard_affine.hip): launch geometry shared with the host side.
+// sdp_hard_affine.h -- the hard (max-plus) affine-gap kernel family, local, global and semi-global (csrc/sdp_hard_affine.hip): launch geometry shared with the host side.
 #ifndef SDP_HARD_AFFINE_H_
 #define SDP_HARD_AFFINE_H_
 
@@ -14,6 +14,9 @@ constexpr int HALF = 16;         // steps of the sweeps' input prefetch: three i
 constexpr int PTR_STEPS = 16;    // steps whose 2-bit pointers fill one 32-bit word of a lane
 constexpr int PLANES = 3;        // x, m, y = 0, 1, 2: the step that entered the cell
 constexpr int START = 3;         // pointer code of plane m alone: the alignment begins at this cell
+constexpr int FREE_X = 1;        // `free_ends` of the semi-global member: rows may hang over (start in column 1, end in column m)
+constexpr int FREE_Y = 2;        // columns may hang over (start in row 1, end in row n)
+constexpr int FREE_ENDS_MASK = 3;
 constexpr int MAX_WAVES = 8;     // waves (strips in flight) of a workgroup
 constexpr int KEY = 256;         // progress word of a wave: strip * KEY + chunks done (chunks of a strip <= 66 < KEY)
 constexpr int LDS_BUDGET = 160 * 1024;   // all of a CU's LDS: every kernel of the family has its dynamic-LDS attribute raised
@@ -45,6 +48,8 @@ __host__ __device__ inline size_t pair_words(int N, int M) { return (size_t)stri
 enum { ID_FWD = 170, ID_FWD_T = 171, ID_VAL = 172, ID_VAL_T = 173, ID_WALK = 174 };
 // the global member's sweeps (184 and 189 answer NULL); its walk is ID_WALK
 enum { ID_GLOBAL_FWD = 185, ID_GLOBAL_FWD_T = 186, ID_GLOBAL_VAL = 187, ID_GLOBAL_VAL_T = 188 };
+// the semi-global member's sweeps (204 and 209 answer NULL); its walk is ID_WALK
+enum { ID_SEMIGLOBAL_FWD = 205, ID_SEMIGLOBAL_FWD_T = 206, ID_SEMIGLOBAL_VAL = 207, ID_SEMIGLOBAL_VAL_T = 208 };
 
 }  // namespace sdp_hard_affine
 
@@ -65,6 +70,14 @@ __global__ void sdp_hard_affine_global_val_kernel(const float *theta, const floa
                                                   const int *lens, int N, int M, int waves);
 __global__ void sdp_hard_affine_global_val_t_kernel(const float *theta, const float *O, const float *X, uint32_t *state, float *Vt, int *ends,
                                                     const int *lens, int N, int M, int waves);
+__global__ void sdp_hard_affine_semiglobal_fwd_kernel(const float *theta, const float *O, const float *X, uint32_t *state, float *Vt,
+                                                      int *ends, const int *lens, int N, int M, int waves, int free_ends);
+__global__ void sdp_hard_affine_semiglobal_fwd_t_kernel(const float *theta, const float *O, const float *X, uint32_t *state, float *Vt,
+                                                        int *ends, const int *lens, int N, int M, int waves, int free_ends);
+__global__ void sdp_hard_affine_semiglobal_val_kernel(const float *theta, const float *O, const float *X, uint32_t *state, float *Vt,
+                                                      int *ends, const int *lens, int N, int M, int waves, int free_ends);
+__global__ void sdp_hard_affine_semiglobal_val_t_kernel(const float *theta, const float *O, const float *X, uint32_t *state, float *Vt,
+                                                        int *ends, const int *lens, int N, int M, int waves, int free_ends);
 __global__ void sdp_hard_affine_local_walk_kernel(const uint32_t *state, const int *ends, const float *Et, float *E, float *GO, float *GX,
                                                   int *states, int *counts, const int *lens, int N, int M, int cap, int ymx);
 }

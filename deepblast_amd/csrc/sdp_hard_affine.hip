@@ -34,6 +34,12 @@
 // at cell (1,1) alone and no zero floor, a path from (1,1) to (n,m), Vt the first maximum of the last cell's three planes, which
 // the lane of row n captures where its column is m -- there is no running best and no join.  Four more sweep kernels; the state
 // format, ends and the stop at START are the same, so the walk above serves both members.
+//
+// The SEMI-GLOBAL member (include/sdp.h: sdp_hard_affine_semiglobal_*) is the third mode of the template: the global
+// member's recurrences (no zero floor) with FREE END GAPS -- START in cell (1,1), in every cell of row 1 under FREE_Y and of column 1
+// under FREE_X, and Vt the first maximum over the END cells alone: (n,m), row n under FREE_Y, column m under FREE_X.  The running
+// best and its join are the local member's, started from -inf and fed by the end cells only; equal values tie at any finite value.
+// Four more sweep kernels with one more argument, `free_ends`; the state, ends and the walk are again the same.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -93,23 +99,29 @@ __device__ __forceinline__ float first_max(float c0, float c1, float c2, uint32_
 
 // is the candidate (v1, r1, c1) the better end than (v0, r0, c0)?  Larger value first; among equal positive values the cell the
 // ORIGINAL problem's row-major scan visits first -- under YMX (a transposed problem) that is column-major in these coordinates.
-// The two are never the same cell, and a value of 0 is never an end.
-template <bool YMX>
+// The two are never the same cell, and a value of 0 is never an end.  ANY (the semi-global member): equal values tie at every finite
+// value, negative ones included, and only -inf is never an end.
+template <bool YMX, bool ANY = false>
 __device__ __forceinline__ bool better_end(float v1, int r1, int c1, float v0, int r0, int c0)
 {
     if (v1 > v0) return true;
-    if (!(v1 == v0) || !(v1 > 0.f)) return false;
+    if (!(v1 == v0) || !(v1 > (ANY ? -__builtin_inff() : 0.f))) return false;
     return YMX ? (c1 < c0 || (c1 == c0 && r1 < r0)) : (r1 < r0 || (r1 == r0 && c1 < c0));
 }
 
 // PTR: write the pointers (else: the value-only sweep); YMX: every scan y, m, x and the first maximum over cells column-major.
 // GLOBAL: the Gotoh form of Needleman-Wunsch -- START at cell (0, 0) alone and no zero floor, no running best:
 // the lane of row n - 1 keeps its three plane values at column m - 1, and Vt is their first maximum in scan order.
+// SEMI: the global member with free end gaps (free_ends: bit 0 FREE_X, bit 1 FREE_Y, read by this mode alone) --
+// START in cell (0, 0), in row 0 under FREE_Y and in column 0 under FREE_X, no zero floor; the running best of the local member,
+// from -inf, over the end cells only: cell (n - 1, m - 1), row n - 1 under FREE_Y, column m - 1 under FREE_X.
 // ends may be NULL.
-template <bool PTR, bool YMX, bool GLOBAL>
+enum { LOCAL = 0, GLOBAL_MODE = 1, SEMI_MODE = 2 };
+template <bool PTR, bool YMX, int MODE>
 __device__ __forceinline__ void hard_affine_forward(const float *theta, const float *O, const float *X, uint32_t *state, float *Vt, int *ends,
-                                                    const int *lens, int N, int M, int W)
+                                                    const int *lens, int N, int M, int W, int free_ends = 0)
 {
+    constexpr bool GLOBAL = MODE == GLOBAL_MODE, SEMI = MODE == SEMI_MODE;
     extern __shared__ float smem[];
     const int Mp = row_pitch(M);
     float *bnd = smem;                                               // [W][PLANES][Mp]: bottom row of strip s in bnd[s % W]
@@ -140,14 +152,16 @@ __device__ __forceinline__ void hard_affine_forward(const float *theta, const fl
     float dx = NINF, dm = NINF, dy = NINF;   // none above: what arrived from the row above one step before
     // the best plane value of the row this lane is in and where: 4 * column + plane (the first that holds it: strict '>' along
     // increasing columns -- a row's cells are in the same order row-major and column-major -- and along the planes of a cell in scan order) ...
-    float rv = 0.f;
+    // (SEMI: of the row's END cells, from -inf: a negative optimum is an optimum)
+    float rv = SEMI ? NINF : 0.f;
     int rcode = -4;
     // ... and of all the rows this lane has finished
-    float bv = 0.f;
+    float bv = SEMI ? NINF : 0.f;
     int brw = -1, bcode = -4;
     // GLOBAL: the three planes of cell (n - 1, m - 1), kept by lane (n - 1) % 64 of the wave that sweeps the pair's last strip
     float ex = NINF, em = NINF, ey = NINF;
     const int endlane = (n - 1) & (STRIP - 1);
+    const bool free_x = SEMI && (free_ends & FREE_X), free_y = SEMI && (free_ends & FREE_Y);
 
     for (int tick = 0;; ++tick) {
         __syncthreads();
@@ -172,6 +186,14 @@ __device__ __forceinline__ void hard_affine_forward(const float *theta, const fl
             const int tlim = (row1 <= n ? m : 0) - colb;
             // GLOBAL: the step of this chunk at which this lane is at the pair's last cell (in no chunk but one, in no lane but one)
             const int tend = (s == S - 1 && lane == endlane) ? m - 1 - colb : -1;
+            // SEMI: row 0 starts in every column under FREE_Y, else in column 0; every other row in column 0 under FREE_X -- the step
+            // of this chunk at which this lane is at column 0 where that is a start cell (-1: none); and the first step whose cell is
+            // an END cell: row n - 1 ends in every column under FREE_Y, else in column m - 1; every other row in column m - 1 under
+            // FREE_X, else nowhere (the pair's n and m: under lengths the end row and column are the pair's)
+            const bool row0 = s == 0 && lane == 0;
+            const bool startrow = row0 && free_y;
+            const int tstart = (row0 || free_x) ? -colb : -1;
+            const int tfirst = (row1 == n && free_y) ? 0 : ((row1 == n || free_x) ? m - 1 - colb : CHUNK);
             uint32_t bits[PLANES][CHUNK / PTR_STEPS] = {{0u, 0u}, {0u, 0u}, {0u, 0u}};
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -190,7 +212,8 @@ __device__ __forceinline__ void hard_affine_forward(const float *theta, const fl
                     uint32_t km, kx, ky;
                     float mbest = first_max<YMX>(dx, dm, dy, km);
                     // (GLOBAL: the path starts at cell (0, 0) and nowhere else, and nothing is floored)
-                    const bool cont = GLOBAL ? !(s == 0 && lane == 0 && col == 0) : mbest > 0.f;
+                    // (SEMI: at the start cells of the free edges, and nothing is floored either)
+                    const bool cont = SEMI ? !(startrow || t == tstart) : GLOBAL ? !(s == 0 && lane == 0 && col == 0) : mbest > 0.f;
                     mbest = cont ? mbest : 0.f;
                     km = cont ? km : (uint32_t)START;
                     float nvm = th[tt] + mbest;
@@ -214,7 +237,7 @@ __device__ __forceinline__ void hard_affine_forward(const float *theta, const fl
                         const bool last = t == tend;
                         ex = last ? nvx : ex, em = last ? nvm : em, ey = last ? nvy : ey;
                     } else {   // the cell's planes join the row's best in scan order (a lane that has not started holds -inf: never a best)
-                        const bool cell = t < tlim;
+                        const bool cell = SEMI ? (t < tlim && t >= tfirst) : t < tlim;
                         const int code = 4 * col;
                         const float p0 = YMX ? nvy : nvx, p2 = YMX ? nvx : nvy;
                         const bool t0 = cell && p0 > rv;
@@ -249,8 +272,8 @@ __device__ __forceinline__ void hard_affine_forward(const float *theta, const fl
                     for (int p = 0; p < PLANES; ++p) dst[(q * PLANES + p) * STRIP] = bits[p][q];
             }
             if (ns != s) {   // the row is finished: it joins the lane's best, and the next row starts from nothing
-                if (!GLOBAL && better_end<YMX>(rv, row1 - 1, rcode >> 2, bv, brw, bcode >> 2)) bv = rv, brw = row1 - 1, bcode = rcode;
-                rv = 0.f, rcode = -4;
+                if (!GLOBAL && better_end<YMX, SEMI>(rv, row1 - 1, rcode >> 2, bv, brw, bcode >> 2)) bv = rv, brw = row1 - 1, bcode = rcode;
+                rv = SEMI ? NINF : 0.f, rcode = -4;
                 vx = NINF, vm = NINF, vy = NINF, dx = NINF, dm = NINF, dy = NINF;
             }
             s = ns, c = nc;
@@ -273,7 +296,7 @@ __device__ __forceinline__ void hard_affine_forward(const float *theta, const fl
     for (int off = 32; off > 0; off >>= 1) {
         const float ov = __shfl_xor(bv, off, 64);
         const int orw = __shfl_xor(brw, off, 64), ocode = __shfl_xor(bcode, off, 64);
-        if (better_end<YMX>(ov, orw, ocode >> 2, bv, brw, bcode >> 2)) bv = ov, brw = orw, bcode = ocode;
+        if (better_end<YMX, SEMI>(ov, orw, ocode >> 2, bv, brw, bcode >> 2)) bv = ov, brw = orw, bcode = ocode;
     }
     int *red = reinterpret_cast<int *>(smem);   // [MAX_WAVES][3] <= the 195 floats of the narrowest ring
     if (lane == 0) red[3 * w] = __float_as_int(bv), red[3 * w + 1] = brw, red[3 * w + 2] = bcode;
@@ -282,7 +305,7 @@ __device__ __forceinline__ void hard_affine_forward(const float *theta, const fl
         for (int q = 1; q < W; ++q) {
             const float ov = __int_as_float(red[3 * q]);
             const int orw = red[3 * q + 1], ocode = red[3 * q + 2];
-            if (better_end<YMX>(ov, orw, ocode >> 2, bv, brw, bcode >> 2)) bv = ov, brw = orw, bcode = ocode;
+            if (better_end<YMX, SEMI>(ov, orw, ocode >> 2, bv, brw, bcode >> 2)) bv = ov, brw = orw, bcode = ocode;
         }
         Vt[b] = bv;
         if (ends) ends[3 * b] = brw, ends[3 * b + 1] = brw < 0 ? -1 : bcode >> 2, ends[3 * b + 2] = brw < 0 ? -1 : bcode & 3;
@@ -295,25 +318,25 @@ extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_local_fwd_kern
                                                                                    uint32_t *state, float *Vt, int *ends, const int *lens,
                                                                                    int N, int M, int waves)
 {
-    hard_affine_forward<true, false, false>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+    hard_affine_forward<true, false, LOCAL>(theta, O, X, state, Vt, ends, lens, N, M, waves);
 }
 extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_local_fwd_t_kernel(const float *theta, const float *O, const float *X,
                                                                                      uint32_t *state, float *Vt, int *ends, const int *lens,
                                                                                      int N, int M, int waves)
 {
-    hard_affine_forward<true, true, false>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+    hard_affine_forward<true, true, LOCAL>(theta, O, X, state, Vt, ends, lens, N, M, waves);
 }
 extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_local_val_kernel(const float *theta, const float *O, const float *X,
                                                                                    uint32_t *state, float *Vt, int *ends, const int *lens,
                                                                                    int N, int M, int waves)
 {
-    hard_affine_forward<false, false, false>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+    hard_affine_forward<false, false, LOCAL>(theta, O, X, state, Vt, ends, lens, N, M, waves);
 }
 extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_local_val_t_kernel(const float *theta, const float *O, const float *X,
                                                                                      uint32_t *state, float *Vt, int *ends, const int *lens,
                                                                                      int N, int M, int waves)
 {
-    hard_affine_forward<false, true, false>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+    hard_affine_forward<false, true, LOCAL>(theta, O, X, state, Vt, ends, lens, N, M, waves);
 }
 
 // the global member's four sweeps: the same arguments, the same state, the same walk
@@ -321,25 +344,52 @@ extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_global_fwd_ker
                                                                                     uint32_t *state, float *Vt, int *ends, const int *lens,
                                                                                     int N, int M, int waves)
 {
-    hard_affine_forward<true, false, true>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+    hard_affine_forward<true, false, GLOBAL_MODE>(theta, O, X, state, Vt, ends, lens, N, M, waves);
 }
 extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_global_fwd_t_kernel(const float *theta, const float *O, const float *X,
                                                                                       uint32_t *state, float *Vt, int *ends, const int *lens,
                                                                                       int N, int M, int waves)
 {
-    hard_affine_forward<true, true, true>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+    hard_affine_forward<true, true, GLOBAL_MODE>(theta, O, X, state, Vt, ends, lens, N, M, waves);
 }
 extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_global_val_kernel(const float *theta, const float *O, const float *X,
                                                                                     uint32_t *state, float *Vt, int *ends, const int *lens,
                                                                                     int N, int M, int waves)
 {
-    hard_affine_forward<false, false, true>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+    hard_affine_forward<false, false, GLOBAL_MODE>(theta, O, X, state, Vt, ends, lens, N, M, waves);
 }
 extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_global_val_t_kernel(const float *theta, const float *O, const float *X,
                                                                                       uint32_t *state, float *Vt, int *ends, const int *lens,
                                                                                       int N, int M, int waves)
 {
-    hard_affine_forward<false, true, true>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+    hard_affine_forward<false, true, GLOBAL_MODE>(theta, O, X, state, Vt, ends, lens, N, M, waves);
+}
+
+// the semi-global member's four sweeps: one more argument, free_ends (bit 0 FREE_X, bit 1 FREE_Y); the same
+// state, the same walk
+extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_semiglobal_fwd_kernel(const float *theta, const float *O, const float *X, uint32_t *state,
+                                                                                        float *Vt, int *ends, const int *lens, int N, int M, int waves,
+                                                                                        int free_ends)
+{
+    hard_affine_forward<true, false, SEMI_MODE>(theta, O, X, state, Vt, ends, lens, N, M, waves, free_ends);
+}
+extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_semiglobal_fwd_t_kernel(const float *theta, const float *O, const float *X, uint32_t *state,
+                                                                                          float *Vt, int *ends, const int *lens, int N, int M, int waves,
+                                                                                          int free_ends)
+{
+    hard_affine_forward<true, true, SEMI_MODE>(theta, O, X, state, Vt, ends, lens, N, M, waves, free_ends);
+}
+extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_semiglobal_val_kernel(const float *theta, const float *O, const float *X, uint32_t *state,
+                                                                                        float *Vt, int *ends, const int *lens, int N, int M, int waves,
+                                                                                        int free_ends)
+{
+    hard_affine_forward<false, false, SEMI_MODE>(theta, O, X, state, Vt, ends, lens, N, M, waves, free_ends);
+}
+extern "C" __global__ void __launch_bounds__(512) sdp_hard_affine_semiglobal_val_t_kernel(const float *theta, const float *O, const float *X, uint32_t *state,
+                                                                                          float *Vt, int *ends, const int *lens, int N, int M, int waves,
+                                                                                          int free_ends)
+{
+    hard_affine_forward<false, true, SEMI_MODE>(theta, O, X, state, Vt, ends, lens, N, M, waves, free_ends);
 }
 
 namespace {

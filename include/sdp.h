@@ -856,6 +856,50 @@ int sdp_hard_affine_global_forward_value_f32(const float *theta, const float *ga
 int sdp_hard_affine_global_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, float *GO, float *GX, int32_t *states,
                                     int32_t *counts, int B, int N, int M, const int32_t *lens, int variant, int device, void *stream);
 
+/* The HARD AFFINE-GAP SEMI-GLOBAL operator (csrc/sdp_hard_affine.hip): the operator above with FREE END GAPS -- the
+ * classical Gotoh alignment with free end gaps, the max-plus member of sdp_affine_semiglobal_* below: where a whole query sits inside
+ * a longer target, or where two sequences overlap at their ends.  (Added after SDP_VERSION 106 without a version change: look the
+ * symbols up.  sdp_kernel_name answers 205 .. 208 for its four sweeps; 204 and 209 answer NULL; its walk is kernel 174.)  Adds and
+ * compares only: the results are the BITS of this loop.  O, X, the x and y planes, the rounding, the -inf border and "where all
+ * candidates are -inf the pointer is the first of the scan" are the global operator's; `free_ends` has the soft operator's bits,
+ * bit 0 (1) = x: rows may hang over, bit 1 (2) = y: columns may hang over:
+ *
+ *     START cells: (1,1) always; (1,j) for every j <= m under y; (i,1) for every i <= n under x
+ *     END cells:   (n,m) always; (n,j) for every j <= m under y; (i,m) for every i <= n under x
+ *     for i in 1..n, j in 1..m:
+ *         m plane: in a START cell H[i,j,m] = t + (+0), P = 3 (START), unconditionally (its diagonal predecessor lies on the -inf
+ *                  border: START is the only candidate);  elsewhere  c = H[i-1,j-1,(x,m,y)], k = FIRST maximum (strict '>'),
+ *                  H[i,j,m] = t + c[k], P[i,j,m] = k
+ *         x plane, y plane: as in the local operator
+ *     Vt  = the largest H over the END cells and their three planes;  end = the FIRST (cell, plane) that holds it -- cells in
+ *           row-major order, planes x, m, y within a cell -- if Vt > -inf, else none
+ *     path: as in the local operator, from end; it stops at the START it meets
+ *
+ * There is NO zero floor, anywhere: the optimum may be negative, and equal values tie at ANY finite value.  A pair without a path
+ * (every gap forbidden under free_ends = 2 with n > m, or -inf masks that cut every route): Vt = -inf, ends = (-1, -1, -1), an empty
+ * list with counts 0 and scratch row (0, -1, -1), E, GO and GX +0.  An empty pair (n < 1 or m < 1): Vt = +0, no end, an empty list.
+ * The scratch row of a list carries the START cell: where the query begins in the target.
+ * SDP_HARD_TIES_YMX: the problem was handed over TRANSPOSED, with the two bits of free_ends SWAPPED by the caller; every plane scan
+ * runs y, m, x, the end cells are scanned column-major in the coordinates swept, and the walk renames the gap planes -- so Vt, the
+ * end and the path do not depend on which way the problem was swept.  free_ends = 0 is legal and is the global operator: the bits
+ * (and the kernels) of sdp_hard_affine_global_*.
+ *   free_ends  bit 0 = x, bit 1 = y; any other bit: SDP_E_VARIANT.
+ *   variant    SDP_HARD_TIES_YMX | SDP_WAVES(w) only.
+ * state, ends, the walk's outputs, null pointers, the limits and the error codes are the global operator's;
+ * sdp_hard_affine_semiglobal_state_bytes is sdp_hard_affine_local_state_bytes and sdp_hard_affine_semiglobal_walk_f32 is
+ * sdp_hard_affine_local_walk_f32: they are here so that the family is whole.  ends may be NULL in the value entry.  NOT built:
+ * sampling and the second order of the semi-global family, float64, a one-score form, the reference's zero border. */
+size_t sdp_hard_affine_semiglobal_state_bytes(int B, int N, int M);
+int sdp_hard_affine_semiglobal_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt,
+                                           int32_t *ends, int B, int N, int M, const int32_t *lens, int free_ends, int variant, int device,
+                                           void *stream);
+int sdp_hard_affine_semiglobal_forward_value_f32(const float *theta, const float *gap_open, const float *gap_extend, float *Vt, int32_t *ends,
+                                                 int B, int N, int M, const int32_t *lens, int free_ends, int variant, int device,
+                                                 void *stream);
+int sdp_hard_affine_semiglobal_walk_f32(const void *state, const int32_t *ends, const float *Et, float *E, float *GO, float *GX,
+                                        int32_t *states, int32_t *counts, int B, int N, int M, const int32_t *lens, int variant, int device,
+                                        void *stream);
+
 /* The AFFINE-GAP SOFT GLOBAL operator (csrc/sdp_affine_global.hip): a differentiable Needleman-Wunsch with opening a
  * gap and extending it priced separately -- the Gotoh global form.  (Added after SDP_VERSION 106 without a version change: look the
  * symbols up.)  Notation of the affine-gap soft local operator above: (n, m) = lens[b] clamped or (N, M), cells 1-based, theta,
@@ -927,8 +971,8 @@ int sdp_affine_global_backward_f32(const void *state, const float *Et, float *E,
  *              the forward entry, read by the backward entry with the same B, N, M, lens and free_ends.
  *   free_ends  bit 0 = x, bit 1 = y; any other bit: SDP_E_VARIANT.
  *   flags      this family defines none: any bit is refused (SDP_E_VARIANT).
- * Launch geometry, LDS, argument checks, codes and limits are those of sdp_affine_global_*.  NOT built: the hard-max member and its
- * walk, sampling, the second order, float64, a one-score form, the reference's zero border. */
+ * Launch geometry, LDS, argument checks, codes and limits are those of sdp_affine_global_*.  The hard-max member and its
+ * walk are sdp_hard_affine_semiglobal_* above.  NOT built: sampling, the second order, float64, a one-score form, the reference's zero border. */
 size_t sdp_affine_semiglobal_state_bytes(int B, int N, int M);
 int sdp_affine_semiglobal_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int B,
                                       int N, int M, const int32_t *lens, int free_ends, int flags, int device, void *stream);
