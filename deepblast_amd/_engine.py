@@ -933,6 +933,53 @@ class HipEngine:
         self.call("sdp_affine_semiglobal_backward_f32", AFFINE_SEMIGLOBAL_KERNELS[202], dev, state, Et, E, GO, GX, B, N, M, lens, free_ends, 0)
         return E, GO, GX
 
+    # ---- alignments sampled from its posterior (include/sdp.h: sdp_affine_semiglobal_end_table_f32, .._sample_paths_f32) ----
+    def affine_semiglobal_end_table(self, state, shape, free_ends, lens=None):
+        """-> ecdf (B, N + M) float32: the running sums of the end cells' weights of every pair, on the `state` of
+        affine_semiglobal_forward under the same free_ends and lens -- candidate e < n_b is cell (e, m_b - 1), e >= n_b cell
+        (n_b - 1, e - n_b); a cell that is no end cell under free_ends weighs exactly 0.  Entries from n_b + m_b - 1 on are not
+        written.  One table serves any number of affine_semiglobal_sample_paths launches (a K split by sample0)."""
+        dev = self.device_of(state)
+        free_ends = self._free_ends(free_ends)
+        B, N, M = shape
+        check_args(state, torch.float32, None, True, state=state)
+        lens = self._lens(lens, B, state.device)
+        ecdf = torch.empty((B, N + M), dtype=torch.float32, device=state.device)
+        self.call("sdp_affine_semiglobal_end_table_f32", AFFINE_SEMIGLOBAL_SAMPLE_KERNELS[211], dev, state, ecdf, B, N, M, lens,
+                  free_ends, 0)
+        return ecdf
+
+    def affine_semiglobal_sample_paths(self, state, ecdf, shape, free_ends, K, lens=None, seed=0, sample0=0, want_states=True,
+                                       want_visits=False, want_opens=False, want_extends=False, want_ends=False):
+        """K semi-global alignments per pair drawn from the posterior, on the `state` of affine_semiglobal_forward and the `ecdf` of
+        affine_semiglobal_end_table (the same free_ends and lens) -> (states (B,K,cap,3) int32 or None, counts (B,K) int32 or None,
+        visits, opens, extends (B,N,M) int32 or None, ends (B,K,3) int32 or None), in the formats of affine_global_sample_paths:
+        the list of sample (b, k) -- sample number sample0 + k of pair b under `seed` whatever K is -- runs from a start cell to
+        the drawn end cell, rows (i, j, plane), RIGHT-aligned in states[b, k]; row cap-1 holds (number of path cells, i, j of the
+        first one), (0, -1, -1) for an empty sample -- an empty pair, or a pair without a path.  ends: (i, j, plane) of the end
+        cell, (-1, -1, -1) for an empty sample."""
+        dev = self.device_of(state)
+        free_ends = self._free_ends(free_ends)
+        B, N, M = shape
+        if not (want_states or want_visits or want_opens or want_extends or want_ends):
+            raise ValueError("affine_semiglobal_sample_paths: nothing asked for (want_states, want_visits, want_opens, want_extends, "
+                             "want_ends)")
+        check_args(state, torch.float32, None, True, state=state)
+        check_args(state, torch.float32, (B, N + M), True, ecdf=ecdf)
+        lens = self._lens(lens, B, state.device)
+        states = counts = ends = None
+        if want_states:
+            cap = self.lib.sdp_traceback_capacity(N, M)
+            states = torch.empty((B, int(K), cap, 3), dtype=torch.int32, device=state.device)
+            counts = torch.empty((B, int(K)), dtype=torch.int32, device=state.device)
+        visits, opens, extends = (torch.zeros((B, N, M), dtype=torch.int32, device=state.device) if want else None
+                                  for want in (want_visits, want_opens, want_extends))
+        if want_ends:
+            ends = torch.empty((B, int(K), 3), dtype=torch.int32, device=state.device)
+        self.call("sdp_affine_semiglobal_sample_paths_f32", AFFINE_SEMIGLOBAL_SAMPLE_KERNELS[212], dev, state, ecdf, states, counts,
+                  visits, opens, extends, ends, B, N, M, int(K), int(sample0), int(seed) & 0xffffffffffffffff, lens, free_ends, 0)
+        return states, counts, visits, opens, extends, ends
+
     def affine_global_adjoint_forward(self, state, ZE, ZGO, ZGX, shape, lens=None, state_d_out=None):
         """The adjoint forward sweep over the records of affine_global_forward -> (Vtd (B,), state_d): ZE, ZGO, ZGX (B,N,M) the
         cotangents of E, GO and GX, each may be None (zeros) but not all three; state_d the dot records (opaque float32 tensor of
@@ -1222,6 +1269,8 @@ AFFINE_GLOBAL_KERNELS = {180: "sdp_affine_global_fwd_kernel", 181: "sdp_affine_g
 # of its free-end-gap member (the same header; csrc/sdp_affine_semiglobal.hip)
 AFFINE_SEMIGLOBAL_KERNELS = {200: "sdp_affine_semiglobal_fwd_kernel", 201: "sdp_affine_semiglobal_val_kernel",
                              202: "sdp_affine_semiglobal_bwd_kernel"}
+# of the kernels that sample from the semi-global posterior (csrc/sdp_affine_semiglobal_sample.h)
+AFFINE_SEMIGLOBAL_SAMPLE_KERNELS = {211: "sdp_affine_semiglobal_end_table_kernel", 212: "sdp_affine_semiglobal_sample_kernel"}
 # of its adjoint pair (the same header)
 AFFINE_GLOBAL_ADJOINT_KERNELS ={193: "sdp_affine_global_adj_fwd_kernel", 194: "sdp_affine_global_adj_bwd_kernel"}
 # and of the kernel that samples from its posterior (csrc/sdp_affine_global_sample.h)

@@ -186,6 +186,10 @@ SIGNATURES = {
                                                                _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "sdp_affine_semiglobal_backward_f32": (ctypes.c_int, [ctypes.c_void_p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int,
                                                           ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_affine_semiglobal_end_table_f32": (ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32p,
+                                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "sdp_affine_semiglobal_sample_paths_f32": (ctypes.c_int, [ctypes.c_void_p, _c_f32p] + [_c_i32p] * 6 + [ctypes.c_int] * 5 +
+                                               [ctypes.c_uint64, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "sdp_affine_global_adjoint_state_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "sdp_affine_global_adjoint_forward_f32": (ctypes.c_int, [ctypes.c_void_p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _c_f32p,
                                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int,

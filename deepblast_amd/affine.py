@@ -41,7 +41,9 @@ The SEMI-GLOBAL form -- the global operator with free end gaps: a whole query in
 at their ends -- is AffineSemiGlobalDecoder(free="y" | "x" | "both") at the end of this file (include/sdp.h:
 sdp_affine_semiglobal_*): softmax and first order only.  Its hard (max-plus) member -- the optimal alignment with
 free end gaps, its score, end, path and subgradients -- is a class of its own, HardAffineSemiGlobalDecoder(free=...), below it
-(include/sdp.h: sdp_hard_affine_semiglobal_*).
+(include/sdp.h: sdp_hard_affine_semiglobal_*).  Sampling from the semi-global posterior is a class of its own too,
+AffineSemiGlobalSampler(free=...), at the end of this file (include/sdp.h: sdp_affine_semiglobal_end_table_f32,
+sdp_affine_semiglobal_sample_paths_f32); the second order of the semi-global operator is not built.
 """
 import torch
 
@@ -742,8 +744,8 @@ class AffineSemiGlobalDecoder(torch.nn.Module):
     the results come back in the caller's coordinates.
     Not built INTO THIS CLASS, each raises NotImplementedError rather than answer for the closed border: operator="hardmax",
     second_order=True, optimal_paths / optimal_alignments / optimal_score, sample_paths / sample_alignments.  The hard-max member
-    and the optimal_* methods are HardAffineSemiGlobalDecoder(free=...) below; sampling and the second order exist for no
-    semi-global class.  Out of scope as well: float64, the
+    and the optimal_* methods are HardAffineSemiGlobalDecoder(free=...) below, sample_paths / sample_alignments are
+    AffineSemiGlobalSampler(free=...) below it; the second order exists for no semi-global class.  Out of scope as well: float64, the
     `distributed` wrappers, `search_scores`, `losses.decode_loss`, a one-score form, and the reference's zero border."""
 
     def __init__(self, free="y", operator="softmax", second_order=False):
@@ -792,8 +794,8 @@ class AffineSemiGlobalDecoder(torch.nn.Module):
 
     def _not_built(self, what):
         raise NotImplementedError(f"{what} is not built for the affine-gap soft semi-global operator (free end gaps): the max-plus "
-                                  "member and its walk are HardAffineSemiGlobalDecoder(free=...), sampling exists for "
-                                  "AffineGlobalDecoder and AffineLocalDecoder only")
+                                  "member and its walk are HardAffineSemiGlobalDecoder(free=...), sampling from the semi-global "
+                                  "posterior is AffineSemiGlobalSampler(free=...)")
 
     def optimal_paths(self, *args, **kwargs):
         self._not_built("optimal_paths")
@@ -886,7 +888,8 @@ class HardAffineSemiGlobalDecoder(torch.nn.Module):
     (i, j), ends, the planes and the scratch row come back in the caller's coordinates: Vt, the end and the path do not depend on
     the way a problem was swept.  Both sides above the limit raise ValueError.  Non-fp32 or non-tensor input: TypeError; a shape
     mismatch: ValueError.
-    Not built: sampling and the second order of the semi-global family, float64, the `distributed` wrappers, `search_scores`,
+    Sampling from the semi-global posterior is AffineSemiGlobalSampler(free=...).  Not built: the second order of the semi-global
+    family, float64, the `distributed` wrappers, `search_scores`,
     `losses.decode_loss`, a one-score form, the reference's zero border."""
 
     def __init__(self, free="y"):
@@ -963,3 +966,76 @@ class HardAffineSemiGlobalDecoder(torch.nn.Module):
             if transposed:   # (j, i) and the other gap plane; no end stays (-1, -1, -1)
                 ends = torch.stack([ends[:, 1], ends[:, 0], torch.where(ends[:, 2] < 0, ends[:, 2], 2 - ends[:, 2])], dim=1).contiguous()
         return Vt, ends
+
+
+# ---- alignments SAMPLED from the affine-gap soft semi-global posterior (include/sdp.h: sdp_affine_semiglobal_end_table_f32,
+# sdp_affine_semiglobal_sample_paths_f32) ----
+class AffineSemiGlobalSampler(torch.nn.Module):
+    """Alignments drawn from the POSTERIOR that AffineSemiGlobalDecoder(free=...) defines, on a ROCm device in float32: a path from a
+    start cell to an end cell under the free end gaps has probability exp(score - Vt) (include/sdp.h:
+    sdp_affine_semiglobal_end_table_f32, sdp_affine_semiglobal_sample_paths_f32).  decode() of that decoder returns
+    the marginals of this distribution, HardAffineSemiGlobalDecoder(free=...).optimal_paths() its mode.
+
+        free="y"     a sample starts in any cell of row 1 and ends in any cell of row n -- alternative placements of a whole query x
+                     inside a longer target y;
+        free="x"     the same for rows: it starts in any cell of column 1 and ends in any cell of column m;
+        free="both"  both: overlap alignment.
+
+    Any other `free` raises ValueError; for no free end there is AffineGlobalDecoder.sample_paths.  One forward sweep, one table of
+    the end cells' running weights and one walk per sample; the end cell is drawn, and a walk stops in plane m on a free border.
+    sample_paths / sample_alignments: the signatures, return tuples and formats of AffineGlobalDecoder's.
+    Inputs, lengths, forbidden gaps, the pair without a path and the empty pair (every sample empty) are AffineSemiGlobalDecoder's.
+    Not built: the second order of the semi-global operator, sampling of problems swept transposed (M above the column limit:
+    ValueError), float64, the `distributed` wrappers, `search_scores`, `losses.decode_loss`."""
+
+    def __init__(self, free="y"):
+        super().__init__()
+        if free not in _FREE_ENDS:
+            raise ValueError(f"free must be 'y', 'x' or 'both', got {free!r} (for no free end there is AffineGlobalDecoder)")
+        self.free = free
+        self.free_ends = _FREE_ENDS[free]
+
+    def forward(self, theta, gap_open, gap_extend, num_samples, lengths=None, seed=0, sample0=0):
+        """sample_paths(...)"""
+        return self.sample_paths(theta, gap_open, gap_extend, num_samples, lengths, seed, sample0)
+
+    def sample_paths(self, theta, gap_open, gap_extend, num_samples, lengths=None, seed=0, sample0=0, return_visits=False,
+                     return_gaps=False, return_ends=False):
+        """-> (Vt (B,), states (B, K, cap, 3) int32, counts (B, K) int32[, visits (B, N, M) int32][, opens, extends (B, N, M)
+        int32][, ends (B, K, 3) int32]), K = num_samples, device tensors without an autograd graph, in the formats of
+        AffineGlobalDecoder.sample_paths: sample k of pair b is states[b, k, :counts[b, k]], rows (i, j, plane), start first (rows
+        between the list and the last one are unspecified); states[b, k, cap - 1] is (number of path cells, i, j of the START
+        cell: where the sample places the query), (0, -1, -1) for an empty sample, which has counts = 0: every sample of an empty
+        pair (Vt = 0) and of a pair without a path (Vt = -inf).  The start cell carries plane m (1).  visits: how many of the K
+        paths pass through each cell; opens / extends (return_gaps): how many of them enter it through a gap step that opens /
+        extends a gap -- over K they estimate E, GO and GX of AffineSemiGlobalDecoder for Et = 1.  ends: the drawn end cell and
+        the plane the path ends in, (-1, -1, -1) for an empty sample.
+        The draws are reproducible: sample k is sample number sample0 + k of pair b under `seed` (a counter-based generator: 64
+        samples at sample0 = 0 are 32 at 0 followed by 32 at 32).
+        Problems wider than the column limit are swept transposed by AffineSemiGlobalDecoder; sampling them is NOT built (the draw
+        must not depend on the sweep direction): ValueError."""
+        _validate(theta, gap_open, gap_extend)
+        K = int(num_samples)
+        if K < 1:
+            raise ValueError(f"num_samples must be positive, got {num_samples}")
+        eng = _engine.get_engine()
+        if theta.shape[2] > eng.max_cols():
+            raise ValueError(f"sample_paths is out of scope for problems swept transposed (M = {theta.shape[2]} exceeds the column "
+                             f"limit {eng.max_cols()}): sampling on a transposed state is not built")
+        shape = tuple(theta.shape)
+        with torch.no_grad():
+            Vt, state = eng.affine_semiglobal_forward(theta.detach(), gap_open.detach(), gap_extend.detach(), self.free_ends, lengths)
+            ecdf = eng.affine_semiglobal_end_table(state, shape, self.free_ends, lengths)
+            states, counts, visits, opens, extends, ends = eng.affine_semiglobal_sample_paths(
+                state, ecdf, shape, self.free_ends, K, lengths, seed=seed, sample0=sample0, want_visits=bool(return_visits),
+                want_opens=bool(return_gaps), want_extends=bool(return_gaps), want_ends=bool(return_ends))
+            states = left_aligned(states, counts)
+        return ((Vt, states, counts) + ((visits,) if return_visits else ()) + ((opens, extends) if return_gaps else ())
+                + ((ends,) if return_ends else ()))
+
+    def sample_alignments(self, theta, gap_open, gap_extend, num_samples, lengths=None, seed=0, sample0=0):
+        """sample_paths() as lists: (Vt, list of B lists of K lists of (i, j, plane)); an empty sample is an empty list."""
+        Vt, states, counts = self.sample_paths(theta, gap_open, gap_extend, num_samples, lengths, seed, sample0)
+        states, counts = states.cpu().numpy(), counts.cpu().numpy()
+        return Vt, [[[tuple(int(v) for v in row) for row in states[b, k, :counts[b, k]]] for k in range(counts.shape[1])]
+                    for b in range(counts.shape[0])]

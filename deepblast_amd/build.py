@@ -22,6 +22,7 @@ SRC = [KERNELS, os.path.join(HERE, "csrc", "sdp_aux.hip"), os.path.join(HERE, "c
        os.path.join(HERE, "csrc", "sdp_affine_local.hip"), os.path.join(HERE, "csrc", "sdp_affine_local_adj.hip"), os.path.join(HERE, "csrc", "sdp_affine_local_sample.hip"),
        os.path.join(HERE, "csrc", "sdp_hard_affine.hip"), os.path.join(HERE, "csrc", "sdp_affine_global.hip"), os.path.join(HERE, "csrc", "sdp_affine_global_adj.hip"),
        os.path.join(HERE, "csrc", "sdp_affine_global_sample.hip"), os.path.join(HERE, "csrc", "sdp_affine_semiglobal.hip"),
+       os.path.join(HERE, "csrc", "sdp_affine_semiglobal_sample.hip"),
        os.path.join(HERE, "csrc", "sdp_api.hip")]
 HDR = [os.path.join(HERE, "csrc", "sdp_kernels.h"), os.path.join(HERE, "csrc", "sdp_device.h"), os.path.join(HERE, "csrc", "sdp_builds.def"), os.path.join(HERE, "csrc", "sdp_hard.h"),
        os.path.join(HERE, "csrc", "sdp_gap.h"), os.path.join(HERE, "csrc", "sdp_sample.h"), os.path.join(HERE, "csrc", "sdp_soft_local.h"),
@@ -29,7 +30,7 @@ HDR = [os.path.join(HERE, "csrc", "sdp_kernels.h"), os.path.join(HERE, "csrc", "
        os.path.join(HERE, "csrc", "sdp_sparsemax.h"), os.path.join(HERE, "csrc", "sdp_affine_local.h"), os.path.join(HERE, "csrc", "sdp_affine_local_sample.h"),
        os.path.join(HERE, "csrc", "sdp_hard_affine.h"), os.path.join(HERE, "csrc", "sdp_affine_global.h"),
        os.path.join(HERE, "csrc", "sdp_affine_global_device.h"),
-       os.path.join(HERE, "csrc", "sdp_affine_global_sample.h"),
+       os.path.join(HERE, "csrc", "sdp_affine_global_sample.h"), os.path.join(HERE, "csrc", "sdp_affine_semiglobal_sample.h"),
        os.path.join(ROOT, "include", "sdp.h")]
 OUT = os.path.join(HERE, "libsdp_hip.so")
 

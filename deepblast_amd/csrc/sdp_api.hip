@@ -19,6 +19,7 @@
 #include "sdp_sparsemax.h"
 #include "sdp_affine_global.h"
 #include "sdp_affine_global_sample.h"
+#include "sdp_affine_semiglobal_sample.h"
 #include "sdp_affine_local.h"
 #include "sdp_affine_local_sample.h"
 #include "sdp_hard_affine.h"
@@ -885,6 +886,9 @@ const char *sdp_kernel_name(int kernel_id)
     case sdp_affine_global::ID_SEMI_FWD: return "sdp_affine_semiglobal_fwd_kernel";
     case sdp_affine_global::ID_SEMI_VAL: return "sdp_affine_semiglobal_val_kernel";
     case sdp_affine_global::ID_SEMI_BWD: return "sdp_affine_semiglobal_bwd_kernel";
+    // sampling from its posterior (csrc/sdp_affine_semiglobal_sample.hip)
+    case sdp_affine_semiglobal_sample::ID_END_TABLE: return "sdp_affine_semiglobal_end_table_kernel";
+    case sdp_affine_semiglobal_sample::ID_SAMPLE: return "sdp_affine_semiglobal_sample_kernel";
     }
     return nullptr;
 }
@@ -2160,6 +2164,41 @@ int sdp_affine_global_sample_paths_f32(const void *state, int32_t *states, int32
     g.states = states, g.counts = counts, g.visits = visits, g.opens = opens, g.extends = extends, g.ends = ends, g.lens = lens;
     g.seed = seed, g.B = B, g.N = N, g.M = M, g.K = K, g.sample0 = sample0, g.cap = cap;
     return strip_launch(sdp_affine_global_sample_kernel, "sdp_affine_global_sample_kernel", (unsigned)waves, SAMPLE_WAVES, 0, stream, g);
+}
+
+// ---- alignments sampled from the semi-global posterior (csrc/sdp_affine_semiglobal_sample.hip): the table of the end cells' running
+// weights, one wave per pair, and one walk per sample from a drawn end cell to a start cell; free_ends = 0 is accepted (one candidate)
+static_assert(sdp_affine_semiglobal_sample::LANES == sdp_affine_global_sample::LANES, "the samplers launch the same workgroups");
+int sdp_affine_semiglobal_end_table_f32(const void *state, float *ecdf, int B, int N, int M, const int32_t *lens, int free_ends,
+                                        int flags, int device, void *stream)
+{
+    if (!state || !ecdf) return fail(SDP_E_NULLPTR, "sdp_affine_semiglobal_end_table_f32: null pointer (state, ecdf)");
+    if (int rc = affine_semiglobal_args(B, N, M, free_ends, flags)) return rc;
+    if (int rc = use_device(device)) return rc;
+    return strip_launch(sdp_affine_semiglobal_end_table_kernel, "sdp_affine_semiglobal_end_table_kernel", (unsigned)B, SAMPLE_WAVES, 0,
+                        stream, static_cast<const float4 *>(state), ecdf, lens, N, M, free_ends);
+}
+
+int sdp_affine_semiglobal_sample_paths_f32(const void *state, const float *ecdf, int32_t *states, int32_t *counts, int32_t *visits,
+                                           int32_t *opens, int32_t *extends, int32_t *ends, int B, int N, int M, int K, int sample0,
+                                           uint64_t seed, const int32_t *lens, int free_ends, int flags, int device, void *stream)
+{
+    if (!state || !ecdf || (states && !counts) || (!states && !counts && !visits && !opens && !extends && !ends))
+        return fail(SDP_E_NULLPTR, "sdp_affine_semiglobal_sample_paths_f32: null pointer (state, ecdf; states with counts, or visits, or "
+                                   "opens, or extends, or ends)");
+    if (int rc = affine_semiglobal_args(B, N, M, free_ends, flags)) return rc;
+    if (K < 1 || sample0 < 0 || (long long)sample0 + K > 0x7fffffffLL)
+        return fail(SDP_E_SHAPE, "sdp_affine_semiglobal_sample_paths_f32: K must be positive, sample0 non-negative and sample0 + K below 2^31");
+    const int cap = sdp_traceback_capacity(N, M);
+    const size_t lim = 0x7fffffffu, waves = (size_t)B * ((K + sdp_affine_semiglobal_sample::LANES - 1) / sdp_affine_semiglobal_sample::LANES);
+    if ((states && (size_t)B * K * cap * 3 > lim) || (size_t)B * K * 3 > lim || waves > lim)
+        return fail(SDP_E_TOOBIG, "sdp_affine_semiglobal_sample_paths_f32: an output exceeds 2^31 elements");
+    if (int rc = use_device(device)) return rc;
+    sdp_affine_semiglobal_sample::Params g = {};
+    g.state = static_cast<const float4 *>(state), g.ecdf = ecdf;
+    g.states = states, g.counts = counts, g.visits = visits, g.opens = opens, g.extends = extends, g.ends = ends, g.lens = lens;
+    g.seed = seed, g.B = B, g.N = N, g.M = M, g.K = K, g.sample0 = sample0, g.cap = cap, g.free_ends = free_ends;
+    return strip_launch(sdp_affine_semiglobal_sample_kernel, "sdp_affine_semiglobal_sample_kernel", (unsigned)waves, SAMPLE_WAVES, 0, stream, g);
 }
 
 // ---- the sparsemax operator (csrc/sdp_sparsemax.hip): the global recurrence under the sparse smoothed maximum, first order ----

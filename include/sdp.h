@@ -972,7 +972,9 @@ int sdp_affine_global_backward_f32(const void *state, const float *Et, float *E,
  *   free_ends  bit 0 = x, bit 1 = y; any other bit: SDP_E_VARIANT.
  *   flags      this family defines none: any bit is refused (SDP_E_VARIANT).
  * Launch geometry, LDS, argument checks, codes and limits are those of sdp_affine_global_*.  The hard-max member and its
- * walk are sdp_hard_affine_semiglobal_* above.  NOT built: sampling, the second order, float64, a one-score form, the reference's zero border. */
+ * walk are sdp_hard_affine_semiglobal_* above; sampling from the posterior is sdp_affine_semiglobal_end_table_f32 and
+ * sdp_affine_semiglobal_sample_paths_f32 below.  NOT built: the second order, sampling of a problem swept transposed, float64, a
+ * one-score form, the reference's zero border. */
 size_t sdp_affine_semiglobal_state_bytes(int B, int N, int M);
 int sdp_affine_semiglobal_forward_f32(const float *theta, const float *gap_open, const float *gap_extend, void *state, float *Vt, int B,
                                       int N, int M, const int32_t *lens, int free_ends, int flags, int device, void *stream);
@@ -980,6 +982,45 @@ int sdp_affine_semiglobal_forward_value_f32(const float *theta, const float *gap
                                             int M, const int32_t *lens, int free_ends, int flags, int device, void *stream);
 int sdp_affine_semiglobal_backward_f32(const void *state, const float *Et, float *E, float *GO, float *GX, int B, int N, int M,
                                        const int32_t *lens, int free_ends, int flags, int device, void *stream);
+
+/* Alignments SAMPLED from the semi-global posterior (csrc/sdp_affine_semiglobal_sample.hip): what
+ * sdp_affine_global_sample_paths_f32 (below) is to the global operator, with two changes -- the END CELL is drawn, and a walk STOPS on
+ * a free border.  (Added after SDP_VERSION 106 without a version change: look the symbols up.  sdp_kernel_name answers 211 for the
+ * table kernel and 212 for the sample kernel; 209, 210 and 213 answer NULL.)  A path from a start cell to an end cell has
+ * probability exp(score - Vt).  sdp_affine_semiglobal_forward_f32 has left the normalised end weights w_s = exp(V_s - Vt) in the
+ * fourth word of the three records of every end cell: the entries take no Vt.  Planes, cells (0-based), (n, m), U and the
+ * numbering of t are those of sdp_affine_global_sample_paths_f32.
+ * CANDIDATES: the end cells of pair b are numbered e in [0, n + m - 1): e < n is cell (e, m-1) -- column m from the top, the corner
+ * at e = n-1 --, e >= n is cell (n-1, e-n) -- row n, columns 0 .. m-2.  The weight of candidate e is ws_e = (wx + wy) + wm, in this
+ * order of fp32 adds, of the fourth words of its three records, and exactly 0 where the cell is no end cell under free_ends (decided
+ * from the flags, such a record is not read): free_ends = 1: only e < n is live; 2: only e >= n-1; 0: only e = n-1; 3: all.
+ * sdp_affine_semiglobal_end_table_f32 writes ecdf (B, N + M) float32: ecdf[b, e] = ws_0 + ... + ws_e by SEQUENTIAL fp32 adds in
+ * increasing e, for e < n + m - 1; the other entries are not written, and a pair with n < 1 or m < 1 writes nothing.  Non-decreasing
+ * by construction, no floating-point atomics, the same bits on every call.  One table serves any number of sample launches.
+ * sdp_affine_semiglobal_sample_paths_f32, sample k of pair b:
+ * END CELL, t = 0: total = ecdf[b, n+m-2]; n < 1, m < 1 or total = 0: the sample is EMPTY.  g = U(.., 0) * total (one fp32 product);
+ * e is the first index with g < ecdf[b, e]; if there is none, the first index whose ecdf equals total (the last candidate of
+ * non-zero weight).  A candidate of weight 0 is never drawn.  U(.., 1) is not used.
+ * END PLANE, t = 2: the expression of sdp_affine_global_sample_paths_f32 on the fourth words of that cell's three records.
+ * WALK, t = 3, 4, ...: that entry's walk, record for record, with another stop rule.  The walk is at a START CELL at cell (0, 0),
+ * in plane m of a cell of row 0 under bit 1 (y), and in plane m of a cell of column 0 under bit 0 (x): there NO record is read and
+ * NO uniform is consumed, the cell is recorded as plane m and counts into visits (not into opens or extends), and the walk ends.
+ * OUTPUTS: states, counts, visits, opens, extends and ends in that entry's formats, right alignment, last row (number of path
+ * cells, i, j of the first cell) and integer atomics; ends is (i, j, plane) of the drawn end cell, (-1, -1, -1) for an empty sample.
+ *   state      what sdp_affine_semiglobal_forward_f32 wrote with the same B, N, M, lens and free_ends.
+ *   ecdf       (B, N + M) float32; the sample entry reads what the table entry wrote for the same state and arguments.
+ *   free_ends  bit 0 = x, bit 1 = y; any other bit: SDP_E_VARIANT.  0 is legal: one live candidate, and the samples are the bits of
+ *              sdp_affine_global_sample_paths_f32 on that state.
+ *   flags      none is defined: any bit is refused (SDP_E_VARIANT).
+ * Null pointers (state, ecdf; states with counts, or one other output), K, sample0, sizes and M: the codes and limits of
+ * sdp_affine_global_sample_paths_f32.  All arguments are checked before any device call.  The table: one wave per pair; the
+ * samples: one wave per 64 samples of a pair; no LDS.  NOT built: the second order of the semi-global operator, sampling a problem
+ * that was swept TRANSPOSED, float64. */
+int sdp_affine_semiglobal_end_table_f32(const void *state, float *ecdf, int B, int N, int M, const int32_t *lens, int free_ends,
+                                        int flags, int device, void *stream);
+int sdp_affine_semiglobal_sample_paths_f32(const void *state, const float *ecdf, int32_t *states, int32_t *counts, int32_t *visits,
+                                           int32_t *opens, int32_t *extends, int32_t *ends, int B, int N, int M, int K, int sample0,
+                                           uint64_t seed, const int32_t *lens, int free_ends, int flags, int device, void *stream);
 
 /* Its SECOND ORDER (csrc/sdp_affine_global_adj.hip): the adjoint pair, what sdp_affine_local_adjoint_* is to the local
  * operator, with the global operator's start and end.  (Added after SDP_VERSION 106 without a version change: look the symbols up.
